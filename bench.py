@@ -24,7 +24,15 @@ the ranks torchrun made are used as they are.  Paths shard by contiguous global 
 (reference: n_gpus is just an argument, examples/benchmark_mc_gpu.cpp:52-69, split at
 src/simulations.cu:599-607); the only exchange is the statistics record, merged in rank order.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints
+the headline (`value`, `ms_per_step`, ...) with the statistics of the last step (`result`).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy:
+  final_values  the per-path final values (float32; above 2^22 paths a fixed, seeded sample of 2^22 paths)
+  chunk_mean, chunk_var   the per-256-path block means / variances (float32; sampled the same way)
+  stats         float64 [count, below, underflow, overflow, sum, sumsq, min, max] of the statistics record
+  histogram     float64 bucket counts of the statistics record
+only those the chosen `--outputs` produces; with N > 1 ranks rank 0 writes its own shard and the merged record.
+`--full` adds everything beside the headline, each measured after the timed region:
   roofline      HBM roofline of the dominant kernel (paths_kernel): algorithmic bytes
                 (4 B per path, the coalesced final-value store) / its HIP-event time.
                 The kernel is VALU-bound by design, so this fraction is tiny; the
@@ -32,7 +40,9 @@ Prints ONE JSON line on rank 0.  Extra objects:
   cpu_baseline  the reference's CPU algorithm (oracle engine R: mt19937 + Lemire +
                 update_fund, OpenMP hw-1 threads) timed on this host on a bounded sample,
                 with deterministic seeds (`value`) and as the reference really does it,
-                one std::random_device per path (`as_reference_value`).
+                one std::random_device per path (`as_reference_value`); --no-cpu-baseline leaves it out.
+  hbm_bound_kernels   the path's HBM-bound neighbours (statistics, quartiles, keepdata) timed live.
+  group_single_process   N > 1: the same workload once more through the one-process group launcher.
 """
 import argparse
 import json
@@ -322,6 +332,49 @@ def _build_digest():
     return _lib.build_digest()
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------
+
+DUMP_SAMPLE = 1 << 22      # per-path outputs longer than this are written as a sample of this many values (16 MB of f32)
+DUMP_SAMPLE_SEED = 0x0D0C  # the sample's positions depend on the output's length only: the same in every run and build
+
+
+def sample_positions(n):
+    """Positions of a length-n output that --dump-outputs writes: None (all of them) up to DUMP_SAMPLE, else
+    DUMP_SAMPLE draws from a fixed-seed generator, sorted, repeats dropped."""
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def _sampled(values):
+    """A device tensor or host array of one value per position -> host float32 array (sampled as above)."""
+    pos = sample_positions(len(values))
+    if pos is None:
+        return np.array(values.cpu().numpy() if hasattr(values, "cpu") else values, dtype=np.float32)
+    if hasattr(values, "cpu"):
+        import torch
+        return values[torch.from_numpy(pos).to(values.device)].cpu().numpy().astype(np.float32)
+    return np.asarray(values[pos], dtype=np.float32)
+
+
+def dump_outputs(out_dir, final=None, chunk_mean=None, chunk_var=None, stats=None):
+    """Writes the last timed step's outputs as out_dir/<name>.npy (see the module docstring); returns the names."""
+    arrays = {}
+    if final is not None:
+        arrays["final_values"] = _sampled(final)
+    if chunk_mean is not None:
+        arrays["chunk_mean"] = _sampled(chunk_mean)
+        arrays["chunk_var"] = _sampled(chunk_var)
+    if stats is not None:
+        arrays["stats"] = np.array([stats.count, stats.below, stats.underflow, stats.overflow, stats.sum, stats.sumsq,
+                                    stats.min, stats.max], dtype=np.float64)
+        arrays["histogram"] = np.asarray(stats.hist, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 # ---- launching the ranks ---------------------------------------------------------------------
 
 
@@ -331,10 +384,11 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def launch_ranks(n_ranks, argv):
+def launch_ranks(n_ranks, argv, full=False):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes, relay rank 0's
-    stdout (the JSON line), return the worst return code.  This parent never initialises the GPU (it
-    has not even imported torch) and nothing here execs: children are ordinary subprocesses."""
+    stdout (the JSON line), return the worst return code; with `full` (--full) the group launcher's run follows.  This
+    parent never initialises the GPU (it has not even imported torch) and nothing here execs: children are ordinary
+    subprocesses."""
     port = _free_port()
     procs = []
     for r in range(n_ranks):
@@ -382,7 +436,7 @@ def launch_ranks(n_ranks, argv):
     # ONE JSON line on stdout; whatever else rank 0 printed there (gloo's connection banner) goes to stderr
     lines = out0.decode(errors="replace").splitlines()
     for i, line in enumerate(lines):
-        if rc == 0 and line.startswith('{"metric"') and "--launch-check" not in argv and not os.environ.get("SMMC_BENCH_NO_GROUP"):
+        if full and rc == 0 and line.startswith('{"metric"') and "--launch-check" not in argv and not os.environ.get("SMMC_BENCH_NO_GROUP"):
             # the ranks are gone: the SAME workload once more through the one-process C-ABI launcher
             # (smmc_group_*, RCCL all-reduce and host merge), from a fresh child of this GPU-less parent
             try:
@@ -472,10 +526,11 @@ def run_group_child(n_gpus, argv, timeout_s=None):
         if skip:
             skip -= 1
             continue
-        if a in ("--gpus", "--backend", "--hash-shards"):
+        if a in ("--gpus", "--backend", "--hash-shards", "--dump-outputs"):
             skip = 1
             continue
-        if a.startswith(("--gpus=", "--backend=", "--hash-shards=")) or a in ("--rehearse-rccl", "--no-cpu-baseline"):
+        if (a.startswith(("--gpus=", "--backend=", "--hash-shards=", "--dump-outputs="))
+                or a in ("--rehearse-rccl", "--no-cpu-baseline", "--full")):
             continue
         keep.append(a)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE",
@@ -556,7 +611,14 @@ def main():
     ap.add_argument("--paths-per-gpu", type=int, default=None, help="weak scaling: this many paths on every rank")
     ap.add_argument("--total-paths", type=int, default=None, help="strong scaling: this many paths sharded over the ranks")
     ap.add_argument("--periods", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure after the timed region: the roofline and VALU pricing of the "
+                         "timed kernel, its HBM-bound neighbour kernels, the CPU baseline and (N > 1) the one-process "
+                         "group launcher on the same workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64, per-path outputs above 2^22 values as a fixed seeded sample; see the module docstring)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl = RCCL (the real multi-GPU run); gloo lets several ranks rehearse on ONE GPU")
     ap.add_argument("--outputs", choices=["all", "final", "stats", "host"], default=None,
@@ -589,7 +651,7 @@ def main():
     have_ranks = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not have_ranks:
         # no launcher made our ranks: make them (BEFORE anything in this process touches torch or HIP)
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+        sys.exit(launch_ranks(args.gpus, sys.argv[1:], full=args.full))
 
     world = int(os.environ.get("WORLD_SIZE", "1")) if have_ranks else 1
     rank = int(os.environ.get("RANK", "0")) if have_ranks else 0
@@ -598,6 +660,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but the launcher made WORLD_SIZE={world} ranks")
     if args.launch_check:
         return launch_check(args, world, rank)
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     preset = CONFIGS[args.config]
     mode_name = args.mode or ("table" if args.stream == "ref" else preset["mode"])
@@ -684,7 +748,7 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    eng.timing(True)
+    eng.timing(True)  # on in every run (event pair + clock probe per launch): the timed steps are the same with --full
     t0 = time.perf_counter()
     last = None
     for _ in range(args.steps):
@@ -719,13 +783,6 @@ def main():
             host_digests = [digest(host_final[f:f + c]) for f, c in (shard_range(n, args.hash_shards, i)
                                                                       for i in range(args.hash_shards))]
 
-    extra = None
-    if rank == 0 and world == 1 and want_final:
-        try:
-            extra = hbm_bound_kernels(eng, S, final, mode)
-        except Exception as ex:  # never lose the headline line to an optional measurement
-            extra = {"error": str(ex)}
-
     stats = None
     if want_stats and last is not None:
         if use_dist:
@@ -734,44 +791,58 @@ def main():
             stats = eng.read_stats(last.stats_raw)
         assert stats.count == n_all, (stats.count, n_all)
 
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, final=host_final if to_host else final,
+                              chunk_mean=last.chunk_mean if want_chunks else None,
+                              chunk_var=last.chunk_var if want_chunks else None, stats=stats)
+
+    extra = None
+    if args.full and rank == 0 and world == 1 and want_final:
+        try:
+            extra = hbm_bound_kernels(eng, S, final, mode)
+        except Exception as ex:  # never lose the headline line to an optional measurement
+            extra = {"error": str(ex)}
+
     if rank == 0:
         value = n_all * args.steps / dt
-        k_s = kernel_ms / 1e3  # summed kernel time of this rank's launches in the timed region
-        k_avg_s = k_s / max(launches, 1)
-        paths_per_launch = n * args.steps / max(launches, 1)  # host pipeline: one launch per 2^22-path chunk
-        writes_final = want_final or to_host
-        bytes_per_launch = 4.0 * paths_per_launch if writes_final else 0.0
-        achieved = bytes_per_launch / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(mode_name if args.stream != "ref" else "ref", n, periods, outputs)
-        insts = VALU_INSTS_PER_STEP[mode_name]
         kind = eng.divide_kind(sim)
-        kernel_name = "paths_kernel"
-        if args.stream == "ref":
-            windowed = periods <= REF_TREE_MAX
-            kernel_name = ("ref_windowed_kernel" if periods <= REF_WINDOW[2] else
-                           "ref_tree_kernel" if windowed else "ref_generic_kernel")
-            # the generic kernel (longer paths still) keeps its generator states in memory and is not priced here
-            insts = None
-            if windowed and periods and kind in (0, 2):  # fast / checked; the IEEE divide is not counted
-                insts = ref_valu_per_path(periods) / periods + (REF_CHECK_VALU / 8 if kind == 2 else 0.0)
-        elif args.stream == "2":
-            insts = None  # round 1's stream: counts in DESIGN.md section 5, not tracked by the ISA test
-        elif kind == 2:  # checked
-            insts = insts + VALU_CHECK_PER_STEP[mode_name]
-        elif kind == 1:  # IEEE divide: not counted
-            insts = None
-        valu_ach = paths_per_launch * periods * insts / k_avg_s if k_avg_s > 0 and insts else 0.0
-        # the same loop priced with this round's measured issue cost of every opcode (half-rate multiplies,
-        # conversions, SDWA ...: tools/valu_model.py over profiles/r04/ubench_ops.jsonl), against the kernel's
-        # time at the clock the chip held while it ran -- sampled live by the launches' own workgroups
-        model, model_src = (pmc_traffic(mode_name, n, periods, outputs, want="valu") if args.stream == "3" and kind == 0
-                            else (None, None))
-        weighted_frac = weighted_frac_measured = None
-        if model and k_avg_s > 0 and held_clock_ghz > 0:
-            simds = eng.geometry()[2] * 4
-            blocks_per_simd = paths_per_launch * periods / model["periods_per_block"] / 64.0 / simds
-            weighted_frac = model["class_clk_per_block"] * blocks_per_simd / (k_avg_s * held_clock_ghz * 1e9)
-            weighted_frac_measured = model["model_clk_per_block"] * blocks_per_simd / (k_avg_s * held_clock_ghz * 1e9)
+        k_s = kernel_ms / 1e3  # summed kernel time of this rank's launches in the timed region
+        if args.full:  # the timed kernel priced against the HBM and VALU roofs
+            k_avg_s = k_s / max(launches, 1)
+            paths_per_launch = n * args.steps / max(launches, 1)  # host pipeline: one launch per 2^22-path chunk
+            writes_final = want_final or to_host
+            bytes_per_launch = 4.0 * paths_per_launch if writes_final else 0.0
+            achieved = bytes_per_launch / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
+            traffic, traffic_src = pmc_traffic(mode_name if args.stream != "ref" else "ref", n, periods, outputs)
+            insts = VALU_INSTS_PER_STEP[mode_name]
+            kernel_name = "paths_kernel"
+            if args.stream == "ref":
+                windowed = periods <= REF_TREE_MAX
+                kernel_name = ("ref_windowed_kernel" if periods <= REF_WINDOW[2] else
+                               "ref_tree_kernel" if windowed else "ref_generic_kernel")
+                # the generic kernel (longer paths still) keeps its generator states in memory and is not priced here
+                insts = None
+                if windowed and periods and kind in (0, 2):  # fast / checked; the IEEE divide is not counted
+                    insts = ref_valu_per_path(periods) / periods + (REF_CHECK_VALU / 8 if kind == 2 else 0.0)
+            elif args.stream == "2":
+                insts = None  # round 1's stream: counts in DESIGN.md section 5, not tracked by the ISA test
+            elif kind == 2:  # checked
+                insts = insts + VALU_CHECK_PER_STEP[mode_name]
+            elif kind == 1:  # IEEE divide: not counted
+                insts = None
+            valu_ach = paths_per_launch * periods * insts / k_avg_s if k_avg_s > 0 and insts else 0.0
+            # the same loop priced with this round's measured issue cost of every opcode (half-rate multiplies,
+            # conversions, SDWA ...: tools/valu_model.py over profiles/r04/ubench_ops.jsonl), against the kernel's
+            # time at the clock the chip held while it ran -- sampled live by the launches' own workgroups
+            model, model_src = (pmc_traffic(mode_name, n, periods, outputs, want="valu") if args.stream == "3" and kind == 0
+                                else (None, None))
+            weighted_frac = weighted_frac_measured = None
+            if model and k_avg_s > 0 and held_clock_ghz > 0:
+                simds = eng.geometry()[2] * 4
+                blocks_per_simd = paths_per_launch * periods / model["periods_per_block"] / 64.0 / simds
+                weighted_frac = model["class_clk_per_block"] * blocks_per_simd / (k_avg_s * held_clock_ghz * 1e9)
+                weighted_frac_measured = model["model_clk_per_block"] * blocks_per_simd / (k_avg_s * held_clock_ghz * 1e9)
         if world == 1:
             par = "single GPU"
         elif to_host:
@@ -801,32 +872,35 @@ def main():
                        "outputs": outputs, "seed": hex(SEED), "stream": args.stream,
                        "divide": ("fast", "exact", "checked")[kind],
                        "parallelism": par},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernel_name, "kernel_ms": k_avg_s * 1e3, "launches": launches,
-                         "bytes_per_launch": bytes_per_launch,
-                         "note": "VALU-bound kernel: 4 B of HBM traffic per path by construction; see valu"},
-            "valu": {"bound": "valu-issue", "achieved": valu_ach, "peak": VALU_PEAK_LANEOPS, "unit": "lane-ops/s",
-                     "frac": valu_ach / VALU_PEAK_LANEOPS, "insts_per_path_period": insts,
-                     # the roofline's x axis: VALU lane-operations per algorithmic HBM byte of this launch
-                     # (4 bytes written per path), against the ridge point peak ops / peak bytes
-                     "arithmetic_intensity": (periods * insts / 4.0) if (insts and writes_final) else None,
-                     "ridge_point": VALU_PEAK_LANEOPS / (HBM_PEAK_GBS * 1e9),
-                     "weighted_frac": weighted_frac, "weighted_frac_measured_costs": weighted_frac_measured,
-                     "weighted_model": ({"class_clk_per_block": model["class_clk_per_block"],
-                                         "half_rate_insts_per_block": model["half_rate_insts_per_block"],
-                                         "measured_cost_clk_per_block": model["model_clk_per_block"],
-                                         "periods_per_block": model["periods_per_block"],
-                                         "valu_insts_per_block": model["valu_insts_per_block"], "source": model_src}
-                                        if model else None),
-                     "held_clock_ghz": held_clock_ghz or None,
-                     "held_clock_source": ("live: s_memtime / s_memrealtime of every workgroup of the timed launches "
-                                           "(smmc_engine_kernel_clock)") if held_clock_ghz else None,
-                     "note": "frac is unweighted: every VALU instruction counted as one 2-clock issue slot at the 2.4 GHz peak; "
-                             "weighted_frac prices every opcode at its class cost (2 clocks full rate, 4 half rate: the "
-                             "classes measured by tools/ubench_ops.hip) and uses the clock the chip held; "
-                             "weighted_frac_measured_costs uses the probes' measured costs, which carry their own overhead; arithmetic_intensity in lane-ops per HBM byte"},
         }
+        if args.full:
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": kernel_name, "kernel_ms": k_avg_s * 1e3, "launches": launches,
+                             "bytes_per_launch": bytes_per_launch,
+                             "note": "VALU-bound kernel: 4 B of HBM traffic per path by construction; see valu"},
+                "valu": {"bound": "valu-issue", "achieved": valu_ach, "peak": VALU_PEAK_LANEOPS, "unit": "lane-ops/s",
+                         "frac": valu_ach / VALU_PEAK_LANEOPS, "insts_per_path_period": insts,
+                         # the roofline's x axis: VALU lane-operations per algorithmic HBM byte of this launch
+                         # (4 bytes written per path), against the ridge point peak ops / peak bytes
+                         "arithmetic_intensity": (periods * insts / 4.0) if (insts and writes_final) else None,
+                         "ridge_point": VALU_PEAK_LANEOPS / (HBM_PEAK_GBS * 1e9),
+                         "weighted_frac": weighted_frac, "weighted_frac_measured_costs": weighted_frac_measured,
+                         "weighted_model": ({"class_clk_per_block": model["class_clk_per_block"],
+                                             "half_rate_insts_per_block": model["half_rate_insts_per_block"],
+                                             "measured_cost_clk_per_block": model["model_clk_per_block"],
+                                             "periods_per_block": model["periods_per_block"],
+                                             "valu_insts_per_block": model["valu_insts_per_block"], "source": model_src}
+                                            if model else None),
+                         "held_clock_ghz": held_clock_ghz or None,
+                         "held_clock_source": ("live: s_memtime / s_memrealtime of every workgroup of the timed launches "
+                                               "(smmc_engine_kernel_clock)") if held_clock_ghz else None,
+                         "note": "frac is unweighted: every VALU instruction counted as one 2-clock issue slot at the 2.4 GHz peak; "
+                                 "weighted_frac prices every opcode at its class cost (2 clocks full rate, 4 half rate: the "
+                                 "classes measured by tools/ubench_ops.hip) and uses the clock the chip held; "
+                                 "weighted_frac_measured_costs uses the probes' measured costs, which carry their own overhead; arithmetic_intensity in lane-ops per HBM byte"},
+            })
         if to_host:
             out["host_pipeline"] = {"bytes_to_host_per_step": 4.0 * n, "GBps_rank0": 4.0 * n * args.steps / dt / 1e9,
                                     "kernel_busy_frac": k_s / dt if dt > 0 else None, "pinned": True}
@@ -835,16 +909,18 @@ def main():
         if stats is not None:
             out["result"] = {"mean": stats.mean, "std": stats.std, "below_initial": stats.below,
                              "hist_total": int(stats.hist.sum()) + stats.underflow + stats.overflow}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if extra is not None:
             out["hbm_bound_kernels"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(table)
 
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not os.environ.get("SMMC_BENCH_CHILD") and not os.environ.get("SMMC_BENCH_NO_GROUP"):
+        if args.full and world > 1 and not os.environ.get("SMMC_BENCH_CHILD") and not os.environ.get("SMMC_BENCH_NO_GROUP"):
             # ranks made by an external launcher (torch.distributed.run): there is no GPU-less parent of ours, so
             # rank 0 -- its timed region over, its collectives done, its engine closed -- starts the fresh child
             # that runs the workload through the one-process C-ABI launcher (self-launched runs: the parent does)

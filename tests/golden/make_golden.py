@@ -11,9 +11,14 @@
                           BOTH modes, so the table-mode values of counter_stream_v3.json are NOT
                           those of round 1 (counter_stream_v2.json holds them, bit-unchanged).
                           Pinned to the oracle itself only.
+  ref_callers.json        `python tests/golden/make_golden.py ref_callers`: what the reference's own
+                          host helpers return / write on the inputs of tests/test_ref_callers_cpu.py
+                          (update_mean_std and update_count_below_min of examples/benchmark_mc_gpu.cpp,
+                          write_data_file and write_vector_file of src/helpers.cpp), executed from
+                          oracle/_ref/ (`make -C oracle _ref`, which needs the reference sources).
 
-The reference implementation could not be built here (see oracle/Makefile), so no
-fixture in this directory comes from an executed reference.
+The reference engine itself could not be built here (see oracle/Makefile); ref_callers.json is
+the only fixture in this directory that comes from executed reference code.
 """
 import json
 import os
@@ -81,6 +86,49 @@ def main():
     print("wrote fixtures")
 
 
+def ref_callers_inputs(table):
+    """The value sets tests/test_ref_callers_cpu.py feeds the reference's statistics helpers, and their thresholds."""
+    final = O.counter_mc(O.make_params(O.MODE_TABLE, 120, 200000, 31, table=table))["final"]
+    sets = [final, final[:1], final[:257], np.exp(np.random.default_rng(1).normal(7, 2, 50000)).astype(np.float32)]
+    return [(v, (1000.0, float(np.median(v)), 0.0, 1e30)) for v in sets]
+
+
+WRITER_RETURNS = [1.5, -2.25, 0.1, 1e-7, 12345.678, -0.0]  # tests/cpp/writers_check.cpp writes the same two vectors
+WRITER_VALUES = [1000.0, 1015.0, 992.1625, 993.154663, 1.0e9, 3.4e38, 1.17549435e-38]
+
+
+def ref_callers():
+    import ctypes as C
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_ref_callers_cpu import REF_SO, load_ref
+    L = load_ref()
+    stats = []
+    for v, thresholds in ref_callers_inputs(load_table()):
+        mean, std = C.c_float(), C.c_float()
+        L.ref_update_mean_std(v.ctypes.data_as(C.c_void_p), v.size, C.byref(mean), C.byref(std))
+        below = [int(L.ref_update_count_below_min(v.ctypes.data_as(C.c_void_p), v.size, t)) for t in thresholds]
+        stats.append({"n": int(v.size), "mean": float(mean.value), "std": float(std.value), "below": below})
+    r = np.array(WRITER_RETURNS, dtype=np.float32)
+    v = np.array(WRITER_VALUES, dtype=np.float32)
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            os.makedirs("outputs")
+            L.ref_write_data_file(b"theirs.csv", r.ctypes.data_as(C.c_void_p), r.size, v.ctypes.data_as(C.c_void_p), v.size)
+            L.ref_write_vector_file(b"outputs/theirs_vec.csv", v.ctypes.data_as(C.c_void_p), v.size)
+            C.CDLL(None).fflush(None)
+            data_file = open("outputs/theirs.csv").read()
+            vector_file = open("outputs/theirs_vec.csv").read()
+        finally:
+            os.chdir(cwd)
+    with open(os.path.join(HERE, "ref_callers.json"), "w") as f:
+        json.dump({"source": os.path.relpath(REF_SO, ROOT), "statistics": stats, "data_file": data_file,
+                   "vector_file": vector_file}, f, indent=1)
+    print("wrote ref_callers.json")
+
+
 def fnv1a(words):
     h = 0xCBF29CE484222325
     for w in np.asarray(words, dtype=np.uint32).tobytes():
@@ -89,4 +137,7 @@ def fnv1a(words):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_callers"]:
+        ref_callers()
+    else:
+        main()

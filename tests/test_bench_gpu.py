@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def _run(*flags, timeout=300):
 
 
 def test_bench_line_carries_the_contract_fields():
-    d = _run("--steps", "2", "--warmup", "1", "--paths-per-gpu", "4000000", "--no-cpu-baseline")
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--paths-per-gpu", "4000000", "--no-cpu-baseline")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -49,6 +50,69 @@ def test_bench_line_carries_the_contract_fields():
     y = d["hbm_bound_kernels"]["box_yardstick"]
     assert 1000 < y["fill_GBps"] < 8000 and 20 < y["sum_GBps"] < 8000  # the sum is over this run's 4e6 values: microseconds
     assert d["hbm_bound_kernels"]["keepdata"]["vs_box_fill"] == pytest.approx(d["hbm_bound_kernels"]["keepdata"]["GBps"] / y["fill_GBps"])
+
+
+def test_plain_run_prints_the_headline_only():
+    """A plain run sets up, warms up, times --steps steps and prints the headline; what is measured beside it
+    (pricing against the roofs, neighbour kernels, CPU baseline, group launcher) is --full's."""
+    d = _run("--steps", "3", "--warmup", "1", "--paths-per-gpu", "1000003")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["value"] == pytest.approx(1000003 * 3 / (d["ms_per_step"] * 3e-3), rel=1e-6)
+    assert d["result"]["hist_total"] == 1000003
+    for key in ("roofline", "valu", "hbm_bound_kernels", "cpu_baseline", "group_single_process", "dumped_outputs"):
+        assert key not in d, key
+
+
+def _oracle_paths(oracle, table, positions):
+    """The oracle's final value of single paths of bench.py's default workload (Gaussian, 360 periods)."""
+    import bench
+    return np.array([oracle.counter_mc(oracle.make_params(oracle.MODE_GAUSSIAN, 360, 1, bench.SEED, first_path=int(p),
+                                                          table=table))["final"][0] for p in positions], dtype=np.float32)
+
+
+def test_dump_outputs_are_the_oracle_values_and_repeat_bit_for_bit(tmp_path, oracle, table):
+    """--dump-outputs: the last timed step's final values, block means / variances and statistics record, the
+    same bits in a second run, and the final values and bucket counts those of the CPU oracle."""
+    import bench
+    n = 20011
+    lines = [_run("--steps", "2", "--warmup", "1", "--paths-per-gpu", str(n), "--dump-outputs", str(tmp_path / d))
+             for d in ("a", "b")]
+    names = ["chunk_mean", "chunk_var", "final_values", "histogram", "stats"]
+    assert lines[0]["dumped_outputs"] == lines[1]["dumped_outputs"] == names
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    for k, a in got.items():
+        assert a.dtype in (np.float32, np.float64), k
+        again = np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == again.dtype and np.array_equal(a.view(np.uint8), again.view(np.uint8)), k
+    o = oracle.counter_mc(oracle.make_params(oracle.MODE_GAUSSIAN, 360, n, bench.SEED, table=table, n_bins=100,
+                                             hist_lo=0.0, hist_hi=20000.0))
+    assert got["final_values"].dtype == np.float32 and got["final_values"].size == n
+    assert np.array_equal(got["final_values"].view(np.uint32), o["final"].view(np.uint32))
+    assert np.array_equal(got["histogram"], o["hist"].astype(np.float64))
+    cm, cv = oracle.chunk_mean_var(o["final"])
+    np.testing.assert_allclose(got["chunk_mean"], cm, rtol=1e-6)
+    np.testing.assert_allclose(got["chunk_var"], cv, rtol=1e-5, atol=1e-6 * float(np.max(cv) + 1))
+    assert got["stats"][0] == n and got["stats"][1] == o["stats"].below == lines[0]["result"]["below_initial"]
+    assert got["stats"][4] / n == pytest.approx(lines[0]["result"]["mean"], rel=1e-12)
+
+
+def test_dump_outputs_of_the_default_workload_stay_under_64_mb(tmp_path, oracle, table):
+    """The default workload (1e8 paths): its final values are written as the fixed sample of bench.sample_positions,
+    the 390625 block means and variances whole, all of it under 64 MB."""
+    import bench
+    n = bench.PATHS_PER_GPU
+    d = _run("--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path))
+    assert d["config"]["paths_rank0"] == n and d["steps"] == 1
+    assert sum(os.path.getsize(tmp_path / f"{k}.npy") for k in d["dumped_outputs"]) <= 64 << 20
+    pos = bench.sample_positions(n)
+    final = np.load(tmp_path / "final_values.npy")
+    assert final.dtype == np.float32 and final.size == pos.size > 0.9 * bench.DUMP_SAMPLE
+    assert np.load(tmp_path / "chunk_mean.npy").size == np.load(tmp_path / "chunk_var.npy").size == (n + 255) // 256
+    assert np.load(tmp_path / "histogram.npy").sum() + np.load(tmp_path / "stats.npy")[2:4].sum() == n
+    picks = np.linspace(0, pos.size - 1, 24).astype(np.int64)  # first, last and evenly spaced samples
+    want = _oracle_paths(oracle, table, pos[picks])
+    assert np.array_equal(final[picks].view(np.uint32), want.view(np.uint32))
 
 
 def test_rccl_collectives_of_the_multi_rank_path_run_with_one_rank():
@@ -173,8 +237,8 @@ def test_self_launched_run_attaches_the_one_process_group_launcher():
     one-GPU box both shards sit on device 0, so the host-merge leg runs and the RCCL leg (which needs distinct
     devices) reports why it cannot -- as an error string inside the object, never as a lost line."""
     total = 5_000_001
-    two = _run("--gpus", "2", "--backend", "gloo", "--config", "3", "--total-paths", str(total), "--steps", "2", "--warmup", "1",
-               timeout=600)
+    two = _run("--full", "--gpus", "2", "--backend", "gloo", "--config", "3", "--total-paths", str(total), "--steps", "2",
+               "--warmup", "1", timeout=600)
     g = two["group_single_process"]
     assert g["devices"] == 2 and g["paths"] == total and g["outputs"] == "stats" and g["n_periods"] == 360
     _check_group_leg(g["host"], total, two["result"])
@@ -182,8 +246,8 @@ def test_self_launched_run_attaches_the_one_process_group_launcher():
     assert "distinct devices" in g["rccl"]["error"]
     # config 4's shape: final values into pinned host memory through every shard's pipeline
     total4 = 2_000_001
-    four = _run("--gpus", "2", "--backend", "gloo", "--config", "4", "--total-paths", str(total4), "--steps", "2", "--warmup", "1",
-                timeout=600)
+    four = _run("--full", "--gpus", "2", "--backend", "gloo", "--config", "4", "--total-paths", str(total4), "--steps", "2",
+                "--warmup", "1", timeout=600)
     g4 = four["group_single_process"]
     assert g4["outputs"] == "host" and g4["n_periods"] == 1000 and g4["paths"] == total4
     assert "error" not in g4["host"] and g4["host"]["value"] > 0
@@ -215,8 +279,8 @@ def test_ranks_made_by_torchrun_attach_the_group_launcher_from_rank_zero():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     total = 3_000_001
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "2", "--backend", "gloo",
-                        "--config", "3", "--total-paths", str(total), "--steps", "2", "--warmup", "1"],
+                        "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH, "--full", "--gpus", "2", "--backend",
+                        "gloo", "--config", "3", "--total-paths", str(total), "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -8,7 +8,7 @@ for ROUND in 1 2; do
   for L in "$@"; do
     P=$L; [ $L = product ] && P=$R/stock_market_monte_carlo_amd/libsmmc_hip.so
     for CFG in 1 2; do
-      SMMC_LIB=$P timeout -k 10 200 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L config$CFG', '%.4g' % d['value'], '%.3f' % d['roofline']['kernel_ms'])" || exit 1
+      SMMC_LIB=$P timeout -k 10 200 python bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L config$CFG', '%.4g' % d['value'], '%.3f' % d['roofline']['kernel_ms'])" || exit 1
     done
   done
 done > $OUT/ab.txt 2>&1

@@ -9,7 +9,7 @@ cd $R
 for X in A B A B; do
   L=$A; [ $X = B ] && L=$B
   echo "== $X $L"
-  SMMC_LIB=$L timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('config1', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])" || exit 1
+  SMMC_LIB=$L timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('config1', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])" || exit 1
   SMMC_LIB=$L timeout -k 10 200 python tools/bench_keepdata.py 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:

@@ -20,7 +20,7 @@ export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_reftraj -- python3 $R/tools/bench_ref.py --traj > $OUT/trace_reftraj.log 2>&1; echo "trace reftraj rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_reftraj -- python3 $R/tools/bench_ref.py --traj > $OUT/pmc_wr_reftraj.log 2>&1; echo "pmc reftraj rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c0 -- python3 $R/bench.py --config 0 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/trace_c0.log 2>&1; echo "trace c0 rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c0 -- python3 $R/bench.py --full --config 0 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/trace_c0.log 2>&1; echo "trace c0 rc=$?"
 cd $R
 F=$(find $OUT/trace_reftraj -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $OUT/kernel_stats_reftraj.csv
 F=$(find $OUT/trace_c0 -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $OUT/kernel_stats_c0.csv

@@ -16,9 +16,9 @@ rows=[json.loads(l) for l in open("gpurun_out/r04b/ubench_ops.jsonl") if l.start
 for r in rows:
     if r["waves_per_simd"]==8: print("%-18s %-24s %.3f Ginst/s/SIMD  %.2f clk" % (r["probe"], r["operands"], r["ginst_per_s_per_simd"], r["clk_per_inst"]))
 PY
-for i in 1 2 3; do timeout -k 10 300 python bench.py --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"; done
-SMMC_SMALL_LAUNCH_ROUNDS=0 timeout -k 10 300 python bench.py --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 uncapped', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
-SMMC_FINALIZE=launch SMMC_SMALL_LAUNCH_ROUNDS=0 timeout -k 10 300 python bench.py --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 r03 form', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config1', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
+for i in 1 2 3; do timeout -k 10 300 python bench.py --full --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"; done
+SMMC_SMALL_LAUNCH_ROUNDS=0 timeout -k 10 300 python bench.py --full --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 uncapped', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
+SMMC_FINALIZE=launch SMMC_SMALL_LAUNCH_ROUNDS=0 timeout -k 10 300 python bench.py --full --config 0 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 r03 form', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config1', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
 rm -f $OUT/ubench_ops
 ls $OUT

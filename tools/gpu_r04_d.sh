@@ -12,7 +12,7 @@ A=$R/stock_market_monte_carlo_amd/_build/libsmmc_hip_A.so
 B=$R/stock_market_monte_carlo_amd/libsmmc_hip.so
 one() {  # label lib bench-args...
   local L=$1 LIB=$2; shift 2
-  SMMC_LIB=$LIB timeout -k 10 200 python bench.py "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'])"
+  SMMC_LIB=$LIB timeout -k 10 200 python bench.py --full "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'])"
 }
 for round in 1 2 3; do
   one A $A --config 1; one B $B --config 1

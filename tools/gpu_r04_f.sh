@@ -11,16 +11,16 @@ python -c "from stock_market_monte_carlo_amd import build; import sys; sys.exit(
 D=$R/stock_market_monte_carlo_amd
 one() {  # label lib bench-args...
   local L=$1 LIB=$2; shift 2
-  SMMC_LIB=$LIB timeout -k 10 200 python bench.py "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'])"
+  SMMC_LIB=$LIB timeout -k 10 200 python bench.py --full "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'])"
 }
 for round in 1 2 3; do
   one A $D/_build/libsmmc_hip_A.so --config 2; one B $D/libsmmc_hip.so --config 2; one T1 $D/_build/libsmmc_hip_T1.so --config 2; one T2 $D/_build/libsmmc_hip_T2.so --config 2
 done 2>&1 | tee $OUT/ab_table.txt
 for i in 1 2; do
 for v in "default:" "uncapped:SMMC_SMALL_LAUNCH_ROUNDS=0" "r03form:SMMC_FINALIZE=launch SMMC_SMALL_LAUNCH_ROUNDS=0" "launch+cap:SMMC_FINALIZE=launch"; do
-  env ${v#*:} timeout -k 10 300 python bench.py --config 0 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 ${v%%:*}', '%.4g' % d['value'], 'us/step %.2f' % (d['ms_per_step']*1e3), 'kernel us %.2f' % (d['roofline']['kernel_ms']*1e3), 'clock', d['valu']['held_clock_ghz'])"
+  env ${v#*:} timeout -k 10 300 python bench.py --full --config 0 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config0 ${v%%:*}', '%.4g' % d['value'], 'us/step %.2f' % (d['ms_per_step']*1e3), 'kernel us %.2f' % (d['roofline']['kernel_ms']*1e3), 'clock', d['valu']['held_clock_ghz'])"
 done; done 2>&1 | tee $OUT/config0_variants.txt
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config1', d['value'], d['roofline']['kernel_ms'], d['valu'])"
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config1', d['value'], d['roofline']['kernel_ms'], d['valu'])"
 timeout -k 10 1100 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; echo "pytest all rc=$?" | tee -a $OUT/pytest_gpu.log
 tail -6 $OUT/pytest_gpu.log
 ls $OUT

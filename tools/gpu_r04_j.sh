@@ -9,7 +9,7 @@ PROF_TAG=prof_r04 timeout -k 10 1000 bash tools/profile_r04.sh > gpurun_out/prof
 tail -5 gpurun_out/prof_r04.log
 OUT=$R/gpurun_out/prof_r04/keep
 cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
-for c in 1 2; do timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_config${c}_after_profile.json 2>/dev/null; python -c "import sys,json; d=json.loads(open('$OUT/bench_config${c}_after_profile.json').read()); print('config$c', '%.4g' % d['value'], d['roofline']['traffic'], d['valu']['weighted_frac'], d['valu']['held_clock_ghz'])"; done
-timeout -k 10 300 python bench.py --stream ref --outputs final --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_stream_ref_after_profile.json 2>/dev/null
+for c in 1 2; do timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_config${c}_after_profile.json 2>/dev/null; python -c "import sys,json; d=json.loads(open('$OUT/bench_config${c}_after_profile.json').read()); print('config$c', '%.4g' % d['value'], d['roofline']['traffic'], d['valu']['weighted_frac'], d['valu']['held_clock_ghz'])"; done
+timeout -k 10 300 python bench.py --full --stream ref --outputs final --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_stream_ref_after_profile.json 2>/dev/null
 head -60 $OUT/pmc_summary.txt | cut -c1-160
 cat $OUT/pmc_summary_reftraj.txt | grep -A3 "ref_windowed_kernel\|ref_tree_kernel" | cut -c1-160

@@ -20,7 +20,7 @@ import json
 for l in open('$O/bench_keepdata_$round.jsonl'):
     j = json.loads(l); print(j['mode'], j['n_paths'], j['n_periods'], j['kernel_ms'], j['GBps'])"
 done
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 > $O/bench_config1.json 2>$O/bench_config1.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 > $O/bench_config1.json 2>$O/bench_config1.err; echo "bench rc=$?"
 python -c "
 import json
 j = json.loads([l for l in open('$O/bench_config1.json') if l.startswith('{\"metric\"')][-1])

@@ -12,7 +12,7 @@ python -c "from stock_market_monte_carlo_amd import build; import sys; sys.exit(
 D=$R/stock_market_monte_carlo_amd
 one() {  # label lib bench-args...
   local L=$1 LIB=$2; shift 2
-  SMMC_LIB=$LIB timeout -k 10 200 python bench.py "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'], 'clock %.3f' % d['valu']['held_clock_ghz'])"
+  SMMC_LIB=$LIB timeout -k 10 200 python bench.py --full "$@" --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', '$*', '%.4g' % d['value'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'], 'clock %.3f' % d['valu']['held_clock_ghz'])"
 }
 for round in 1 2 3; do
   one B $D/libsmmc_hip.so --config 1; one Z $D/_build/libsmmc_hip_Z.so --config 1; one ZR $D/_build/libsmmc_hip_ZR.so --config 1; one ZC $D/_build/libsmmc_hip_ZC.so --config 1; one P $D/_build/libsmmc_hip_P.so --config 1

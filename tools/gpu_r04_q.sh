@@ -15,8 +15,8 @@ tail -4 $OUT/pytest_gpu.log
 grep -q "pytest rc=0" $OUT/pytest_gpu.log || exit 1
 for i in 1 2 3; do
 for v in "product:$D/libsmmc_hip.so" "memset:$D/_build/libsmmc_hip_MEMSET.so"; do
-  SMMC_LIB=${v#*:} timeout -k 10 300 python bench.py --config 0 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d.get('hbm_bound_kernels') or {}; print('config0 ${v%%:*}', '%.4g' % d['value'], 'us/step %.2f' % (d['ms_per_step']*1e3), 'kernel us %.2f' % (d['roofline']['kernel_ms']*1e3), 'values_stats us %.2f' % (h.get('values_stats', {}).get('kernel_ms', 0)*1e3))"
+  SMMC_LIB=${v#*:} timeout -k 10 300 python bench.py --full --config 0 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d.get('hbm_bound_kernels') or {}; print('config0 ${v%%:*}', '%.4g' % d['value'], 'us/step %.2f' % (d['ms_per_step']*1e3), 'kernel us %.2f' % (d['roofline']['kernel_ms']*1e3), 'values_stats us %.2f' % (h.get('values_stats', {}).get('kernel_ms', 0)*1e3))"
 done; done 2>&1 | tee $OUT/config0_no_memset.txt
 for v in "product:$D/libsmmc_hip.so" "memset:$D/_build/libsmmc_hip_MEMSET.so"; do
-  SMMC_LIB=${v#*:} timeout -k 10 300 python bench.py --config 1 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d['hbm_bound_kernels']; print('config1 ${v%%:*}', '%.4g' % d['value'], 'ms/step %.3f' % d['ms_per_step'], 'values_stats us %.2f' % (h['values_stats']['kernel_ms']*1e3), 'radix us %.2f' % (h['quartiles_radix_pass']['kernel_ms']*1e3))"
+  SMMC_LIB=${v#*:} timeout -k 10 300 python bench.py --full --config 1 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d['hbm_bound_kernels']; print('config1 ${v%%:*}', '%.4g' % d['value'], 'ms/step %.3f' % d['ms_per_step'], 'values_stats us %.2f' % (h['values_stats']['kernel_ms']*1e3), 'radix us %.2f' % (h['quartiles_radix_pass']['kernel_ms']*1e3))"
 done 2>&1 | tee -a $OUT/config0_no_memset.txt

@@ -47,4 +47,4 @@ done 2>&1 | tee $O/radix_match_forms.txt
 rm -rf $O/trace_table $O/trace_chain
 unset SMMC_RADIX_MATCH
 cd $R
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(d['hbm_bound_kernels']['quartiles_radix_pass'])); print(json.dumps(d['hbm_bound_kernels']['values_stats']))" | tee -a $O/radix_match_forms.txt
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(d['hbm_bound_kernels']['quartiles_radix_pass'])); print(json.dumps(d['hbm_bound_kernels']['values_stats']))" | tee -a $O/radix_match_forms.txt

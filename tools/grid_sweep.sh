@@ -6,7 +6,7 @@ cd $R
 for round in 1 2 3; do
   for c in 1 2; do
     for b in 16 32 64 128 256 512 1536; do
-      SMMC_BLOCKS_PER_CU=$b timeout -k 10 120 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+      SMMC_BLOCKS_PER_CU=$b timeout -k 10 120 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

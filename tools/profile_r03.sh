@@ -14,10 +14,10 @@ export TMPDIR=/tmp
 cd /tmp
 run_passes() {  # tag, bench arguments...
   local TAG=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -- python3 $R/bench.py "$@" --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_sq_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_wr_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_rd_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_rd_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -- python3 $R/bench.py --full "$@" --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_sq_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_wr_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_rd_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_rd_$TAG.log 2>&1 || return 1
   echo "passes done: $TAG"
 }
 run_passes c1 --config 1 || exit 1

@@ -14,10 +14,10 @@ export TMPDIR=/tmp
 cd /tmp
 run_passes() {  # tag, bench arguments...
   local TAG=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -- python3 $R/bench.py "$@" --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_sq_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_wr_$TAG.log 2>&1 || return 1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_rd_$TAG -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_rd_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -- python3 $R/bench.py --full "$@" --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_sq_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_wr_$TAG.log 2>&1 || return 1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_rd_$TAG -- python3 $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_rd_$TAG.log 2>&1 || return 1
   echo "passes done: $TAG"
 }
 run_passes c1 --config 1 || exit 1
@@ -28,7 +28,7 @@ run_passes ref1000 --config 2 --stream ref --outputs final --periods 1000 --path
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_reftraj -- python3 $R/tools/bench_ref.py --traj > $OUT/trace_reftraj.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_wr_reftraj -- python3 $R/tools/bench_ref.py --traj > $OUT/pmc_wr_reftraj.log 2>&1 || exit 1
 # the 1e6-path step (BASELINE configs[0] size): one launch per step now
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c0 -- python3 $R/bench.py --config 0 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/trace_c0.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c0 -- python3 $R/bench.py --full --config 0 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/trace_c0.log 2>&1 || exit 1
 cd $R
 python3 tools/pmc_summary.py $OUT/pmc_wr_reftraj > $OUT/pmc_summary_reftraj.txt
 F=$(find $OUT/trace_reftraj -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $OUT/kernel_stats_reftraj.csv
