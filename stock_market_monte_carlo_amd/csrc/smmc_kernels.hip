@@ -176,8 +176,11 @@ constexpr uint32_t kBm3Floats = kBm3RadiusEntries * 4 + kBm3TrigEntries * 2;  //
 // binary32 pattern of the SIGNED distance -- exponent's low five bits and three mantissa bits at
 // [4, 12), the sign (the side) left where the shift puts it, bit 15 -- so side 0 lies at [0, 4 KiB) and
 // side 1 at [32, 36 KiB); the angle table fills [4, 20 KiB) between them, [20, 32 KiB) stays unused.
-// 36 KiB per workgroup instead of 24 are four workgroups of paths_kernel per CU instead of six: the same
-// speed (measured with a padded allocation, profiles/r02/ab_lds_pad.txt; two per CU lose 17 %).
+// 36 KiB per workgroup instead of 24 are four workgroups of paths_kernel per CU instead of six (the same speed
+// at 256 threads each, measured with a padded allocation, profiles/r02/ab_lds_pad.txt; two per CU lose 17 %).
+// paths_kernel puts EIGHT waves on one copy (paths_halves): four workgroups are then 8 waves per SIMD instead of
+// 4, which takes 6.6 % of the launch's clocks and, the chip holding 2.03 instead of 2.13 GHz under it, 1.95 % of
+// the headline step's time (13.16 -> 12.91 ms, profiles/wide_groups/ab_wide_groups.txt).
 constexpr uint32_t kBm3RadiusMask = 0x8000u | ((32u << kBm3SubBits) - 1u) << 4;
 constexpr uint32_t kBm3Side1Bytes = 0x8000u, kBm3SideBytes = (32u << kBm3SubBits) * 16u;
 constexpr uint32_t kBm3TrigBytes = kBm3SideBytes;                     // LDS byte address of the angle table
@@ -516,8 +519,23 @@ __device__ __forceinline__ void partial_add(BlockPartial &a, const BlockPartial 
 // Persistent workgroups; each iteration one chunk of 256 consecutive paths (one
 // per lane) so the final-value store of a wave is one 256-byte line-aligned
 // segment.  LDS: [table (100 + r)] [histogram u32 bins].
+//
+// Counter stream v3's Gaussian mode runs TWO such blocks per workgroup (paths_halves): threads [0, 256) and
+// [256, 512) are "virtual blocks" vb = 2 blockIdx.x and 2 blockIdx.x + 1 of a grid of `vgrid`, and the eight waves
+// read ONE staged copy of the draw tables -- four 36 KiB workgroups per CU are then eight waves per SIMD instead of
+// four.  A half walks the chunks vb, vb + vgrid, ... with its own accumulators, reduction scratch and partial,
+// exactly as a 256-thread workgroup of a vgrid-wide launch does: every output holds the same values added in the
+// same order.  The halves share the LDS histogram (integer atomics) and the barriers, so the chunk loop runs the
+// trip count of half 0 -- never the smaller one, its vb is the lower -- and a half whose chunk does not exist
+// (vb == vgrid when vgrid is odd, or one trip short) goes through the trip with every lane inactive.
+constexpr uint32_t paths_halves(int mode) { return mode == SMMC_MODE_GAUSSIAN ? 2u : 1u; }
+// ... which needs the kernel inside 64 VGPRs: asked of the compiler for that mode only (1 = no constraint)
+constexpr uint32_t paths_min_waves(int mode) { return paths_halves(mode) > 1 ? 8u : 1u; }
 template <int kMode, int kDiv, bool kDense>
-__global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
+__global__ __launch_bounds__(kBlock * paths_halves(kMode)) __attribute__((amdgpu_waves_per_eu(paths_min_waves(kMode))))
+void paths_kernel(const KernelArgs k, const uint32_t vgrid) {
+  constexpr uint32_t kHalves = paths_halves(kMode);
+  constexpr uint32_t kGroup = kBlock * kHalves;  // threads per workgroup
   extern __shared__ __align__(16) unsigned char lds_raw[];
   float *lds_table = reinterpret_cast<float *>(lds_raw);  // returns table, or the Box-Muller tables
   const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
@@ -526,21 +544,25 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
   // static __shared__ arrays: static LDS is placed first, and a draw table that does not start at LDS
   // address 0 costs one address add per gather (two VALU instructions per Philox block in Gaussian mode).
   const uint32_t scratch_words = (table_words + ((k.partials != nullptr) ? k.n_bins : 0u) + 1u) & ~1u;  // 8-byte aligned
-  double *red_scratch = reinterpret_cast<double *>(reinterpret_cast<uint32_t *>(lds_raw) + scratch_words);  // [4 * kWaves]
-  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(red_scratch + 4 * kWaves);                     // [kWaves]
+  double *red_scratch = reinterpret_cast<double *>(reinterpret_cast<uint32_t *>(lds_raw) + scratch_words);  // [kHalves][4 * kWaves]
+  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(red_scratch + 4 * kWaves * kHalves);          // [kHalves][kWaves]
 
-  const uint32_t tid = threadIdx.x;
+  const uint32_t half = kHalves > 1 ? threadIdx.x / kBlock : 0u;  // wave-uniform
+  const uint32_t tid = kHalves > 1 ? threadIdx.x % kBlock : threadIdx.x;
+  const uint32_t vb = blockIdx.x * kHalves + half;  // the virtual block: <= vgrid, == vgrid only for the idle half of an odd grid
+  red_scratch += half * (4 * kWaves);
+  wave_part += half * kWaves;
   bool parity = false;
   unsigned long long clk0 = 0, real0 = 0;
   if (k.clock_probe) {  // uniform; timing instrumentation only
     clk0 = __builtin_amdgcn_s_memtime();
     real0 = __builtin_amdgcn_s_memrealtime();
   }
-  stage_tables<kMode>(k, lds_table);
+  stage_tables<kMode>(k, lds_table, kGroup);
   const bool want_stats = k.partials != nullptr;
   const bool want_hist = want_stats && k.n_bins != 0;
   if (want_hist) {
-    for (uint32_t i = tid; i < k.n_bins; i += kBlock) lds_hist[i] = 0u;
+    for (uint32_t i = threadIdx.x; i < k.n_bins; i += kGroup) lds_hist[i] = 0u;
   }
   __syncthreads();
 
@@ -550,9 +572,13 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
   const DrawRegs dr = make_draw_regs(k);
 
   const uint64_t n_chunks = (k.n_paths + kBlock - 1) / kBlock;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+  // chunk0 is the chunk of half 0 and workgroup-uniform: every wave of the workgroup makes the same trips and
+  // meets the same barriers; `live` says whether this half has a chunk in this trip
+  for (uint64_t chunk0 = static_cast<uint64_t>(blockIdx.x) * kHalves; chunk0 < n_chunks; chunk0 += vgrid) {
+    const uint64_t chunk = chunk0 + half;
+    const bool live = kHalves == 1 || (vb < vgrid && chunk < n_chunks);  // wave-uniform
     const uint64_t i = chunk * kBlock + tid;
-    const bool active = i < k.n_paths;
+    const bool active = live && i < k.n_paths;
     float v = 0.0f;
     if (active) {
       v = simulate_path<kMode, kDiv, kDense>(k, dr, lds_table, k.first_path + i);
@@ -578,11 +604,11 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
         }
       }
     }
-    if (k.d_chunk_mean || k.d_chunk_var) {  // wave-uniform
+    if (k.d_chunk_mean || k.d_chunk_var) {  // uniform over the workgroup
       // mean and population variance of this chunk from one pass (sum and sum of squares in
       // double: the cancellation in E[x^2] - mean^2 costs ~1e-15 relative here), one barrier:
       // the scratch slots alternate with the iteration's parity
-      const uint64_t left = k.n_paths - chunk * kBlock;
+      const uint64_t left = k.n_paths - chunk * kBlock;  // meaningless in a half that is not live: not used there
       const double n_in = static_cast<double>(left < kBlock ? left : kBlock);
       const double dv = active ? static_cast<double>(v) : 0.0;
       const double s1 = wave_sum(dv), s2 = wave_sum(dv * dv);
@@ -594,7 +620,7 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
         slot[kWaves + wave] = s2;
       }
       __syncthreads();
-      if (tid == 0) {
+      if (tid == 0 && live) {
         double t1 = slot[0], t2 = slot[kWaves];
 #pragma unroll
         for (int w = 1; w < kWaves; ++w) {
@@ -609,7 +635,7 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
     }
   }
 
-  if (k.clock_probe && tid == 0) {
+  if (k.clock_probe && threadIdx.x == 0) {
     atomicAdd(&k.clock_probe[0], __builtin_amdgcn_s_memtime() - clk0);
     atomicAdd(&k.clock_probe[1], __builtin_amdgcn_s_memrealtime() - real0);
   }
@@ -627,7 +653,7 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
     const int lane = tid & 63, wave = tid >> 6;
     if (lane == 0) wave_part[wave] = p;
     __syncthreads();
-    if (tid == 0) {
+    if (tid == 0 && vb < vgrid) {  // one partial per virtual block; the idle half of an odd grid has none
       BlockPartial t = wave_part[0];
 #pragma unroll
       for (int w = 1; w < kWaves; ++w) {
@@ -640,10 +666,10 @@ __global__ __launch_bounds__(kBlock) void paths_kernel(const KernelArgs k) {
         t.min = fminf(t.min, wave_part[w].min);
         t.max = fmaxf(t.max, wave_part[w].max);
       }
-      k.partials[blockIdx.x] = t;
+      k.partials[vb] = t;
     }
     if (want_hist) {  // LDS atomics of all waves are complete after the barrier above
-      for (uint32_t b = tid; b < k.n_bins; b += kBlock) {
+      for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
         const uint32_t c = lds_hist[b];
         if (c) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(c));
       }
@@ -1203,9 +1229,11 @@ static size_t draw_table_words(uint32_t table_len, int stream) {
   return table_len ? table_len : (stream == 2 ? kBmFloats : kBm3LdsWords);
 }
 size_t paths_lds_bytes(uint32_t table_len, uint32_t n_bins, int stream) {
-  // [draw tables][histogram][pad to 8 bytes][red_scratch: 4 kWaves doubles][wave_part: kWaves BlockPartial]
+  // [draw tables][histogram][pad to 8 bytes][red_scratch: 4 kWaves doubles][wave_part: kWaves BlockPartial], the
+  // last two once per 256-thread half of the workgroup (paths_halves)
   const size_t words = (draw_table_words(table_len, stream) + n_bins + 1u) & ~static_cast<size_t>(1);
-  return words * 4u + 4u * kWaves * sizeof(double) + kWaves * sizeof(BlockPartial);
+  const size_t halves = paths_halves(table_len ? SMMC_MODE_TABLE : (stream == 2 ? kModeGaussianV2 : SMMC_MODE_GAUSSIAN));
+  return words * 4u + halves * (4u * kWaves * sizeof(double) + kWaves * sizeof(BlockPartial));
 }
 bool table_is_dense(uint32_t table_len);
 // keepdata_kernel: tables + per wave 64 rows of (tile 16 | 32 columns + kDraws more slots, at the
@@ -1252,11 +1280,14 @@ static hipError_t allow_lds(Kernel kernel, size_t lds) {
                              static_cast<int>(lds));
 }
 
+// `grid` counts 256-thread virtual blocks (one partial each); a workgroup holds paths_halves(kMode) of them
 template <int kMode, int kDiv, bool kDense>
 static hipError_t launch_paths_variant(const KernelArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  constexpr uint32_t kHalves = paths_halves(kMode);
   hipError_t err = allow_lds(paths_kernel<kMode, kDiv, kDense>, lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL((paths_kernel<kMode, kDiv, kDense>), dim3(grid), dim3(kBlock), lds, stream, a);
+  hipLaunchKernelGGL((paths_kernel<kMode, kDiv, kDense>), dim3((grid + kHalves - 1) / kHalves), dim3(kBlock * kHalves), lds,
+                     stream, a, grid);
   return hipGetLastError();
 }
 
