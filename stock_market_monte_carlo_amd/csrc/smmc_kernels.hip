@@ -278,7 +278,13 @@ __device__ __forceinline__ Bm3Pending bm3_issue(const float *lds_bm, uint32_t ua
   const uint32_t aoff = (ub >> 16) & ((kBm3TrigEntries - 1u) << 3);  // sector * 8, no rounding add
   // residual angle from the sector's middle, (low bits - half a sector) 2 pi / 2^30: the low bits as the
   // mantissa of a float in [1, 1 + 2^-4), then one fma
-  const float ya = __uint_as_float((ub & ((1u << kRes) - 1u)) | 0x3f800000u);
+  // (ub & mask) | 1.0f as ONE v_bitop3_b32 (truth table 0xEA): the only three-input logic opcode that issues at
+  // full rate on gfx950 -- v_and_or_b32, which the compiler selects for the plain expression (and for a bitop3 of
+  // two constants, hence the opaque mask), takes a half-rate slot like every other VOP3-only integer operation.
+  // The mask stays scalar: one constant-bus read beside the inline constant, no register.
+  uint32_t res_mask = (1u << kRes) - 1u;
+  asm("" : "+s"(res_mask));
+  const float ya = __uint_as_float(__builtin_amdgcn_bitop3_b32(ub, res_mask, 0x3f800000u, 0xEA));
   p.delta = __builtin_fmaf(ya, kBm3AngleK, -kBm3AngleC);
   const f32x2_t cs = lds_load_at<f32x2_t>(aoff + kBm3TrigBytes);
   p.cs = make_float2(cs.x, cs.y);
@@ -514,6 +520,41 @@ __device__ __forceinline__ void partial_add(BlockPartial &a, const BlockPartial 
   a.max = fmaxf(a.max, b.max);
 }
 
+// The two wave sums of a chunk's statistics, without LDS traffic: s1 summed over the wave arrives in lane 0, s2 in
+// lane 32 (other lanes: partial sums nobody reads), each added in the association of dev::wave_sum,
+//   for (off = 32; off > 0; off >>= 1) v += shfl_down(v, off),
+// as lane 0 sees it -- ((x0 + x32) + (x16 + x48)) + ... -- because the sum of squares is not exact in binary64 and
+// the chunk variance is a bit-exact contract.  v_permlane32_swap puts the low halves of BOTH operands into one
+// register and the high halves into the other, so ONE add does the offset-32 step of both sums (s1 in lanes
+// [0, 32), s2 in [32, 64)); v_permlane16_swap pairs rows 0 + 1 and 2 + 3; the offsets 8 .. 1 stay inside a row of
+// 16 lanes, which DPP row shifts read (lanes shifted in from outside the row read 0 and only reach lanes that lane 0
+// and lane 32 never take from).  20 VALU instructions for both sums; wave_sum's ds_bpermute form took 24 LDS
+// instructions and about 20 of lane arithmetic beside the 12 adds.  Every lane of the wave must be enabled.
+__device__ __forceinline__ uint32_t lo32(double v) { return static_cast<uint32_t>(__double_as_longlong(v)); }
+__device__ __forceinline__ uint32_t hi32(double v) { return static_cast<uint32_t>(__double_as_longlong(v) >> 32); }
+__device__ __forceinline__ double join64(uint32_t lo, uint32_t hi) {
+  return __longlong_as_double(static_cast<long long>(static_cast<uint64_t>(hi) << 32 | lo));
+}
+template <int kShift>
+__device__ __forceinline__ double row_shl_add(double v) {  // v[i] += v[i + kShift] inside each row of 16 lanes
+  constexpr int kRowShl = 0x100 + kShift;                   // DPP control row_shl:kShift
+  const uint32_t lo = __builtin_amdgcn_update_dpp(0u, lo32(v), kRowShl, 0xf, 0xf, true);
+  const uint32_t hi = __builtin_amdgcn_update_dpp(0u, hi32(v), kRowShl, 0xf, 0xf, true);
+  return v + join64(lo, hi);
+}
+__device__ __forceinline__ double wave_sum_pair(double s1, double s2) {
+  const auto l = __builtin_amdgcn_permlane32_swap(lo32(s1), lo32(s2), false, false);  // [0]: low halves of s1, s2
+  const auto h = __builtin_amdgcn_permlane32_swap(hi32(s1), hi32(s2), false, false);  // [1]: their high halves
+  double v = join64(l[0], h[0]) + join64(l[1], h[1]);                                 // x[i] + x[i + 32]
+  const auto l16 = __builtin_amdgcn_permlane16_swap(lo32(v), lo32(v), false, false);  // [0]: rows 0 0 2 2, [1]: 1 1 3 3
+  const auto h16 = __builtin_amdgcn_permlane16_swap(hi32(v), hi32(v), false, false);
+  v = join64(l16[0], h16[0]) + join64(l16[1], h16[1]);                                // ... + v[i + 16]
+  v = row_shl_add<8>(v);
+  v = row_shl_add<4>(v);
+  v = row_shl_add<2>(v);
+  return row_shl_add<1>(v);
+}
+
 // ---- main kernel ---------------------------------------------------------------
 
 // Persistent workgroups; each iteration one chunk of 256 consecutive paths (one
@@ -608,17 +649,12 @@ void paths_kernel(const KernelArgs k, const uint32_t vgrid) {
       // mean and population variance of this chunk from one pass (sum and sum of squares in
       // double: the cancellation in E[x^2] - mean^2 costs ~1e-15 relative here), one barrier:
       // the scratch slots alternate with the iteration's parity
-      const uint64_t left = k.n_paths - chunk * kBlock;  // meaningless in a half that is not live: not used there
-      const double n_in = static_cast<double>(left < kBlock ? left : kBlock);
       const double dv = active ? static_cast<double>(v) : 0.0;
-      const double s1 = wave_sum(dv), s2 = wave_sum(dv * dv);
+      const double s12 = wave_sum_pair(dv, dv * dv);  // lane 0: the wave's sum, lane 32: its sum of squares
       double *slot = red_scratch + (parity ? 2 * kWaves : 0);
       parity = !parity;
       const int lane = tid & 63, wave = tid >> 6;
-      if (lane == 0) {
-        slot[wave] = s1;
-        slot[kWaves + wave] = s2;
-      }
+      if ((lane & 31) == 0) slot[(lane ? kWaves : 0) + wave] = s12;
       __syncthreads();
       if (tid == 0 && live) {
         double t1 = slot[0], t2 = slot[kWaves];
@@ -627,8 +663,19 @@ void paths_kernel(const KernelArgs k, const uint32_t vgrid) {
           t1 += slot[w];
           t2 += slot[kWaves + w];
         }
-        const double mean = t1 / n_in;
-        const double var = t2 / n_in - mean * mean;
+        // A full chunk -- every chunk but the last one of a launch -- needs no divide: t * 2^-8 and t / 256 are the
+        // same binary64 for every sum of binary32 values or of their squares (no subnormal double arises; inf and
+        // NaN go through alike).  The IEEE divides stay for the one chunk that may be ragged.
+        double mean, var;
+        if (chunk + 1 < n_chunks) {
+          static_assert(kBlock == 256, "the full chunk's reciprocal is 2^-8");
+          mean = t1 * 0x1p-8;
+          var = t2 * 0x1p-8 - mean * mean;
+        } else {
+          const double n_in = static_cast<double>(k.n_paths - chunk * kBlock);  // 1 .. kBlock
+          mean = t1 / n_in;
+          var = t2 / n_in - mean * mean;
+        }
         if (k.d_chunk_mean) k.d_chunk_mean[chunk] = static_cast<float>(mean);
         if (k.d_chunk_var) k.d_chunk_var[chunk] = static_cast<float>(var > 0.0 ? var : 0.0);
       }

@@ -136,6 +136,12 @@ constexpr int kPerIter = 64;
 #define CNDMASK_S(n) "v_cndmask_b32 %[a" #n "], %[a" #n "], %[b" #n "], s[10:11]\n"
 #define READFIRST(n) "v_readfirstlane_b32 s1" #n ", %[a" #n "]\n"
 #define DPP_ROW(n) "v_mov_b32_dpp %[a" #n "], %[b" #n "] row_shr:1 row_mask:0xf bank_mask:0xf\n"
+// (x & mask) | 1.0f in one instruction, the residual angle of the Gaussian draw (bm3_issue): the mask in an SGPR (what
+// v_and_or_b32 reads today: ANDOR_S) or in a VGPR, and the scalar form among three VGPR-only instructions as in the loop
+#define BITOP_EA_S(n) "v_bitop3_b32 %[a" #n "], %[a" #n "], %[sk], 1.0 bitop3:0xea\n"
+#define BITOP_EA_V(n) "v_bitop3_b32 %[a" #n "], %[a" #n "], %[vk], 1.0 bitop3:0xea\n"
+#define BITOP_EA_MIX4(n) "v_bitop3_b32 %[a" #n "], %[a" #n "], %[sk], 1.0 bitop3:0xea\n v_xor_b32 %[b" #n "], %[vk], %[b" #n "]\n v_add_u32 %[b" #n "], %[vk], %[b" #n "]\n v_xor_b32 %[b" #n "], %[vk], %[b" #n "]\n"
+#define ANDOR_MIX4(n) "v_and_or_b32 %[a" #n "], %[a" #n "], %[sk], 1.0\n v_xor_b32 %[b" #n "], %[vk], %[b" #n "]\n v_add_u32 %[b" #n "], %[vk], %[b" #n "]\n v_xor_b32 %[b" #n "], %[vk], %[b" #n "]\n"
 #define DS_SWZ(n) "ds_bpermute_b32 %[a" #n "], %[b" #n "], %[a" #n "]\n"
 
 template <int OP>
@@ -169,7 +175,7 @@ __global__ __launch_bounds__(256) void probe(unsigned *out, unsigned sk, float s
     PROBE(60, BITOP_BANKS_DISTINCT) PROBE(61, BITOP_BANKS_SAME) PROBE(62, BITOP_X4) PROBE(64, FMA_DISTINCT)
     PROBE(65, FMA_X4) PROBE(80, FMA_T2) PROBE(81, XOR_MIX2) PROBE(82, XOR_MIX4) PROBE(83, MAD_MIX2) PROBE(84, MAD_MIX3) PROBE(85, MADS_MIX2) PROBE(66, FMA_3V) PROBE(67, FMAC_2V) PROBE(68, XOR_2V) PROBE(69, AND_L) PROBE(70, OR_I) PROBE(71, LSHL_I)
     PROBE(72, SUB_V) PROBE(73, MULF_E64_S) PROBE(74, MAX_V) PROBE(75, ADDF64) PROBE(76, ADDCO) PROBE(77, CNDMASK_S) PROBE(78, READFIRST)
-    PROBE(79, DPP_ROW)
+    PROBE(79, DPP_ROW) PROBE(100, BITOP_EA_S) PROBE(101, BITOP_EA_V) PROBE(102, BITOP_EA_MIX4) PROBE(103, ANDOR_MIX4)
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
   if (threadIdx.x == 0) { clk[2 * blockIdx.x] = t1 - t0; clk[2 * blockIdx.x + 1] = r1 - r0; }
@@ -248,5 +254,7 @@ int main() {
   RUN(69, "v_and_b32", "literal") RUN(70, "v_or_b32", "inline 1.0") RUN(71, "v_lshlrev_b32", "inline") RUN(72, "v_sub_u32", "vgpr")
   RUN(73, "v_mul_f32_e64", "sgpr") RUN(74, "v_max_f32", "vgpr") RUN(75, "v_add_f64", "vgpr") RUN(76, "v_add_co_u32", "vgpr -> vcc")
   RUN(77, "v_cndmask_b32", "vgpr, sgpr-pair mask") RUN(78, "v_readfirstlane_b32", "vgpr -> sgpr") RUN(79, "v_mov_b32_dpp", "row_shr:1")
+  RUN(100, "v_bitop3_b32", "sgpr mask + inline 1.0, 0xEA") RUN(101, "v_bitop3_b32", "vgpr mask + inline 1.0, 0xEA")
+  RUN(102, "mix: v_bitop3 0xEA sgpr + 3 vgpr-only", "per GROUP of 4: count x 4") RUN(103, "mix: v_and_or sgpr + 3 vgpr-only", "per GROUP of 4: count x 4")
   return 0;
 }
