@@ -188,6 +188,40 @@ int smmc_engine_simulate(smmc_engine *e, const smmc_sim *sim, float *d_final, fl
  * otherwise). */
 int smmc_engine_simulate_keepdata(smmc_engine *e, const smmc_sim *sim, float *d_traj, float *d_final);
 
+/* ---- checkpoint statistics: the value distribution at chosen periods ------------------------ */
+
+#define SMMC_MAX_CHECKPOINTS 64
+/* largest n_checkpoints * n_bins of one call: the kernel keeps that many 32-bit bucket counters in LDS beside
+ * the draw tables (32 KiB: 64 checkpoints x 128 buckets, or 31 x 256, or 2 x 4096) */
+#define SMMC_MAX_CHECKPOINT_BINS 8192
+
+/* Enqueues one simulation that also reduces the paths' values at n_checkpoints chosen periods.
+ * periods[0 .. n_checkpoints): HOST array, strictly increasing, 1 <= periods[k] <= sim->n_periods; the value
+ * of a path "at period p" is its value after p compounding steps = column p of its keepdata row.
+ * d_records: DEVICE, n_checkpoints packed records back to back, smmc_stats_bytes(sim->n_bins) bytes each,
+ * 8-byte aligned; record k is the record smmc_engine_values_stats would write for column periods[k] of the
+ * trajectories smmc_engine_simulate_keepdata writes for the same sim (below_threshold, n_bins, hist_lo,
+ * hist_hi of sim apply to every checkpoint): integer fields, min, max and bucket counts exactly, sum and sumsq
+ * as double sums in a fixed order (two identical calls give the same bytes; no floating-point atomics).
+ * d_final (may be NULL): as in smmc_engine_simulate, and bit-identical to it.
+ * The values are in a register at every period; reducing them there costs K small records instead of the
+ * 4 (n_periods + 1) bytes per path of keepdata.  Replaces the per-frame host passes over mc_data that put the
+ * MINIMUM / TARGET levels next to the plotted lines (examples/visualize_returns_cpu_v2.cpp:397-411) and
+ * update_count_below_min (:125-138) evaluated for an earlier period than the last.
+ * Divide: a checkpoint value has to be right when it is taken, so the end-of-path rerun of SMMC_DIV_CHECKED
+ * does not apply; the launch follows the keepdata rule, smmc_engine_divide_kind(e, sim, 1): the fast form when
+ * the host proves the window, the IEEE divide otherwise or with SMMC_FLAG_EXACT_DIV.
+ * SMMC_ERR_INVALID: n_checkpoints == 0 or > SMMC_MAX_CHECKPOINTS; a period that is 0, above n_periods or not
+ * above the one before it; NULL periods or d_records; SMMC_FLAG_STREAM_REF or SMMC_FLAG_STREAM_V2 (counter
+ * stream v3 only); n_checkpoints * n_bins > SMMC_MAX_CHECKPOINT_BINS; more than 2^32 paths per workgroup
+ * (n_paths beyond some 10^13: shard the request, the records merge with smmc_stats_merge).
+ * Asynchronous on the engine stream; periods[] may be reused on return. */
+int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const uint32_t *periods,
+                                     uint32_t n_checkpoints, float *d_final, void *d_records);
+/* Synchronous convenience: the same into HOST memory (records: n_checkpoints * smmc_stats_bytes(n_bins) bytes). */
+int smmc_engine_simulate_checkpoints_to_host(smmc_engine *e, const smmc_sim *sim, const uint32_t *periods,
+                                             uint32_t n_checkpoints, float *host_final, void *host_records);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

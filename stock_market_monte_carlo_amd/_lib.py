@@ -27,6 +27,8 @@ CHUNK = 256
 MAX_TABLE = 16384
 MAX_BINS = 4096
 MAX_RANKS = 8
+MAX_CHECKPOINTS = 64
+MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
 
 
 class Sim(C.Structure):
@@ -89,6 +91,10 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("smmc_engine_simulate_keepdata", C.c_int, [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p]),
     ("smmc_engine_sync", C.c_int, [C.c_void_p]),
+    ("smmc_engine_simulate_checkpoints", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_checkpoints_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -23,6 +23,16 @@
 #include "smmc_host.h"
 #include "smmc_internal.h"
 
+// The host-side test builds link this file against stand-ins for the kernel translation units that predate the
+// checkpoint kernel: where it is missing, smmc_engine_simulate_checkpoints reports that after its argument checks
+// (an error, never another path to a result).
+namespace smmc {
+extern __attribute__((weak)) decltype(launch_checkpoints) launch_checkpoints;
+extern __attribute__((weak)) decltype(launch_finalize_checkpoints) launch_finalize_checkpoints;
+extern __attribute__((weak)) decltype(checkpoints_group_paths) checkpoints_group_paths;
+extern __attribute__((weak)) decltype(checkpoints_lds_bytes) checkpoints_lds_bytes;
+}  // namespace smmc
+
 namespace {
 
 #include "smmc_bm_tables.inc"  // smmc_bm_radius[1024][4], smmc_bm_trig[256][2]
@@ -146,6 +156,8 @@ struct smmc_engine {
   // and its finalize -- the next user clears the whole array first (hist_acc_ready).
   unsigned long long *d_hist_spread = nullptr;
   bool hist_dirty = false;
+  smmc::BlockPartial *d_ck_partials = nullptr;  // checkpoints_kernel: [checkpoint][workgroup], grown on demand
+  size_t ck_partials_cap = 0;
 
   // SMMC_FLAG_STREAM_REF (smmc_ref_kernels.hip)
   float *d_ref_final = nullptr;     // final values of a launch that asked for none (statistics are formed from them)
@@ -699,6 +711,7 @@ void smmc_engine_destroy(smmc_engine *e) {
   if (e->d_scratch_stats) (void)hipFree(e->d_scratch_stats);
   if (e->d_work_counter) (void)hipFree(e->d_work_counter);
   if (e->d_hist_spread) (void)hipFree(e->d_hist_spread);
+  if (e->d_ck_partials) (void)hipFree(e->d_ck_partials);
   if (e->d_ref_final) (void)hipFree(e->d_ref_final);
   if (e->d_ref_redo) (void)hipFree(e->d_ref_redo);
   if (e->d_ref_ws) (void)hipFree(e->d_ref_ws);
@@ -891,6 +904,125 @@ int smmc_engine_simulate_keepdata(smmc_engine *e, const smmc_sim *sim, float *d_
     if (err != hipSuccess) return bail(err, "launch_final_column");
   }
   return timing_end(e);
+}
+
+// Workgroups of checkpoints_kernel per CU.  Fewer than paths_kernel's 64: every workgroup leaves one partial PER
+// CHECKPOINT (56 bytes) and flushes n_checkpoints x n_bins bucket counts; 32 still hand the CUs work in pieces of
+// 1 / 32 of their share.
+constexpr uint32_t kCheckpointGroupsPerCU = 32;
+static_assert(static_cast<uint64_t>(SMMC_MAX_CHECKPOINT_BINS) <= static_cast<uint64_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
+              "the engine's bucket accumulator holds a checkpoint launch's counters");
+
+static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints,
+                             const void *final_ptr, const void *records) {
+  int rc = check_sim(e, sim);
+  if (rc) return rc;
+  if (!periods) return fail(SMMC_ERR_INVALID, "periods is NULL");
+  if (!records) return fail(SMMC_ERR_INVALID, "the records pointer is NULL");
+  if (n_checkpoints == 0) return fail(SMMC_ERR_INVALID, "n_checkpoints is 0");
+  if (n_checkpoints > SMMC_MAX_CHECKPOINTS)
+    return fail(SMMC_ERR_INVALID, "n_checkpoints %u exceeds SMMC_MAX_CHECKPOINTS %d", n_checkpoints, SMMC_MAX_CHECKPOINTS);
+  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
+    return fail(SMMC_ERR_INVALID, "checkpoint statistics support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
+                (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  for (uint32_t i = 0; i < n_checkpoints; ++i) {
+    if (periods[i] == 0) return fail(SMMC_ERR_INVALID, "periods[%u] is 0: checkpoints are periods 1 .. n_periods", i);
+    if (periods[i] > sim->n_periods)
+      return fail(SMMC_ERR_INVALID, "periods[%u] = %u is above n_periods %u", i, periods[i], sim->n_periods);
+    if (i && periods[i] <= periods[i - 1])
+      return fail(SMMC_ERR_INVALID, "periods must be strictly increasing (periods[%u] = %u after %u)", i, periods[i],
+                  periods[i - 1]);
+  }
+  if (static_cast<uint64_t>(n_checkpoints) * sim->n_bins > SMMC_MAX_CHECKPOINT_BINS)
+    return fail(SMMC_ERR_INVALID, "n_checkpoints * n_bins = %u * %u exceeds SMMC_MAX_CHECKPOINT_BINS %d", n_checkpoints,
+                sim->n_bins, SMMC_MAX_CHECKPOINT_BINS);
+  if (reinterpret_cast<uintptr_t>(final_ptr) & 3u) return fail(SMMC_ERR_INVALID, "the final-value pointer must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(SMMC_ERR_INVALID, "the records pointer must be 8-byte aligned");
+  if (!smmc::launch_checkpoints || !smmc::launch_finalize_checkpoints || !smmc::checkpoints_group_paths ||
+      !smmc::checkpoints_lds_bytes)
+    return fail(SMMC_ERR_HIP, "this build carries no checkpoint kernel");
+  return SMMC_OK;
+}
+
+int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints,
+                                     float *d_final, void *d_records) {
+  int rc = check_checkpoints(e, sim, periods, n_checkpoints, d_final, d_records);
+  if (rc) return rc;
+  // launch geometry: a workgroup walks chunks of group_paths consecutive paths
+  const uint32_t group_paths = smmc::checkpoints_group_paths(sim->mode);
+  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
+  const uint32_t grid = static_cast<uint32_t>(
+      std::min<uint64_t>(n_chunks, std::min(e->compute_units * kCheckpointGroupsPerCU, e->max_grid)));
+  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS buckets)
+  if (grid && (n_chunks + grid - 1) / grid * group_paths >= (1ull << 32))
+    return fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
+                static_cast<unsigned long long>(sim->n_paths));
+  smmc::KernelArgs a = make_args(e, sim);
+  const size_t lds = smmc::checkpoints_lds_bytes(a.mode, a.table_len, n_checkpoints, a.n_bins);
+  if (lds + 2048 > e->max_lds)
+    return fail(SMMC_ERR_INVALID, "table + checkpoint histograms need %zu bytes of LDS, device allows %zu", lds, e->max_lds);
+  DeviceGuard guard(e->device);
+  if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+  const size_t want = static_cast<size_t>(grid) * n_checkpoints;
+  if (e->ck_partials_cap < want) {
+    SMMC_HIP(hipStreamSynchronize(e->stream));  // an earlier launch may still read the old array
+    if (e->d_ck_partials) SMMC_HIP(hipFree(e->d_ck_partials));
+    e->d_ck_partials = nullptr;
+    e->ck_partials_cap = 0;
+    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_ck_partials), sizeof(smmc::BlockPartial) * want));
+    e->ck_partials_cap = want;
+  }
+  a.d_final = d_final;
+  a.partials = e->d_ck_partials;
+  if (sim->n_bins) {
+    rc = hist_acc_ready(e);
+    if (rc) return rc;
+    a.d_hist = e->d_hist_spread;  // [checkpoint][bucket], zero now and zero again after the finalize
+    e->hist_dirty = true;
+  }
+  if (grid) {
+    float unused_lo, unused_hi;
+    const bool exact_div = divide_kind(e, sim, false, &unused_lo, &unused_hi) != SMMC_DIV_FAST;
+    rc = timing_begin(e);
+    if (rc) return rc;
+    const hipError_t err = smmc::launch_checkpoints(a, periods, n_checkpoints, exact_div, grid, e->stream);
+    if (err != hipSuccess) {
+      (void)timing_end(e);
+      return fail(SMMC_ERR_HIP, "launch_checkpoints failed: %s", hipGetErrorString(err));
+    }
+    rc = timing_end(e);
+    if (rc) return rc;
+  }
+  SMMC_HIP(smmc::launch_finalize_checkpoints(e->d_ck_partials, grid, n_checkpoints, d_records, sim->n_bins,
+                                             sim->n_bins ? e->d_hist_spread : nullptr, e->stream));
+  e->hist_dirty = false;
+  return SMMC_OK;
+}
+
+int smmc_engine_simulate_checkpoints_to_host(smmc_engine *e, const smmc_sim *sim, const uint32_t *periods,
+                                             uint32_t n_checkpoints, float *host_final, void *host_records) {
+  int rc = check_checkpoints(e, sim, periods, n_checkpoints, nullptr, host_records ? reinterpret_cast<const void *>(8) : nullptr);
+  if (rc) return rc;
+  DeviceGuard guard(e->device);
+  if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+  const size_t rec_bytes = static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) * n_checkpoints;
+  const size_t final_bytes = host_final ? sizeof(float) * sim->n_paths : 0;
+  void *d_records = nullptr;
+  float *d_final = nullptr;
+  SMMC_HIP(hipMalloc(&d_records, rec_bytes));
+  hipError_t err = final_bytes ? hipMalloc(reinterpret_cast<void **>(&d_final), final_bytes) : hipSuccess;
+  if (err == hipSuccess) {
+    rc = smmc_engine_simulate_checkpoints(e, sim, periods, n_checkpoints, d_final, d_records);
+    if (rc == SMMC_OK) err = hipStreamSynchronize(e->stream);
+    if (rc == SMMC_OK && err == hipSuccess) err = hipMemcpy(host_records, d_records, rec_bytes, hipMemcpyDeviceToHost);
+    if (rc == SMMC_OK && err == hipSuccess && final_bytes) err = hipMemcpy(host_final, d_final, final_bytes, hipMemcpyDeviceToHost);
+  }
+  if (rc != SMMC_OK) (void)hipStreamSynchronize(e->stream);  // nothing of the call may outlive its buffers
+  (void)hipFree(d_records);
+  if (d_final) (void)hipFree(d_final);
+  if (rc) return rc;
+  if (err != hipSuccess) return fail(SMMC_ERR_HIP, "simulate_checkpoints_to_host: %s", hipGetErrorString(err));
+  return SMMC_OK;
 }
 
 int smmc_engine_sync(smmc_engine *e) {

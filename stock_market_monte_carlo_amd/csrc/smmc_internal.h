@@ -138,6 +138,16 @@ uint32_t keepdata_draws(uint32_t table_len);
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
                            hipStream_t stream);
 size_t paths_lds_bytes(uint32_t table_len, uint32_t n_bins, int stream);
+// checkpoints_kernel (smmc_engine_simulate_checkpoints; counter stream v3 only).  a.partials: n_checkpoints x grid
+// entries, [checkpoint][workgroup]; a.d_hist: n_checkpoints x a.n_bins counters, zero before the launch.  A workgroup
+// walks chunks of checkpoints_group_paths(mode) consecutive paths.  launch_finalize_checkpoints folds both into the
+// n_checkpoints packed records at d_records and leaves the counters zero.
+hipError_t launch_checkpoints(const KernelArgs &a, const uint32_t *periods, uint32_t n_checkpoints, bool exact_div,
+                              uint32_t grid, hipStream_t stream);
+hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_partials, uint32_t n_checkpoints,
+                                       void *d_records, uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream);
+uint32_t checkpoints_group_paths(int32_t mode);
+size_t checkpoints_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_checkpoints, uint32_t n_bins);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0

@@ -772,6 +772,253 @@ __global__ __launch_bounds__(kFinalizeBlock) void finalize_kernel(const BlockPar
   }
 }
 
+// ---- checkpoints: the value distribution at chosen periods ---------------------------------------
+//
+// smmc_engine_simulate_checkpoints: the paths of paths_kernel, reduced not only at the end but after each of
+// c.n chosen periods -- one statistics record per checkpoint instead of a trajectory per path.  Bound like
+// paths_kernel: VALU issue; HBM sees 4 B per path (d_final) or nothing.
+//
+// Work.  A WAVE owns a chunk of 64 consecutive paths (one 256-byte final-value store) and walks the chunks
+// wc = blockIdx.x * kW + wave, + gridDim.x * kW, ...; there is no barrier inside the walk.  Every lane of a wave
+// runs a path, also beyond n_paths in the launch's last chunk (the wave reductions want the whole wave; such a
+// lane contributes nothing), so control flow is wave-uniform throughout.
+//
+// Where the checkpoint test sits.  The sorted periods are kernel arguments, read with scalar loads; `next_p`, the
+// next one, lives in an SGPR.  One scalar compare per Philox block decides between the block of simulate_path
+// (no checkpoint inside: the same instructions) and the slow form, which keeps the block's kDraws prefix values
+// and records those next_p names.  The path's last, partial block takes the slow form too.
+//
+// A record (checkpoint_record).  Two double sums by wave_sum_pair, min and -max by the same lane movements
+// (wave_min_pair), the four counters by ballots and scalar population counts, one LDS add per live lane into the
+// [checkpoint][bucket] u32 histogram behind the draw tables.  The wave's totals are then ADDED BY LANE ck to the
+// accumulators it holds in registers: lane k of a wave keeps checkpoint k (SMMC_MAX_CHECKPOINTS is the wave
+// size), ten registers per lane for any number of checkpoints, no LDS, and a fixed order -- a wave's chunks in
+// ascending order.  At the end the waves put their partials over the draw tables (no longer needed), thread k
+// folds the kW of checkpoint k in wave order and writes partials[k][blockIdx.x]; finalize_checkpoints_kernel folds
+// those in a fixed order, one workgroup per record.
+//
+// u32 counters (lane accumulators, LDS buckets) count paths of ONE workgroup: the host refuses a launch in which
+// a workgroup would get 2^32 or more (smmc_capi.cpp).
+struct CheckpointArgs {
+  uint32_t n;                              // 1 .. SMMC_MAX_CHECKPOINTS
+  uint32_t periods[SMMC_MAX_CHECKPOINTS];  // strictly increasing, 1 .. n_periods
+};
+static_assert(SMMC_MAX_CHECKPOINTS <= 64, "lane k of a wave accumulates checkpoint k");
+
+constexpr uint32_t checkpoint_waves(int mode) { return mode == SMMC_MODE_GAUSSIAN ? 8u : 4u; }  // per workgroup
+// LDS words in front of the histogram: the draw tables, later the waves' partials [kW][n]
+constexpr uint32_t checkpoint_front_words(uint32_t table_words, uint32_t waves, uint32_t n) {
+  const uint32_t part_words = waves * n * static_cast<uint32_t>(sizeof(BlockPartial) / 4u);
+  return ((table_words > part_words ? table_words : part_words) + 1u) & ~1u;
+}
+
+struct CheckpointAcc {  // what lane k holds for checkpoint k
+  double sum, sumsq;
+  uint32_t count, below, under, over;
+  float min, max;
+};
+
+template <int kShift>
+__device__ __forceinline__ float row_shl_min(float v) {  // v[i] = min(v[i], v[i + kShift]) inside each row of 16 lanes
+  constexpr int kRowShl = 0x100 + kShift;                 // lanes shifted in from outside the row keep +inf
+  const uint32_t o = __builtin_amdgcn_update_dpp(0x7f800000u, __float_as_uint(v), kRowShl, 0xf, 0xf, false);
+  return fminf(v, __uint_as_float(o));
+}
+// min of a over the wave in lane 0, of b in lane 32: the lane movements of wave_sum_pair.  No NaN among the inputs.
+__device__ __forceinline__ float wave_min_pair(float a, float b) {
+  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  float v = fminf(__uint_as_float(s[0]), __uint_as_float(s[1]));
+  const auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = fminf(__uint_as_float(t[0]), __uint_as_float(t[1]));
+  v = row_shl_min<8>(v);
+  v = row_shl_min<4>(v);
+  v = row_shl_min<2>(v);
+  return row_shl_min<1>(v);
+}
+__device__ __forceinline__ double read_lane(double v, int lane) {
+  return join64(__builtin_amdgcn_readlane(lo32(v), lane), __builtin_amdgcn_readlane(hi32(v), lane));
+}
+__device__ __forceinline__ uint32_t ballot_count(bool pred) {
+  return static_cast<uint32_t>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(pred)));
+}
+
+// The wave's values v (lanes with !active: none) go into checkpoint ck: the record values_stats forms of them.
+// Every lane of the wave must be enabled; ck is wave-uniform.
+__device__ __forceinline__ void checkpoint_record(const KernelArgs &k, uint32_t ck, float v, bool active, uint32_t lane,
+                                                  uint32_t *lds_hist, CheckpointAcc &acc) {
+  const double dv = static_cast<double>(v);
+  const double s12 = wave_sum_pair(active ? dv : 0.0, active ? dv * dv : 0.0);  // lane 0: sum, lane 32: sum of squares
+  const bool ordered = active && v == v;  // min and max skip NaN, as fminf / fmaxf do
+  const float mm = wave_min_pair(ordered ? v : __builtin_inff(), ordered ? -v : __builtin_inff());  // lane 0: min, lane 32: -max
+  const uint32_t n_count = ballot_count(active);
+  const uint32_t n_below = ballot_count(active && v < k.below_threshold);
+  uint32_t n_under = 0, n_over = 0;
+  if (k.n_bins) {  // uniform
+    const bool under = active && v < k.hist_lo;
+    const bool inside = active && !under && v < k.hist_hi;
+    n_under = ballot_count(under);
+    n_over = ballot_count(active && !under && !inside);  // >= hist_hi, or NaN
+    if (inside) {
+      int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
+      b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
+      atomicAdd(&lds_hist[ck * k.n_bins + static_cast<uint32_t>(b)], 1u);
+    }
+  }
+  const double w_sum = read_lane(s12, 0), w_sumsq = read_lane(s12, 32);
+  const float w_min = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 0));
+  const float w_max = -__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 32));
+  if (lane == ck) {
+    acc.sum += w_sum;
+    acc.sumsq += w_sumsq;
+    acc.count += n_count;
+    acc.below += n_below;
+    acc.under += n_under;
+    acc.over += n_over;
+    acc.min = fminf(acc.min, w_min);
+    acc.max = fmaxf(acc.max, w_max);
+  }
+}
+
+template <int N>
+__device__ __forceinline__ float pick(const float (&t)[N], uint32_t j) {  // t[j], j wave-uniform: N - 1 selects
+  float v = t[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) {
+    v = (j == static_cast<uint32_t>(i)) ? t[i] : v;
+    asm("" : "+v"(v));  // left alone the compiler turns the chain into an array in scratch memory
+  }
+  return v;
+}
+
+template <int kMode, bool kExactDiv, bool kDense>
+__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *lds_table = reinterpret_cast<float *>(lds_raw);
+  const uint32_t front_words = checkpoint_front_words(is_table(kMode) ? k.table_len : bm_lds_words(kMode), kW, c.n);
+  uint32_t *lds_hist = reinterpret_cast<uint32_t *>(lds_raw) + front_words;  // [c.n][k.n_bins]
+  const uint32_t hist_words = c.n * k.n_bins;
+
+  stage_tables<kMode>(k, lds_table, kGroup);
+  for (uint32_t i = threadIdx.x; i < hist_words; i += kGroup) lds_hist[i] = 0u;
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  CheckpointAcc acc;
+  acc.sum = acc.sumsq = 0.0;
+  acc.count = acc.below = acc.under = acc.over = 0u;
+  acc.min = __builtin_inff();
+  acc.max = -__builtin_inff();
+  const DrawRegs dr = make_draw_regs(k);
+
+  const uint32_t n_blocks = (k.n_periods + kDraws - 1) / kDraws;  // >= 1: a checkpoint is a period >= 1
+  const uint32_t last_j = k.n_periods - (n_blocks - 1) * kDraws - 1;  // the final value's place in the last block
+  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
+  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
+       wc += static_cast<uint64_t>(gridDim.x) * kW) {
+    const uint64_t i = wc * 64u + lane;
+    const bool active = i < k.n_paths;
+    const uint64_t path = k.first_path + i;
+    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+    float total = k.initial_capital;
+    uint32_t ck = 0, next_p = c.periods[0];
+    for (uint32_t blk = 0; blk < n_blocks; ++blk) {
+      float a[kDraws];
+      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+      const uint32_t p_end = (blk + 1) * kDraws;  // periods done after this block
+      if (next_p > p_end && p_end <= k.n_periods) {  // uniform: no checkpoint inside, not the partial block
+#pragma unroll
+        for (int j = 0; j < kDraws; ++j) total = compound<kExactDiv>(total, a[j]);
+      } else {
+        float t[kDraws];
+#pragma unroll
+        for (int j = 0; j < kDraws; ++j) {
+          total = compound<kExactDiv>(total, a[j]);
+          t[j] = total;
+        }
+        while (next_p <= p_end) {  // next_p <= n_periods, or none is left
+          checkpoint_record(k, ck, pick(t, next_p - blk * kDraws - 1), active, lane, lds_hist, acc);
+          ++ck;
+          next_p = ck < c.n ? c.periods[ck] : 0xffffffffu;
+        }
+        if (p_end > k.n_periods) total = pick(t, last_j);  // draws past the last period are dropped
+      }
+    }
+    if (active && k.d_final) k.d_final[i] = total;
+  }
+
+  __syncthreads();  // every wave is through with the draw tables, and its LDS adds are complete
+  BlockPartial *part = reinterpret_cast<BlockPartial *>(lds_raw);  // [kW][c.n]
+  if (lane < c.n) {
+    BlockPartial p;
+    p.sum = acc.sum;
+    p.sumsq = acc.sumsq;
+    p.count = acc.count;
+    p.below = acc.below;
+    p.underflow = acc.under;
+    p.overflow = acc.over;
+    p.min = acc.min;
+    p.max = acc.max;
+    part[wave * c.n + lane] = p;
+  }
+  __syncthreads();
+  if (threadIdx.x < c.n) {
+    BlockPartial t = part[threadIdx.x];
+    for (uint32_t w = 1; w < kW; ++w) partial_add(t, part[w * c.n + threadIdx.x]);
+    k.partials[static_cast<size_t>(threadIdx.x) * gridDim.x + blockIdx.x] = t;
+  }
+  for (uint32_t b = threadIdx.x; b < hist_words; b += kGroup) {
+    const uint32_t n = lds_hist[b];
+    if (n) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(n));
+  }
+}
+
+// One workgroup per checkpoint: folds its bucket counts out of the accumulator (left zero, as finalize_kernel
+// leaves it) and its n_partials workgroup partials in a fixed order, and writes record blockIdx.x.
+constexpr int kCheckpointFinalizeBlock = 256;
+__global__ __launch_bounds__(kCheckpointFinalizeBlock) void finalize_checkpoints_kernel(
+    const BlockPartial *partials, uint32_t n_partials, unsigned char *records, uint32_t n_bins,
+    unsigned long long *hist_acc) {
+  const size_t record_bytes = sizeof(smmc_stats) + sizeof(unsigned long long) * n_bins;
+  smmc_stats *out = reinterpret_cast<smmc_stats *>(records + blockIdx.x * record_bytes);
+  unsigned long long *hist = reinterpret_cast<unsigned long long *>(out + 1);
+  for (uint32_t b = threadIdx.x; b < n_bins; b += kCheckpointFinalizeBlock) {
+    unsigned long long *src = hist_acc + static_cast<size_t>(blockIdx.x) * n_bins + b;
+    const unsigned long long v = *src;
+    if (v) *src = 0;
+    hist[b] = v;
+  }
+  __shared__ BlockPartial sh[kCheckpointFinalizeBlock];
+  const BlockPartial *mine = partials + static_cast<size_t>(blockIdx.x) * n_partials;
+  BlockPartial t;
+  partial_identity(t);
+  for (uint32_t j = threadIdx.x; j < n_partials; j += kCheckpointFinalizeBlock) partial_add(t, mine[j]);
+  sh[threadIdx.x] = t;
+  __syncthreads();
+  for (uint32_t s = kCheckpointFinalizeBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) partial_add(sh[threadIdx.x], sh[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const BlockPartial &r = sh[0];
+    out->count = r.count;
+    out->below = r.below;
+    out->underflow = r.underflow;
+    out->overflow = r.overflow;
+    out->sum = r.sum;
+    out->sumsq = r.sumsq;
+    out->min = r.min;
+    out->max = r.max;
+    out->n_bins = n_bins;
+    out->reserved = 0;
+  }
+}
+
 // ---- keepdata: every trajectory, path-major ------------------------------------
 //
 // mc_data of mc_simulations_keepdata (src/simulations.cpp:139-186): row i holds the
@@ -1306,6 +1553,8 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(keepdata_comb_kernel<SMMC_MODE_GAUSSIAN, true, false, 1>),
       reinterpret_cast<const void *>(keepdata_comb_kernel<SMMC_MODE_GAUSSIAN, false, false, 2>),
       reinterpret_cast<const void *>(keepdata_comb_kernel<SMMC_MODE_GAUSSIAN, true, false, 2>),
+      reinterpret_cast<const void *>(checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false>),
+      reinterpret_cast<const void *>(checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false>),
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -1468,6 +1717,51 @@ hipError_t launch_keepdata(const KernelArgs &a, bool exact_div, int tile, int wa
                                        : launch_keepdata_mode<kModeTableV2, false>(a, exact_div, tile, waves, grid, stream);
   return table_is_dense(a.table_len) ? launch_keepdata_mode<SMMC_MODE_TABLE, true>(a, exact_div, tile, waves, grid, stream)
                                      : launch_keepdata_mode<SMMC_MODE_TABLE, false>(a, exact_div, tile, waves, grid, stream);
+}
+
+// ---- checkpoints ----
+
+uint32_t checkpoints_group_paths(int32_t mode) { return 64u * checkpoint_waves(mode == SMMC_MODE_TABLE ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN); }
+
+size_t checkpoints_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_checkpoints, uint32_t n_bins) {
+  const bool table = mode == SMMC_MODE_TABLE;
+  const uint32_t front = checkpoint_front_words(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN),
+                                                checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN), n_checkpoints);
+  return (static_cast<size_t>(front) + static_cast<size_t>(n_checkpoints) * n_bins) * 4u;
+}
+
+template <int kMode, bool kDense>
+static hipError_t launch_checkpoints_mode(const KernelArgs &a, const CheckpointArgs &c, bool exact_div, uint32_t grid, size_t lds,
+                                          hipStream_t stream) {
+  const dim3 block(64u * checkpoint_waves(kMode));
+  hipError_t err = exact_div ? allow_lds(checkpoints_kernel<kMode, true, kDense>, lds)
+                             : allow_lds(checkpoints_kernel<kMode, false, kDense>, lds);
+  if (err != hipSuccess) return err;
+  if (exact_div)
+    hipLaunchKernelGGL((checkpoints_kernel<kMode, true, kDense>), dim3(grid), block, lds, stream, a, c);
+  else
+    hipLaunchKernelGGL((checkpoints_kernel<kMode, false, kDense>), dim3(grid), block, lds, stream, a, c);
+  return hipGetLastError();
+}
+
+// a.partials: n_checkpoints x grid entries ([checkpoint][workgroup]); a.d_hist: n_checkpoints x a.n_bins zeroed counters
+hipError_t launch_checkpoints(const KernelArgs &a, const uint32_t *periods, uint32_t n_checkpoints, bool exact_div, uint32_t grid,
+                              hipStream_t stream) {
+  if (n_checkpoints < 1 || n_checkpoints > SMMC_MAX_CHECKPOINTS || a.stream == 2) return hipErrorInvalidValue;
+  CheckpointArgs c;
+  c.n = n_checkpoints;
+  for (uint32_t i = 0; i < SMMC_MAX_CHECKPOINTS; ++i) c.periods[i] = i < n_checkpoints ? periods[i] : 0xffffffffu;
+  const size_t lds = checkpoints_lds_bytes(a.mode, a.table_len, n_checkpoints, a.n_bins);
+  if (a.mode != SMMC_MODE_TABLE) return launch_checkpoints_mode<SMMC_MODE_GAUSSIAN, false>(a, c, exact_div, grid, lds, stream);
+  return table_is_dense(a.table_len) ? launch_checkpoints_mode<SMMC_MODE_TABLE, true>(a, c, exact_div, grid, lds, stream)
+                                     : launch_checkpoints_mode<SMMC_MODE_TABLE, false>(a, c, exact_div, grid, lds, stream);
+}
+
+hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_partials, uint32_t n_checkpoints, void *d_records,
+                                       uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream) {
+  hipLaunchKernelGGL(finalize_checkpoints_kernel, dim3(n_checkpoints), dim3(kCheckpointFinalizeBlock), 0, stream, partials,
+                     n_partials, static_cast<unsigned char *>(d_records), n_bins, hist_acc);
+  return hipGetLastError();
 }
 
 }  // namespace smmc

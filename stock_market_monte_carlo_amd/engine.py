@@ -5,6 +5,7 @@ include/stock_market_monte_carlo/simulations.h of the reference (cited per funct
 the work happens in libsmmc_hip.so on the MI355X.  PyTorch only provides device
 memory and the stream.
 """
+import collections
 import ctypes as C
 import dataclasses
 import os
@@ -29,6 +30,8 @@ class Stats:
     min: float
     max: float
     hist: np.ndarray
+    hist_lo: float = None  # the bucket range, where the producer knows it (simulate_checkpoints; fan() reads it)
+    hist_hi: float = None
 
     @property
     def mean(self):
@@ -60,6 +63,49 @@ def merge_stats_bytes(records):
         src = (C.c_char * len(r)).from_buffer_copy(bytes(r))
         _lib.check(L.smmc_stats_merge(dst, src))
     return bytes(acc)
+
+
+Fan = collections.namedtuple("Fan", "values clipped")
+
+
+def fan(stats_list, quantiles, hist_lo=None, hist_hi=None):
+    """Quantiles over time from checkpoint records: Fan(values, clipped), both [len(stats_list), len(quantiles)].
+    values[k, j] is quantile quantiles[j] (0 .. 1) of record k, interpolated linearly inside the bucket in which the
+    cumulative count -- underflow first, then the buckets -- reaches q * count: right to within one bucket width.
+    A quantile that falls into the underflow or overflow mass cannot be located: it is returned as hist_lo or
+    hist_hi and clipped[k, j] says so (-1 below the range, +1 above it, 0 inside).  NaN for an empty record.
+    The bucket range is taken from the records (Engine.simulate_checkpoints fills it) unless given.
+    The band a caller draws around the plotted lines (examples/visualize_returns_cpu_v2.cpp:397-411 of the
+    reference draws two fixed levels there)."""
+    qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+    if qs.size and (qs.min() < 0.0 or qs.max() > 1.0):
+        raise ValueError("quantiles must lie in [0, 1]")
+    values = np.full((len(stats_list), qs.size), np.nan)
+    clipped = np.zeros((len(stats_list), qs.size), dtype=np.int8)
+    for k, st in enumerate(stats_list):
+        lo = st.hist_lo if hist_lo is None else hist_lo
+        hi = st.hist_hi if hist_hi is None else hist_hi
+        n_bins = len(st.hist)
+        if lo is None or hi is None or not n_bins:
+            raise ValueError("fan() needs records with a histogram and its range")
+        if not st.count:
+            continue
+        hist = np.asarray(st.hist, dtype=np.float64)
+        edges = float(st.underflow) + np.concatenate(([0.0], np.cumsum(hist)))  # cumulative count at the bucket edges
+        width = (float(hi) - float(lo)) / n_bins
+        filled = np.flatnonzero(hist)
+        for j, q in enumerate(qs):
+            target = q * st.count
+            if target < edges[0] or (filled.size == 0 and st.underflow):
+                values[k, j], clipped[k, j] = lo, -1
+            elif target > edges[-1] or filled.size == 0:
+                values[k, j], clipped[k, j] = hi, 1
+            else:
+                b = min(int(np.searchsorted(edges[1:], target, side="left")), n_bins - 1)  # first bucket that closes at >= target
+                b = int(filled[min(np.searchsorted(filled, b), filled.size - 1)])        # ... that holds anything
+                inside = min(max((target - edges[b]) / hist[b], 0.0), 1.0)
+                values[k, j] = lo + (b + inside) * width
+    return Fan(values, clipped)
 
 
 @dataclasses.dataclass
@@ -218,6 +264,59 @@ class Engine:
                                                 ptr(res.chunk_var), ptr(res.stats_raw)))
         self._leave(cur, res.final, res.chunk_mean, res.chunk_var, res.stats_raw)
         return res
+
+    def simulate_checkpoints(self, sim, periods, want_final=False):
+        """The value distribution at chosen periods: ([Stats per checkpoint], final values or None).
+        periods: strictly increasing integers in 1 .. n_periods (any integer sequence), at most
+        _lib.MAX_CHECKPOINTS of them; record k describes the paths' values after periods[k] compounding steps --
+        column periods[k] of simulate_keepdata's trajectories -- with sim's threshold and bucket range
+        (smmc_engine_simulate_checkpoints, include/smmc.h).  Waits for the records; the final values stay on
+        the device."""
+        torch = self._torch
+        per = np.ascontiguousarray([int(p) for p in periods], dtype=np.int64)
+        if per.size and (per.min() < 0 or per.max() > 0xFFFFFFFF):
+            raise ValueError("periods must be non-negative 32-bit integers")
+        per = per.astype(np.uint32)
+        n, rec = int(sim.n_paths), int(self._L.smmc_stats_bytes(sim.n_bins))
+        final = torch.empty(n, dtype=torch.float32, device=self.tdevice) if want_final else None
+        raw = torch.empty(max(per.size, 1) * rec, dtype=torch.uint8, device=self.tdevice)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_checkpoints(
+            self._h, C.byref(sim), per.ctypes.data_as(C.c_void_p), per.size,
+            C.c_void_p(final.data_ptr()) if final is not None and n else None, C.c_void_p(raw.data_ptr())))
+        self._leave(cur, final, raw)
+        self.sync()
+        host = raw.cpu().numpy().tobytes()
+        out = []
+        for k in range(per.size):
+            st = stats_from_bytes(host[k * rec:(k + 1) * rec])
+            st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+            out.append(st)
+        return out, final
+
+    def simulate_checkpoints_raw(self, sim, periods, want_final=False, to_host=False):
+        """The packed records as bytes (n_checkpoints x smmc_stats_bytes(n_bins)) and the final values (numpy, or
+        None): through the device entry, or through smmc_engine_simulate_checkpoints_to_host."""
+        per = np.ascontiguousarray(periods, dtype=np.uint32)
+        n, rec = int(sim.n_paths), int(self._L.smmc_stats_bytes(sim.n_bins))
+        if to_host:
+            buf = np.zeros(max(per.size, 1) * rec, dtype=np.uint8)
+            final = np.empty(n, dtype=np.float32) if want_final else None
+            self._enter()
+            _lib.check(self._L.smmc_engine_simulate_checkpoints_to_host(
+                self._h, C.byref(sim), per.ctypes.data_as(C.c_void_p), per.size,
+                final.ctypes.data_as(C.c_void_p) if final is not None else None, buf.ctypes.data_as(C.c_void_p)))
+            return buf[: per.size * rec].tobytes(), final
+        torch = self._torch
+        final = torch.empty(n, dtype=torch.float32, device=self.tdevice) if want_final else None
+        raw = torch.empty(max(per.size, 1) * rec, dtype=torch.uint8, device=self.tdevice)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_checkpoints(
+            self._h, C.byref(sim), per.ctypes.data_as(C.c_void_p), per.size,
+            C.c_void_p(final.data_ptr()) if final is not None and n else None, C.c_void_p(raw.data_ptr())))
+        self._leave(cur, final, raw)
+        self.sync()
+        return raw.cpu().numpy()[: per.size * rec].tobytes(), (final.cpu().numpy() if final is not None else None)
 
     def read_stats(self, stats_raw):
         """Copies a device record to the host after the engine stream has drained."""

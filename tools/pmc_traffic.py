@@ -14,6 +14,7 @@ it compiles now differs) and `source_sha256` (kernel sources + compiler flags --
 time and reports `traffic: null` for a stale entry).
 
 usage: pmc_traffic.py --key "gaussian|100000000|360|all" --write DIR --fetch DIR --source TEXT
+       pmc_traffic.py --restamp      (sources changed, the profiled kernels' instructions did not: see restamp())
 """
 import argparse
 import csv
@@ -78,6 +79,29 @@ def refresh_valu(out):
         fh.write("\n")
 
 
+def restamp(out):
+    """For a source change that leaves the profiled kernels as they were (new code beside them in the same files):
+    entries whose kernel still compiles to the SAME instructions (isa_fingerprint) get the sources' new digest --
+    the counters were measured on exactly this code -- and a note in `source`; an entry whose kernel changed is an
+    error, as in refresh_valu: that needs a new PMC pass."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import isa_loop_count as I
+    table = json.load(open(out))
+    for key, rec in table.items():
+        ident = build_identity(I.traffic_kernel_of(key))
+        if ident["isa_fingerprint"] != rec["isa_fingerprint"] or ident["kernel"] != rec["kernel"]:
+            raise SystemExit(f"{key}: the kernel changed since the PMC pass: profile again")
+        if ident["source_sha256"] != rec["source_sha256"]:
+            rec["source_sha256"] = ident["source_sha256"]
+            note = "; sources changed beside the kernel since, its instructions did not (isa_fingerprint): digest re-stamped"
+            if note not in rec["source"]:
+                rec["source"] += note
+    with open(out, "w") as fh:
+        json.dump(table, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--key")
@@ -85,10 +109,13 @@ def main():
     ap.add_argument("--fetch")
     ap.add_argument("--source")
     ap.add_argument("--refresh-valu", action="store_true")
+    ap.add_argument("--restamp", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     a = ap.parse_args()
     if a.refresh_valu:
         return refresh_valu(a.out)
+    if a.restamp:
+        return restamp(a.out)
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import isa_loop_count as I
