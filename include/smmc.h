@@ -222,6 +222,69 @@ int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const 
 int smmc_engine_simulate_checkpoints_to_host(smmc_engine *e, const smmc_sim *sim, const uint32_t *periods,
                                              uint32_t n_checkpoints, float *host_final, void *host_records);
 
+/* ---- cash flows: withdrawal and contribution schedules with depletion statistics ------------- */
+
+#define SMMC_MAX_CASHFLOW_PERIODS 4096 /* depletion counters live in LDS: 16 KiB of u32 */
+
+/* What is taken out of (or, negative, paid into) every path after each period's return.  For period t = 1 ..
+ * n_periods, a_t = 100 + r_t as in smmc_engine_simulate, every operation binary32 and rounded on its own:
+ *   g  = (v * a_t) / 100                       update_fund, src/simulations.cpp:14-16
+ *   w  = amount[t-1] + g * fraction[t-1]       the product is rounded, then the sum
+ *   v' = g - w
+ *   live path, v' > floor:     v = v', paid += w
+ *   live path, !(v' > floor):  depleted at t: v = 0, paid += max(g, 0), ruin_period = t (NaN counts as depleted;
+ *                              max is fmaxf: a NaN g pays 0)
+ *   depleted path:             v stays 0, paid and ruin_period stay; its draws are still consumed
+ * amount is in money units, fraction a plain fraction of the value after the period's return (0.004 = 0.4 %).
+ * The reference README's open "withdrawal strategies": a fixed amount every period (amount, fraction 0), some
+ * percentage every period (fraction, amount 0), a varying percentage every period (the arrays; also how a caller
+ * indexes amounts to inflation).  With amount = fraction = 0 and floor = 0 the final values are those of
+ * smmc_engine_simulate, bit for bit, while no multiplier is <= 0. */
+typedef struct smmc_cashflow {
+  uint32_t struct_size;   /* = sizeof(smmc_cashflow) */
+  float amount, fraction; /* used for every period when the array below is NULL */
+  const float *amounts;   /* HOST, n_periods floats, or NULL */
+  const float *fractions; /* HOST, n_periods floats, or NULL */
+  float floor;            /* depleted when !(value > floor); >= 0 */
+} smmc_cashflow;
+
+/* Enqueues one simulation with the cash flow cf on the engine stream and returns without waiting; the host arrays
+ * of cf may be reused on return (the engine stages them).  All outputs are DEVICE pointers, any may be NULL; they
+ * are written, not accumulated into:
+ *   d_final        n_paths final values, 0 for a depleted path
+ *   d_paid         n_paths totals paid out (binary32 running sums in period order, from 0)
+ *   d_ruin_period  n_paths periods of depletion, 0 = never depleted
+ *   d_stats        packed record of the final values, smmc_stats_bytes(sim->n_bins) bytes, 8-byte aligned, with
+ *                  the field rules of smmc_engine_simulate
+ *   d_depleted_at  n_periods + 1 counts: [0] paths never depleted, [t] paths depleted at period t; their sum is
+ *                  n_paths.  8-byte aligned.
+ * A path's outputs depend only on (seed, global path id, parameters, schedule), never on first_path, the shard or
+ * the launch geometry; shards of one request merge by smmc_stats_merge and by adding d_depleted_at.  Integer
+ * fields, min, max, bucket counts and d_depleted_at are exact; sum and sumsq are double sums in a fixed order
+ * (no floating-point atomics): two identical calls give the same bytes.
+ * Divide: the result never depends on the variant.  The proof behind smmc_engine_divide_kind does not carry over
+ * (a live value can come close to 0), so the reciprocal-multiply form is used only when BOTH hold, the IEEE
+ * divide otherwise or with SMMC_FLAG_EXACT_DIV (smmc_engine_cashflow_divide_kind says which):
+ *   below  every live value is above L = the larger of floor and, when every amount is <= 0 and every fraction
+ *          is in [0, 1), capital * min(1, lo (1 - max fraction))^n_periods (lo, hi: the smallest and largest
+ *          multiplier / 100); capital itself is the first live value; min(capital, L) times the smallest
+ *          multiplier stays above 2^-88.  A depleted path's product 0 * a is exact in both forms.
+ *   above  every fraction is in [0, 1], and (capital + the sum of the contributions, the amounts < 0)
+ *          * max(1, hi)^n_periods times the largest multiplier stays below 2^126.
+ * SMMC_ERR_INVALID with a text: NULL cf or a wrong struct_size; n_periods == 0 or > SMMC_MAX_CASHFLOW_PERIODS;
+ * floor negative or not finite; a non-finite amount, fraction or schedule entry; SMMC_FLAG_STREAM_REF or
+ * SMMC_FLAG_STREAM_V2 (counter stream v3 only); the table-mode and bin-count errors of smmc_engine_simulate;
+ * 2^32 paths or more per workgroup (shard the request). */
+int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, float *d_final,
+                                  float *d_paid, uint32_t *d_ruin_period, void *d_stats, uint64_t *d_depleted_at);
+/* Synchronous convenience: the same into HOST memory. */
+int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf,
+                                          float *host_final, float *host_paid, uint32_t *host_ruin_period,
+                                          void *host_stats, uint64_t *host_depleted_at);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT: the divide a smmc_engine_simulate_cashflow of (sim, cf) uses, by the rule above
+ * (never SMMC_DIV_CHECKED), or an error of that call's argument checks. */
+int smmc_engine_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

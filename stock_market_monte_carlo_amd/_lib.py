@@ -29,6 +29,7 @@ MAX_BINS = 4096
 MAX_RANKS = 8
 MAX_CHECKPOINTS = 64
 MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
+MAX_CASHFLOW_PERIODS = 4096  # largest n_periods of a simulate_cashflow call
 
 
 class Sim(C.Structure):
@@ -67,6 +68,18 @@ class Stats(C.Structure):
     ]
 
 
+class Cashflow(C.Structure):
+    """smmc_cashflow"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("amount", C.c_float),
+        ("fraction", C.c_float),
+        ("amounts", C.c_void_p),
+        ("fractions", C.c_void_p),
+        ("floor", C.c_float),
+    ]
+
+
 # every symbol include/smmc.h declares: (name, restype, argtypes)
 DIV_FAST, DIV_EXACT, DIV_CHECKED = 0, 1, 2  # smmc_engine_divide_kind
 MERGE_HOST, MERGE_RCCL = 0, 1  # smmc_group_create
@@ -95,6 +108,11 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("smmc_engine_simulate_checkpoints_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_cashflow", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_cashflow_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_cashflow_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -84,19 +84,7 @@ struct PhaseLog {
   }
 };
 
-// Makes `device` current for the scope and restores the caller's device after.
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
+using smmc::DeviceGuard;  // smmc_internal.h
 
 // Workgroups launched per CU.  About 6 are resident (SGPR-limited); the rest queue and
 // are handed out as others finish, which evens out CU/XCD speed differences: measured
@@ -158,6 +146,7 @@ struct smmc_engine {
   bool hist_dirty = false;
   smmc::BlockPartial *d_ck_partials = nullptr;  // checkpoints_kernel: [checkpoint][workgroup], grown on demand
   size_t ck_partials_cap = 0;
+  smmc::EngineExt ext = {nullptr, nullptr};     // state of another translation unit (smmc_internal.h: engine_ext)
 
   // SMMC_FLAG_STREAM_REF (smmc_ref_kernels.hip)
   float *d_ref_final = nullptr;     // final values of a launch that asked for none (statistics are formed from them)
@@ -693,6 +682,7 @@ void smmc_engine_destroy(smmc_engine *e) {
     (void)hipStreamSynchronize(e->copy_stream);
     (void)hipStreamDestroy(e->copy_stream);
   }
+  if (e->ext.release) e->ext.release(e->ext.state);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->ev_order) (void)hipEventDestroy(e->ev_order);
   for (int i = 0; i < 2; ++i) {
@@ -1687,3 +1677,35 @@ int smmc_stats_merge(void *dst_packed, const void *src_packed) {
 }
 
 }  // extern "C"
+
+// ---- shared with the library's other host translation units (smmc_internal.h) ----
+namespace smmc {
+
+int host_fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+  return code;
+}
+int host_check_sim(const smmc_engine *e, const smmc_sim *s) { return check_sim(e, s); }
+bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a) {
+  return multiplier_bounds(e, s, lo_a, hi_a);
+}
+KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s) { return make_args(e, s); }
+EngineView engine_view(const smmc_engine *e) {
+  return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials};
+}
+EngineExt *engine_ext(smmc_engine *e) { return &e->ext; }
+int engine_acc_begin(smmc_engine *e, unsigned long long **acc) {
+  const int rc = hist_acc_ready(e);
+  if (rc) return rc;
+  *acc = e->d_hist_spread;
+  e->hist_dirty = true;
+  return SMMC_OK;
+}
+void engine_acc_clean(smmc_engine *e) { e->hist_dirty = false; }
+int engine_timing_begin(smmc_engine *e) { return timing_begin(e); }
+int engine_timing_end(smmc_engine *e) { return timing_end(e); }
+
+}  // namespace smmc

@@ -1,0 +1,288 @@
+// smmc_cashflow.cpp -- smmc_engine_simulate_cashflow and its siblings (include/smmc.h): withdrawal and
+// contribution schedules with depletion statistics.
+//
+// A translation unit of its own: smmc_capi.cpp owns struct smmc_engine and never calls into this file; what is
+// needed of an engine comes through smmc_internal.h (engine_view, engine_acc_begin, ...), and what this file keeps
+// per engine -- the staged schedule -- hangs in the engine's extension slot (engine_ext), released by
+// smmc_engine_destroy.  The reference has no counterpart: its README lists withdrawal strategies as open.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "smmc_internal.h"
+
+namespace {
+
+using smmc::DeviceGuard;
+using smmc::host_fail;
+
+#define SMMC_CF_HIP(call)                                                                                          \
+  do {                                                                                                             \
+    hipError_t err__ = (call);                                                                                     \
+    if (err__ != hipSuccess)                                                                                       \
+      return host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
+  } while (0)
+
+// Workgroups per CU, as checkpoints_kernel (smmc_capi.cpp): a workgroup flushes n_periods + 1 + n_bins counters.
+constexpr uint32_t kCashflowGroupsPerCU = 32;
+// schedule entries per array as staged: n_periods rounded up to whole Philox blocks (8 draws at the most)
+constexpr uint32_t kStrideMax = (SMMC_MAX_CASHFLOW_PERIODS + 7u) & ~7u;
+// The depletion counters take the engine's accumulator from copy 1 on (copy 0 holds the final-value histogram).
+constexpr size_t kDepletedAt = SMMC_MAX_BINS;
+static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
+              "the engine's accumulator holds the histogram and the depletion counters");
+
+// The staged schedule of an engine.  The caller's arrays may be reused on return, so a call copies them into one of
+// kSlots page-locked slots and enqueues the upload from there; a slot is reused only after the upload that read it
+// has finished (its event).  One device copy is enough: the upload of a call is ordered behind the kernel of the
+// call before it on the engine stream.
+constexpr int kSlots = 4;
+struct CashflowState {
+  float *h_slots = nullptr;  // page-locked, kSlots x 2 x kStrideMax
+  float *d_schedule = nullptr;  // 2 x kStrideMax
+  hipEvent_t uploaded[kSlots] = {nullptr, nullptr, nullptr, nullptr};
+  bool in_flight[kSlots] = {false, false, false, false};
+  int next = 0;
+};
+
+void release_state(void *p) {
+  CashflowState *st = static_cast<CashflowState *>(p);
+  if (!st) return;
+  for (hipEvent_t ev : st->uploaded)
+    if (ev) (void)hipEventDestroy(ev);
+  if (st->h_slots) (void)hipHostFree(st->h_slots);
+  if (st->d_schedule) (void)hipFree(st->d_schedule);
+  delete st;
+}
+
+// Device must be current.
+int state_of(smmc_engine *e, CashflowState **out) {
+  smmc::EngineExt *ext = smmc::engine_ext(e);
+  if (!ext->state) {
+    CashflowState *st = new (std::nothrow) CashflowState();
+    if (!st) return host_fail(SMMC_ERR_NOMEM, "out of host memory");
+    ext->state = st;
+    ext->release = release_state;
+    const size_t bytes = sizeof(float) * 2u * kStrideMax;
+    SMMC_CF_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->h_slots), bytes * kSlots, hipHostMallocDefault));
+    SMMC_CF_HIP(hipMalloc(reinterpret_cast<void **>(&st->d_schedule), bytes));
+    for (hipEvent_t &ev : st->uploaded) SMMC_CF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  *out = static_cast<CashflowState *>(ext->state);
+  if (!(*out)->h_slots || !(*out)->d_schedule || !(*out)->uploaded[kSlots - 1])
+    return host_fail(SMMC_ERR_HIP, "the engine's cash-flow staging buffers could not be allocated earlier");
+  return SMMC_OK;
+}
+
+bool varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }
+float amount_at(const smmc_cashflow *cf, uint32_t t) { return cf->amounts ? cf->amounts[t] : cf->amount; }
+float fraction_at(const smmc_cashflow *cf, uint32_t t) { return cf->fractions ? cf->fractions[t] : cf->fraction; }
+
+int check_cashflow(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
+  int rc = smmc::host_check_sim(e, sim);
+  if (rc) return rc;
+  if (!cf) return host_fail(SMMC_ERR_INVALID, "cf is NULL");
+  if (cf->struct_size != sizeof(smmc_cashflow))
+    return host_fail(SMMC_ERR_INVALID, "smmc_cashflow.struct_size is %u, this library expects %zu", cf->struct_size,
+                     sizeof(smmc_cashflow));
+  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
+    return host_fail(SMMC_ERR_INVALID, "cash flows support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
+                     (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  if (sim->n_periods == 0) return host_fail(SMMC_ERR_INVALID, "n_periods is 0: a cash flow needs at least one period");
+  if (sim->n_periods > SMMC_MAX_CASHFLOW_PERIODS)
+    return host_fail(SMMC_ERR_INVALID, "n_periods %u exceeds SMMC_MAX_CASHFLOW_PERIODS %d", sim->n_periods,
+                     SMMC_MAX_CASHFLOW_PERIODS);
+  if (!std::isfinite(cf->floor) || cf->floor < 0.0f)
+    return host_fail(SMMC_ERR_INVALID, "floor must be finite and >= 0 (got %g)", static_cast<double>(cf->floor));
+  if (!cf->amounts && !std::isfinite(cf->amount))
+    return host_fail(SMMC_ERR_INVALID, "amount is not finite");
+  if (!cf->fractions && !std::isfinite(cf->fraction))
+    return host_fail(SMMC_ERR_INVALID, "fraction is not finite");
+  for (uint32_t t = 0; t < sim->n_periods; ++t) {
+    if (cf->amounts && !std::isfinite(cf->amounts[t])) return host_fail(SMMC_ERR_INVALID, "amounts[%u] is not finite", t);
+    if (cf->fractions && !std::isfinite(cf->fractions[t])) return host_fail(SMMC_ERR_INVALID, "fractions[%u] is not finite", t);
+  }
+  return SMMC_OK;
+}
+
+// The rule of include/smmc.h (smmc_engine_simulate_cashflow, "Divide").  The two-instruction divide is exact for
+// products of at least 2^-114; as smmc_capi.cpp the host keeps them above 2^-89 and below 2^127, one bit of margin
+// on each side for the roundings along a path.
+int cashflow_divide(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
+  if (sim->flags & SMMC_FLAG_EXACT_DIV) return SMMC_DIV_EXACT;
+  const double cap = sim->initial_capital;
+  if (!(cap > 0.0) || !std::isfinite(cap)) return SMMC_DIV_EXACT;
+  double lo_a, hi_a;
+  if (!smmc::host_multiplier_bounds(e, sim, &lo_a, &hi_a)) return SMMC_DIV_EXACT;
+  const uint32_t n = sim->n_periods, n_sched = varying(cf) ? n : 1u;
+  double contributions = 0.0, max_amount = -INFINITY, min_fraction = INFINITY, max_fraction = -INFINITY;
+  for (uint32_t t = 0; t < n_sched; ++t) {
+    const double am = amount_at(cf, t), fr = fraction_at(cf, t);
+    if (am < 0.0) contributions += -am * (varying(cf) ? 1.0 : static_cast<double>(n));
+    max_amount = std::max(max_amount, am);
+    min_fraction = std::min(min_fraction, fr);
+    max_fraction = std::max(max_fraction, fr);
+  }
+  if (!(min_fraction >= 0.0 && max_fraction <= 1.0)) return SMMC_DIV_EXACT;
+  const double p = n;
+  // above: w >= -|amount| for a live path (g >= 0, fraction >= 0), so a value never exceeds what the capital and
+  // all contributions, paid in at once, grow to
+  const double grow = std::max(0.0, std::log2(hi_a / 100.0));
+  if (!(std::log2(cap + contributions) + p * grow + std::log2(hi_a) + 1.0 < 127.0)) return SMMC_DIV_EXACT;
+  // below: a live value is the capital, or above the floor, or -- nothing but contributions and fractions below
+  // 1 -- at least the capital shrunk by the worst period n times
+  double live_log2 = cf->floor > 0.0f ? std::log2(static_cast<double>(cf->floor)) : -INFINITY;
+  if (max_amount <= 0.0 && max_fraction < 1.0) {
+    const double shrink = std::min(0.0, std::log2(lo_a / 100.0 * (1.0 - max_fraction)));
+    live_log2 = std::max(live_log2, std::log2(cap) + p * shrink);
+  }
+  live_log2 = std::min(live_log2, std::log2(cap));
+  if (!(live_log2 + std::min(0.0, std::log2(lo_a)) - 1.0 > -89.0)) return SMMC_DIV_EXACT;
+  return SMMC_DIV_FAST;
+}
+
+uint32_t launch_grid(const smmc::EngineView &v, const smmc_sim *sim, uint32_t group_paths) {
+  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
+  return static_cast<uint32_t>(std::min<uint64_t>(n_chunks, std::min(v.compute_units * kCashflowGroupsPerCU, v.max_grid)));
+}
+
+int check_outputs(const void *fin, const void *paid, const void *ruin, const void *stats, const void *dep) {
+  if ((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(paid) | reinterpret_cast<uintptr_t>(ruin)) & 3u)
+    return host_fail(SMMC_ERR_INVALID, "the final-value, paid and ruin-period pointers must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(dep)) & 7u)
+    return host_fail(SMMC_ERR_INVALID, "the statistics and depletion-count pointers must be 8-byte aligned");
+  return SMMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smmc_engine_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
+  const int rc = check_cashflow(e, sim, cf);
+  if (rc) return rc;
+  return cashflow_divide(e, sim, cf);
+}
+
+int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, float *d_final,
+                                  float *d_paid, uint32_t *d_ruin_period, void *d_stats, uint64_t *d_depleted_at) {
+  int rc = check_cashflow(e, sim, cf);
+  if (rc) return rc;
+  rc = check_outputs(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
+  if (rc) return rc;
+  const smmc::EngineView view = smmc::engine_view(e);
+  const uint32_t group_paths = smmc::cashflow_group_paths(sim->mode);
+  const uint32_t grid = launch_grid(view, sim, group_paths);
+  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS counters)
+  if (grid && ((sim->n_paths + group_paths - 1) / group_paths + grid - 1) / grid * group_paths >= (1ull << 32))
+    return host_fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
+                     static_cast<unsigned long long>(sim->n_paths));
+  smmc::KernelArgs a = smmc::host_make_args(e, sim);
+  if (!d_stats) a.n_bins = 0;
+  const size_t lds = smmc::cashflow_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
+  if (lds + 2048 > view.max_lds)
+    return host_fail(SMMC_ERR_INVALID, "table, depletion counters and histogram need %zu bytes of LDS, device allows %zu", lds,
+                     view.max_lds);
+  DeviceGuard guard(view.device);
+  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+
+  smmc::CashflowArgs c;
+  std::memset(&c, 0, sizeof c);
+  c.amount = cf->amount;
+  c.fraction = cf->fraction;
+  c.floor = cf->floor;
+  c.d_paid = d_paid;
+  c.d_ruin_period = d_ruin_period;
+  if (varying(cf) && grid) {
+    CashflowState *st = nullptr;
+    rc = state_of(e, &st);
+    if (rc) return rc;
+    const int slot = st->next;
+    if (st->in_flight[slot]) SMMC_CF_HIP(hipEventSynchronize(st->uploaded[slot]));
+    st->in_flight[slot] = false;
+    const uint32_t stride = (sim->n_periods + 7u) & ~7u;
+    float *h = st->h_slots + static_cast<size_t>(slot) * 2u * kStrideMax;
+    for (uint32_t t = 0; t < stride; ++t) {
+      h[t] = t < sim->n_periods ? amount_at(cf, t) : 0.0f;
+      h[stride + t] = t < sim->n_periods ? fraction_at(cf, t) : 0.0f;
+    }
+    SMMC_CF_HIP(hipMemcpyAsync(st->d_schedule, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
+    SMMC_CF_HIP(hipEventRecord(st->uploaded[slot], view.stream));
+    st->in_flight[slot] = true;
+    st->next = (slot + 1) % kSlots;
+    c.schedule = st->d_schedule;
+    c.stride = stride;
+  }
+  a.d_final = d_final;
+  unsigned long long *acc = nullptr;
+  const bool use_acc = (d_stats && sim->n_bins) || d_depleted_at;
+  if (use_acc) {  // zero now, and zero again after the finalize launches below
+    rc = smmc::engine_acc_begin(e, &acc);
+    if (rc) return rc;
+  }
+  if (d_stats) {
+    a.partials = view.d_partials;
+    a.d_hist = sim->n_bins ? acc : nullptr;
+  }
+  if (d_depleted_at) c.d_depleted = acc + kDepletedAt;
+  if (grid) {
+    const bool exact_div = cashflow_divide(e, sim, cf) != SMMC_DIV_FAST;
+    rc = smmc::engine_timing_begin(e);
+    if (rc) return rc;
+    const hipError_t err = smmc::launch_cashflow(a, c, exact_div, grid, view.stream);
+    if (err != hipSuccess) {
+      (void)smmc::engine_timing_end(e);
+      return host_fail(SMMC_ERR_HIP, "launch_cashflow failed: %s", hipGetErrorString(err));
+    }
+    rc = smmc::engine_timing_end(e);
+    if (rc) return rc;
+  }
+  if (d_stats)
+    SMMC_CF_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), sim->n_bins, view.stream,
+                                      sim->n_bins ? acc : nullptr, sim->n_bins ? 1u : 0u));
+  if (d_depleted_at)
+    SMMC_CF_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
+                                               reinterpret_cast<unsigned long long *>(d_depleted_at), view.stream));
+  if (use_acc) smmc::engine_acc_clean(e);
+  return SMMC_OK;
+}
+
+int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, float *host_final,
+                                          float *host_paid, uint32_t *host_ruin_period, void *host_stats,
+                                          uint64_t *host_depleted_at) {
+  int rc = check_cashflow(e, sim, cf);
+  if (rc) return rc;
+  const smmc::EngineView view = smmc::engine_view(e);
+  DeviceGuard guard(view.device);
+  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  // one device allocation for all outputs, the 8-byte aligned ones first
+  const size_t stats_bytes = host_stats ? static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) : 0;
+  const size_t dep_bytes = host_depleted_at ? sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u) : 0;
+  const size_t per_path = sizeof(float) * sim->n_paths;
+  const size_t final_bytes = host_final ? per_path : 0, paid_bytes = host_paid ? per_path : 0,
+               ruin_bytes = host_ruin_period ? per_path : 0;
+  const size_t total = stats_bytes + dep_bytes + final_bytes + paid_bytes + ruin_bytes;
+  char *d = nullptr;
+  if (total) SMMC_CF_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
+  char *d_stats = d, *d_dep = d_stats + stats_bytes, *d_fin = d_dep + dep_bytes, *d_paid = d_fin + final_bytes,
+       *d_ruin = d_paid + paid_bytes;
+  rc = smmc_engine_simulate_cashflow(e, sim, cf, final_bytes ? reinterpret_cast<float *>(d_fin) : nullptr,
+                                     paid_bytes ? reinterpret_cast<float *>(d_paid) : nullptr,
+                                     ruin_bytes ? reinterpret_cast<uint32_t *>(d_ruin) : nullptr, stats_bytes ? d_stats : nullptr,
+                                     dep_bytes ? reinterpret_cast<uint64_t *>(d_dep) : nullptr);
+  hipError_t err = hipStreamSynchronize(view.stream);  // also after a failure: nothing of the call may outlive its buffer
+  struct Piece { void *host; const char *dev; size_t bytes; };
+  const Piece pieces[5] = {{host_stats, d_stats, stats_bytes}, {host_depleted_at, d_dep, dep_bytes}, {host_final, d_fin, final_bytes},
+                           {host_paid, d_paid, paid_bytes}, {host_ruin_period, d_ruin, ruin_bytes}};
+  for (const Piece &p : pieces)
+    if (rc == SMMC_OK && err == hipSuccess && p.bytes) err = hipMemcpy(p.host, p.dev, p.bytes, hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (rc) return rc;
+  if (err != hipSuccess) return host_fail(SMMC_ERR_HIP, "simulate_cashflow_to_host: %s", hipGetErrorString(err));
+  return SMMC_OK;
+}
+
+}  // extern "C"

@@ -148,8 +148,69 @@ hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_
                                        void *d_records, uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream);
 uint32_t checkpoints_group_paths(int32_t mode);
 size_t checkpoints_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_checkpoints, uint32_t n_bins);
+// cashflow_kernel (smmc_engine_simulate_cashflow, csrc/smmc_cashflow.cpp; counter stream v3 only): the paths of
+// paths_kernel with a withdrawal / contribution step after every period's return ("Cash flows").
+struct CashflowArgs {
+  float amount, fraction;   // every period's entries when `schedule` is null
+  float floor;              // a path is depleted when !(value > floor)
+  const float *schedule;    // device, nullable: amounts[stride] then fractions[stride]; entries beyond n_periods are 0
+  uint32_t stride;          // n_periods rounded up to a multiple of 8 (whole Philox blocks are read)
+  float *d_paid;            // nullable: n_paths totals paid out
+  uint32_t *d_ruin_period;  // nullable: n_paths periods of depletion, 0 = never
+  unsigned long long *d_depleted;  // nullable: n_periods + 1 counters, zero before the launch ([0]: never depleted)
+};
+// a.partials: `grid` entries (one per workgroup) or null; a.d_hist: a.n_bins counters, zero before the launch.  A
+// workgroup walks chunks of cashflow_group_paths(mode) consecutive paths.
+hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, hipStream_t stream);
+// d_out[i] = acc[i] for i < n, and leaves acc zero (the engine's accumulator between launches)
+hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream);
+uint32_t cashflow_group_paths(int32_t mode);
+size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
+
+// ---- what smmc_capi.cpp shares with the library's other host translation units (smmc_cashflow.cpp) ----------
+// Defined in smmc_capi.cpp, which owns struct smmc_engine; a unit that adds an entry point goes through these and
+// keeps what it needs per engine in its own state (engine_ext), so that smmc_capi.cpp never calls into it.
+
+// Makes `device` current for the scope and restores the caller's device after.
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != device) ok = hipSetDevice(device) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+struct EngineView {  // what a launch needs to know of an engine
+  int device;
+  hipStream_t stream;
+  uint32_t compute_units, max_grid;
+  size_t max_lds;
+  BlockPartial *d_partials;  // max_grid entries
+};
+struct EngineExt {  // one slot of state owned by another translation unit: smmc_engine_destroy calls release(state)
+  void *state;
+  void (*release)(void *state);
+};
+int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));  // sets smmc_last_error()
+int host_check_sim(const smmc_engine *e, const smmc_sim *s);
+// bounds on a = 100 + r of one period; false if there are none (smmc_capi.cpp, divide_kind)
+bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
+KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
+EngineView engine_view(const smmc_engine *e);
+EngineExt *engine_ext(smmc_engine *e);
+// The engine's zeroed accumulator (kHistSpread x SMMC_MAX_BINS counters; a launch that adds into it must have its
+// finalize put it back to zero): *acc is ready, and marked dirty until engine_acc_clean says the finalize is queued.
+int engine_acc_begin(smmc_engine *e, unsigned long long **acc);
+void engine_acc_clean(smmc_engine *e);
+int engine_timing_begin(smmc_engine *e);
+int engine_timing_end(smmc_engine *e);
 
 }  // namespace smmc

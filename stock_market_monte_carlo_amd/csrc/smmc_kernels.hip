@@ -1509,6 +1509,192 @@ __global__ __launch_bounds__(kBlock) void selftest_kernel(uint32_t lo, uint32_t 
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, bad);
 }
 
+// ---- cash flows: a withdrawal or contribution after every period's return -------------------------
+//
+// smmc_engine_simulate_cashflow ("Cash flows"): the draws of paths_kernel, and after each period's
+//   g = (v * a) / 100             update_fund, as compound<>()
+// the step, every operation a binary32 rounding of its own (__fmul_rn, __fadd_rn, __fsub_rn: nothing may fuse)
+//   w = amount + g * fraction,  v' = g - w
+//   live lane, v' > floor:     v = v', paid += w
+//   live lane, !(v' > floor):  depleted at this period: v = 0, paid += max(g, 0), ruin_period = t  (NaN is depleted)
+//   depleted lane:             nothing changes; its draws are still made, so the stream position of a path never
+//                              depends on what happened to it
+// Bound like paths_kernel: VALU issue.  Nine VALU instructions per period on top of the compounding chain: multiply,
+// add, subtract, compare, the select of v, max, the select of what is paid, its add, the select of ruin_period.  The
+// "live" flag is a lane mask in a scalar register pair and is combined with the compare on the scalar unit;
+// depletion is per lane, control flow stays wave-uniform.  A depleted lane holds v = 0, so its product and
+// its divide (either form: 0 * a is exact in both) stay 0; the mask, not the arithmetic, keeps it from coming back
+// when a contribution (amount < 0) would lift v' above the floor.
+//
+// Work split, as checkpoints_kernel: a WAVE owns a chunk of 64 consecutive paths and walks the chunks
+// wc = blockIdx.x * kW + wave, + gridDim.x * kW, ... without a barrier; every lane runs a path, also beyond
+// n_paths in the launch's last chunk (such a lane stores and counts nothing).
+//
+// Schedule.  kVarying = false: amount and fraction are kernel arguments, two scalar registers, no loads.
+// kVarying = true: the period index is wave-uniform, so the entries of a Philox block are read with scalar loads
+// through the constant address space (one wide load per array and block, issued before the block's Philox rounds);
+// the host pads both arrays to whole blocks.  No per-lane global load in the loop.
+//
+// Outputs.  A lane adds its final value to per-lane statistics accumulators as paths_kernel does (one partial per
+// workgroup, folded by finalize_kernel), one LDS add into the final-value histogram and one into the
+// [n_periods + 1] depletion counters behind the draw tables; both are flushed with 64-bit integer atomics at the
+// end.  The u32 counters count paths of ONE workgroup: the host refuses a launch in which a workgroup would get
+// 2^32 or more (smmc_cashflow.cpp).
+typedef const __attribute__((address_space(4))) float *const_float_ptr;  // scalar (uniform) loads
+
+template <bool kExactDiv>
+__device__ __forceinline__ void cashflow_step(float a, float amount, float fraction, float floor, uint32_t t, float &v,
+                                              float &paid, uint32_t &ruin, bool &alive) {
+  const float g = compound<kExactDiv>(v, a);
+  const float w = __fadd_rn(amount, __fmul_rn(g, fraction));
+  const float vn = __fsub_rn(g, w);
+  const bool goes_on = alive && vn > floor;  // false for NaN
+  const bool dies = alive && !goes_on;
+  v = goes_on ? vn : 0.0f;
+  paid = __fadd_rn(paid, goes_on ? w : fmaxf(g, 0.0f));  // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0)
+  ruin = dies ? t : ruin;
+  alive = goes_on;
+}
+
+template <int kMode, bool kExactDiv, bool kDense, bool kVarying>
+__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *lds_table = reinterpret_cast<float *>(lds_raw);
+  const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
+  uint32_t *lds_dep = reinterpret_cast<uint32_t *>(lds_raw) + table_words;  // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);                        // [n_bins]
+  const uint32_t counter_words = k.n_periods + 1u + k.n_bins;
+  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(reinterpret_cast<uint32_t *>(lds_raw) +
+                                                             ((table_words + counter_words + 1u) & ~1u));  // [kW]
+
+  stage_tables<kMode>(k, lds_table, kGroup);
+  for (uint32_t i = threadIdx.x; i < counter_words; i += kGroup) lds_dep[i] = 0u;
+  __syncthreads();
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double sum = 0.0, sumsq = 0.0;
+  uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
+  float vmin = __builtin_inff(), vmax = -__builtin_inff();
+  const DrawRegs dr = make_draw_regs(k);
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+
+  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
+  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
+  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
+       wc += static_cast<uint64_t>(gridDim.x) * kW) {
+    const uint64_t i = wc * 64u + lane;
+    const bool active = i < k.n_paths;
+    const uint64_t path = k.first_path + i;
+    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+    float v = k.initial_capital, paid = 0.0f;
+    uint32_t ruin = 0u;
+    bool alive = true;
+    for (uint32_t blk = 0; blk < full; ++blk) {
+      float am[kDraws], fr[kDraws];
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j) {
+        am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+        fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+      }
+      float a[kDraws];
+      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j)
+        cashflow_step<kExactDiv>(a[j], am[j], fr[j], c.floor, blk * kDraws + j + 1u, v, paid, ruin, alive);
+    }
+    if (rem) {  // wave-uniform: the path's last, partial block (the schedule is padded to whole blocks)
+      float am[kDraws], fr[kDraws];
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j) {
+        am[j] = kVarying ? amounts[full * kDraws + j] : c.amount;
+        fr[j] = kVarying ? fractions[full * kDraws + j] : c.fraction;
+      }
+      float a[kDraws];
+      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
+#pragma unroll
+      for (int j = 0; j < kDraws - 1; ++j)
+        if (static_cast<uint32_t>(j) < rem)
+          cashflow_step<kExactDiv>(a[j], am[j], fr[j], c.floor, full * kDraws + j + 1u, v, paid, ruin, alive);
+    }
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) {  // the final value's statistics, as paths_kernel forms them
+      const double dv = static_cast<double>(v);
+      sum += dv;
+      sumsq += dv * dv;
+      n_count += 1;
+      n_below += (v < k.below_threshold) ? 1u : 0u;
+      vmin = fminf(vmin, v);
+      vmax = fmaxf(vmax, v);
+      if (want_hist) {
+        if (v < k.hist_lo) {
+          n_under += 1;
+        } else if (v < k.hist_hi) {
+          int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
+          b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
+          atomicAdd(&lds_hist[b], 1u);
+        } else {
+          n_over += 1;
+        }
+      }
+    }
+  }
+
+  if (want_stats) {
+    BlockPartial p;
+    p.sum = wave_sum(sum);
+    p.sumsq = wave_sum(sumsq);
+    p.count = wave_sum(static_cast<unsigned long long>(n_count));
+    p.below = wave_sum(static_cast<unsigned long long>(n_below));
+    p.underflow = wave_sum(static_cast<unsigned long long>(n_under));
+    p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
+    p.min = wave_min(vmin);
+    p.max = wave_max(vmax);
+    if (lane == 0) wave_part[wave] = p;
+  }
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) {
+    BlockPartial t = wave_part[0];
+    for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[w]);
+    k.partials[blockIdx.x] = t;
+  }
+  if (want_dep) {
+    for (uint32_t b = threadIdx.x; b <= k.n_periods; b += kGroup) {
+      const uint32_t n = lds_dep[b];
+      if (n) atomicAdd(&c.d_depleted[b], static_cast<unsigned long long>(n));
+    }
+  }
+  if (want_hist) {
+    for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
+      const uint32_t n = lds_hist[b];
+      if (n) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(n));
+    }
+  }
+}
+
+// d_out[i] = acc[i], and acc is left zero for the next launch (as finalize_kernel leaves the bucket accumulator).
+__global__ __launch_bounds__(kBlock) void finalize_depleted_kernel(unsigned long long *acc, uint32_t n, unsigned long long *d_out) {
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const unsigned long long v = acc[i];
+    if (v) acc[i] = 0;
+    d_out[i] = v;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
@@ -1555,6 +1741,10 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(keepdata_comb_kernel<SMMC_MODE_GAUSSIAN, true, false, 2>),
       reinterpret_cast<const void *>(checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false>),
       reinterpret_cast<const void *>(checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false>),
+      reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, false>),
+      reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, false>),
+      reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, true>),
+      reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, true>),
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -1761,6 +1951,52 @@ hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_
                                        uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream) {
   hipLaunchKernelGGL(finalize_checkpoints_kernel, dim3(n_checkpoints), dim3(kCheckpointFinalizeBlock), 0, stream, partials,
                      n_partials, static_cast<unsigned char *>(d_records), n_bins, hist_acc);
+  return hipGetLastError();
+}
+
+// ---- cash flows ----
+
+uint32_t cashflow_group_paths(int32_t mode) { return checkpoints_group_paths(mode); }
+
+size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
+  // [draw tables][depletion counters n_periods + 1][histogram][pad to 8 bytes][one BlockPartial per wave]
+  const bool table = mode == SMMC_MODE_TABLE;
+  const size_t words = (static_cast<size_t>(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN)) + n_periods + 1u + n_bins + 1u) &
+                       ~static_cast<size_t>(1);
+  return words * 4u + checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN) * sizeof(BlockPartial);
+}
+
+template <int kMode, bool kDense, bool kExactDiv>
+static hipError_t launch_cashflow_variant(const KernelArgs &a, const CashflowArgs &c, uint32_t grid, size_t lds, hipStream_t stream) {
+  const dim3 block(64u * checkpoint_waves(kMode));
+  hipError_t err = c.schedule ? allow_lds(cashflow_kernel<kMode, kExactDiv, kDense, true>, lds)
+                              : allow_lds(cashflow_kernel<kMode, kExactDiv, kDense, false>, lds);
+  if (err != hipSuccess) return err;
+  if (c.schedule)
+    hipLaunchKernelGGL((cashflow_kernel<kMode, kExactDiv, kDense, true>), dim3(grid), block, lds, stream, a, c);
+  else
+    hipLaunchKernelGGL((cashflow_kernel<kMode, kExactDiv, kDense, false>), dim3(grid), block, lds, stream, a, c);
+  return hipGetLastError();
+}
+
+template <int kMode, bool kDense>
+static hipError_t launch_cashflow_mode(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, size_t lds,
+                                       hipStream_t stream) {
+  return exact_div ? launch_cashflow_variant<kMode, kDense, true>(a, c, grid, lds, stream)
+                   : launch_cashflow_variant<kMode, kDense, false>(a, c, grid, lds, stream);
+}
+
+hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (c.schedule && (c.stride % 8u != 0u || c.stride < a.n_periods)) return hipErrorInvalidValue;
+  const size_t lds = cashflow_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
+  if (a.mode != SMMC_MODE_TABLE) return launch_cashflow_mode<SMMC_MODE_GAUSSIAN, false>(a, c, exact_div, grid, lds, stream);
+  return table_is_dense(a.table_len) ? launch_cashflow_mode<SMMC_MODE_TABLE, true>(a, c, exact_div, grid, lds, stream)
+                                     : launch_cashflow_mode<SMMC_MODE_TABLE, false>(a, c, exact_div, grid, lds, stream);
+}
+
+hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream) {
+  hipLaunchKernelGGL(finalize_depleted_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, acc, n, d_out);
   return hipGetLastError();
 }
 

@@ -116,6 +116,31 @@ class SimResult:
     stats_raw: object = None    # torch.uint8 [smmc_stats_bytes(n_bins)] on device, or None
 
 
+@dataclasses.dataclass
+class CashflowResult:
+    """What Engine.simulate_cashflow returns: the outputs that were asked for, None for the others."""
+    n_paths: int
+    n_periods: int
+    final: object = None         # torch.float32 [n_paths] on the engine's device: 0 for a depleted path
+    paid: object = None          # torch.float32 [n_paths]: the total paid out to each path
+    ruin_period: object = None   # torch.int32 [n_paths] holding uint32 values: period of depletion, 0 = never
+    stats: Stats = None          # record of the final values
+    depleted_at: np.ndarray = None  # uint64 [n_periods + 1]: [0] never depleted, [t] depleted at period t
+
+    def survival(self):
+        """Share of paths still alive after each period: [0] = 1, [t] = 1 - (paths depleted at periods 1 .. t) / n;
+        length n_periods + 1."""
+        if self.depleted_at is None:
+            raise ValueError("survival() needs depleted_at (want_depleted_at=True)")
+        d = np.asarray(self.depleted_at, dtype=np.float64)
+        n = d.sum()
+        if n == 0:
+            return np.full(d.size, np.nan)
+        gone = np.cumsum(d)
+        gone -= d[0]  # [0] counts the paths that were never depleted
+        return 1.0 - gone / n
+
+
 class Engine:
     """One engine per (process, device): table, workspace and stream stay resident."""
 
@@ -317,6 +342,97 @@ class Engine:
         self._leave(cur, final, raw)
         self.sync()
         return raw.cpu().numpy()[: per.size * rec].tobytes(), (final.cpu().numpy() if final is not None else None)
+
+    # -- cash flows: withdrawal and contribution schedules (smmc_engine_simulate_cashflow) ------------
+    @staticmethod
+    def make_cashflow(n_periods, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0):
+        """(smmc_cashflow, the arrays it points to): keep the second alive until the call has returned."""
+        keep = []
+        cf = _lib.Cashflow()
+        cf.struct_size = C.sizeof(_lib.Cashflow)
+        cf.amount, cf.fraction, cf.floor = float(amount), float(fraction), float(floor)
+        for name, arr in (("amounts", amounts), ("fractions", fractions)):
+            if arr is None:
+                continue
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            if a.ndim != 1 or a.size != int(n_periods):
+                raise ValueError(f"{name} must hold n_periods = {int(n_periods)} entries")
+            keep.append(a)
+            setattr(cf, name, a.ctypes.data)
+        return cf, keep
+
+    def simulate_cashflow(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0,
+                          want_final=True, want_paid=False, want_ruin_period=False, want_stats=False,
+                          want_depleted_at=True):
+        """One simulation in which, after every period's return, amount + fraction * value is taken out of every
+        path (negative amounts are contributions): a fixed amount, some percentage, or per-period arrays of
+        n_periods entries (amounts, fractions).  A path whose value would not stay above `floor` is depleted: it pays
+        out what is left and stays at 0.  Returns a CashflowResult; per-path outputs stay on the device,
+        stats and depleted_at are read back (that waits).  include/smmc.h states the arithmetic."""
+        raw = self.simulate_cashflow_raw(sim, amount, fraction, amounts, fractions, floor, want_final, want_paid,
+                                         want_ruin_period, want_stats, want_depleted_at)
+        res = CashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_cashflow_raw(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0,
+                              want_final=True, want_paid=False, want_ruin_period=False, want_stats=False,
+                              want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, paid (float32),
+        ruin_period (int32 holding uint32 values), stats_raw (uint8, the packed record) and depleted_at (int64
+        holding uint64 counts, n_periods + 1); None for what was not asked for."""
+        torch = self._torch
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, count, dtype: torch.empty(count, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        out = {"final": new(want_final, n, torch.float32), "paid": new(want_paid, n, torch.float32),
+               "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_cashflow(
+            self._h, C.byref(sim), C.byref(cf), ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
+            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
+        self._leave(cur, *out.values())
+        del keep
+        return out
+
+    def simulate_cashflow_to_host(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0,
+                                  want_final=True, want_paid=False, want_ruin_period=False, want_stats=False,
+                                  want_depleted_at=True):
+        """The same through smmc_engine_simulate_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, count, dtype: np.zeros(count, dtype=dtype) if want else None  # noqa: E731
+        out = {"final": new(want_final, n, np.float32), "paid": new(want_paid, n, np.float32),
+               "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_cashflow_to_host(
+            self._h, C.byref(sim), C.byref(cf), ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
+            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
+        del keep
+        if want_stats:
+            out["stats_raw"] = out["stats_raw"].tobytes()
+        return out
+
+    def cashflow_divide_kind(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_cashflow uses for this request (results never depend on it)."""
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        rc = self._L.smmc_engine_cashflow_divide_kind(self._h, C.byref(sim), C.byref(cf))
+        del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
 
     def read_stats(self, stats_raw):
         """Copies a device record to the host after the engine stream has drained."""
