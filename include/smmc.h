@@ -285,6 +285,65 @@ int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, c
  * (never SMMC_DIV_CHECKED), or an error of that call's argument checks. */
 int smmc_engine_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf);
 
+/* ---- excursions: drawdown, running extremes, first passage of levels -------------------------- */
+
+#define SMMC_MAX_EXCURSION_PERIODS 4096 /* two arrays of n_periods + 1 u32 first-passage counters live in LDS */
+
+/* What happened ALONG a path, reduced while its value is in a register.  For a path with values v_0 =
+ * initial_capital and v_t, t = 1 .. n_periods -- bit for bit the row of smmc_engine_simulate_keepdata for the same
+ * smmc_sim -- every operation binary32 and rounded on its own (nothing fuses), every comparison false for NaN:
+ *   at t = 0: peak = low = dd_peak = dd_low = v_0; dd_period = run = longest = first_below = first_reach = 0
+ *   for t = 1 .. n_periods, v = v_t:
+ *     if (v > peak) peak = v
+ *     if (v < low)  low  = v
+ *     if (fl(v * dd_peak) < fl(dd_low * peak))    a deeper relative drawdown than the deepest so far (strict); uses
+ *         dd_peak = peak, dd_low = v, dd_period = t      the peak already updated above
+ *     run = (v < peak) ? run + 1 : 0;  longest = max(longest, run)
+ *     if (first_below == 0 && v <  lower)  first_below = t     the reference's `val < min_final_amount`
+ *     if (first_reach == 0 && v >= target) first_reach = t
+ *   at the end: drawdown = fl(fl(dd_peak - dd_low) / dd_peak)  one IEEE divide per path
+ * v / peak > dd_low / dd_peak is decided by cross-multiplication, which keeps the divide out of the period loop and
+ * is part of the contract: the two products round, and overflow to inf, as binary32 products do.  For values that
+ * stay finite and positive, drawdown is max over t of 1 - v_t / (running maximum) to a few binary32 roundings. */
+typedef struct smmc_excursions {
+  uint32_t struct_size;     /* = sizeof(smmc_excursions) */
+  float lower;              /* MINIMUM level: first_below = first t with v_t <  lower  */
+  float target;             /* TARGET level:  first_reach = first t with v_t >= target */
+  float drawdown_threshold; /* `below` of the drawdown record counts paths with drawdown < this */
+} smmc_excursions;
+
+/* All pointers DEVICE (HOST in the _to_host form), any may be NULL; written, not accumulated into.  The per-path
+ * arrays are 4-byte aligned, the records and the count arrays 8-byte aligned. */
+typedef struct smmc_excursion_outputs {
+  uint32_t struct_size; /* = sizeof(smmc_excursion_outputs) */
+  float *final, *peak, *low, *drawdown;                               /* n_paths each */
+  uint32_t *drawdown_period, *underwater, *first_below, *first_reach; /* n_paths each; underwater = `longest` */
+  void *stats;          /* record of the final values: exactly smmc_engine_simulate's d_stats */
+  void *drawdown_stats; /* record of `drawdown`: n_bins buckets over [0, 1), below = drawdown < drawdown_threshold,
+                           underflow < 0, overflow >= 1 or NaN; smmc_stats_bytes(sim->n_bins) bytes */
+  uint64_t *first_below_at, *first_reach_at; /* n_periods + 1 counts each: [0] never, [t] first at period t; the
+                                                sum of each is n_paths */
+} smmc_excursion_outputs;
+
+/* Enqueues one simulation on the engine stream and returns without waiting.  A path's outputs depend only on
+ * (seed, global path id, parameters), never on first_path, the shard or the launch geometry.  Integer fields, min,
+ * max, bucket counts and the two count arrays are exact; sum and sumsq are double sums in a fixed order (no
+ * floating-point atomics): two identical calls give the same bytes.  Shards of one request merge by
+ * smmc_stats_merge and by adding the count arrays.
+ * Divide by 100: a value has to be right when it is looked at, so the launch follows the keepdata rule,
+ * smmc_engine_divide_kind(e, sim, 1): the fast form when proven, the IEEE divide otherwise or with
+ * SMMC_FLAG_EXACT_DIV; never SMMC_DIV_CHECKED.  The result does not depend on it.
+ * SMMC_ERR_INVALID with a text: NULL x or out, or a wrong struct_size; n_periods == 0 or >
+ * SMMC_MAX_EXCURSION_PERIODS; a NaN lower, target or drawdown_threshold (+-inf is allowed: "never" / "always");
+ * SMMC_FLAG_STREAM_REF or SMMC_FLAG_STREAM_V2 (counter stream v3 only); the table-mode and bin-count errors of
+ * smmc_engine_simulate; table, counters and histograms beyond the device's LDS; 2^32 paths or more per workgroup
+ * (shard the request). */
+int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
+                                    const smmc_excursion_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
+                                            const smmc_excursion_outputs *out);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

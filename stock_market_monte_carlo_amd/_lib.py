@@ -30,6 +30,7 @@ MAX_RANKS = 8
 MAX_CHECKPOINTS = 64
 MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
 MAX_CASHFLOW_PERIODS = 4096  # largest n_periods of a simulate_cashflow call
+MAX_EXCURSION_PERIODS = 4096  # largest n_periods of a simulate_excursions call
 
 
 class Sim(C.Structure):
@@ -80,6 +81,26 @@ class Cashflow(C.Structure):
     ]
 
 
+class Excursions(C.Structure):
+    """smmc_excursions"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("lower", C.c_float),
+        ("target", C.c_float),
+        ("drawdown_threshold", C.c_float),
+    ]
+
+
+# the pointer fields of smmc_excursion_outputs, in the order of the structure
+EXCURSION_OUTPUTS = ("final", "peak", "low", "drawdown", "drawdown_period", "underwater", "first_below", "first_reach",
+                     "stats", "drawdown_stats", "first_below_at", "first_reach_at")
+
+
+class ExcursionOutputs(C.Structure):
+    """smmc_excursion_outputs"""
+    _fields_ = [("struct_size", C.c_uint32)] + [(name, C.c_void_p) for name in EXCURSION_OUTPUTS]
+
+
 # every symbol include/smmc.h declares: (name, restype, argtypes)
 DIV_FAST, DIV_EXACT, DIV_CHECKED = 0, 1, 2  # smmc_engine_divide_kind
 MERGE_HOST, MERGE_RCCL = 0, 1  # smmc_group_create
@@ -113,6 +134,10 @@ SYMBOLS = [
     ("smmc_engine_simulate_cashflow_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("smmc_engine_cashflow_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow)]),
+    ("smmc_engine_simulate_excursions", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Excursions), C.POINTER(ExcursionOutputs)]),
+    ("smmc_engine_simulate_excursions_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Excursions), C.POINTER(ExcursionOutputs)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

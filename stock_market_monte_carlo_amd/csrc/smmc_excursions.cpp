@@ -1,0 +1,235 @@
+// smmc_excursions.cpp -- smmc_engine_simulate_excursions and its _to_host form (include/smmc.h): drawdown, running
+// extremes, time under water and the first passage of two levels, reduced along every path.
+//
+// A translation unit of its own, as smmc_cashflow.cpp: smmc_capi.cpp owns struct smmc_engine and never calls into
+// this file; what is needed of an engine comes through smmc_internal.h.  It keeps no state per engine: the two
+// records use the halves of the engine's partial array, the four counter arrays the engine's zeroed accumulator.
+// The reference draws the MINIMUM and TARGET levels across its trajectory plot
+// (examples/visualize_returns_cpu_v2.cpp:397-411) and counts final values below the minimum (:125-138); what
+// happened along a path it can only read off the stored trajectories.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "smmc_internal.h"
+
+namespace {
+
+using smmc::DeviceGuard;
+using smmc::host_fail;
+
+#define SMMC_EX_HIP(call)                                                                                          \
+  do {                                                                                                             \
+    hipError_t err__ = (call);                                                                                     \
+    if (err__ != hipSuccess)                                                                                       \
+      return host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
+  } while (0)
+
+// Workgroups per CU, as cashflow_kernel: a workgroup flushes 2 (n_periods + 1) + 2 n_bins counters.
+constexpr uint32_t kExcursionGroupsPerCU = 32;
+// The engine's accumulator (kHistSpread x SMMC_MAX_BINS counters, zero between launches) as this launch divides it:
+// the histogram of the final values, the histogram of the drawdowns, the first_below and the first_reach counts.
+constexpr size_t kAccDrawdownHist = SMMC_MAX_BINS;
+constexpr size_t kAccBelowAt = 2u * SMMC_MAX_BINS;
+constexpr size_t kAccReachAt = kAccBelowAt + SMMC_MAX_EXCURSION_PERIODS + 1u;
+static_assert(kAccReachAt + SMMC_MAX_EXCURSION_PERIODS + 1u <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
+              "the engine's accumulator holds two histograms and two first-passage count arrays");
+
+int check_excursions(const smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x, const smmc_excursion_outputs *out) {
+  int rc = smmc::host_check_sim(e, sim);
+  if (rc) return rc;
+  if (!x) return host_fail(SMMC_ERR_INVALID, "the smmc_excursions argument is NULL");
+  if (x->struct_size != sizeof(smmc_excursions))
+    return host_fail(SMMC_ERR_INVALID, "smmc_excursions.struct_size is %u, this library expects %zu", x->struct_size,
+                     sizeof(smmc_excursions));
+  if (!out) return host_fail(SMMC_ERR_INVALID, "the smmc_excursion_outputs argument is NULL");
+  if (out->struct_size != sizeof(smmc_excursion_outputs))
+    return host_fail(SMMC_ERR_INVALID, "smmc_excursion_outputs.struct_size is %u, this library expects %zu", out->struct_size,
+                     sizeof(smmc_excursion_outputs));
+  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
+    return host_fail(SMMC_ERR_INVALID, "excursions support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
+                     (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  if (sim->n_periods == 0) return host_fail(SMMC_ERR_INVALID, "n_periods is 0: an excursion needs at least one period");
+  if (sim->n_periods > SMMC_MAX_EXCURSION_PERIODS)
+    return host_fail(SMMC_ERR_INVALID, "n_periods %u exceeds SMMC_MAX_EXCURSION_PERIODS %d", sim->n_periods,
+                     SMMC_MAX_EXCURSION_PERIODS);
+  if (std::isnan(x->lower)) return host_fail(SMMC_ERR_INVALID, "lower is NaN (-inf means never below)");
+  if (std::isnan(x->target)) return host_fail(SMMC_ERR_INVALID, "target is NaN (+inf means never reached)");
+  if (std::isnan(x->drawdown_threshold)) return host_fail(SMMC_ERR_INVALID, "drawdown_threshold is NaN");
+  return SMMC_OK;
+}
+
+int check_alignment(const smmc_excursion_outputs *o) {
+  const uintptr_t words = reinterpret_cast<uintptr_t>(o->final) | reinterpret_cast<uintptr_t>(o->peak) |
+                          reinterpret_cast<uintptr_t>(o->low) | reinterpret_cast<uintptr_t>(o->drawdown) |
+                          reinterpret_cast<uintptr_t>(o->drawdown_period) | reinterpret_cast<uintptr_t>(o->underwater) |
+                          reinterpret_cast<uintptr_t>(o->first_below) | reinterpret_cast<uintptr_t>(o->first_reach);
+  if (words & 3u) return host_fail(SMMC_ERR_INVALID, "the per-path output pointers must be 4-byte aligned");
+  const uintptr_t wide = reinterpret_cast<uintptr_t>(o->stats) | reinterpret_cast<uintptr_t>(o->drawdown_stats) |
+                         reinterpret_cast<uintptr_t>(o->first_below_at) | reinterpret_cast<uintptr_t>(o->first_reach_at);
+  if (wide & 7u) return host_fail(SMMC_ERR_INVALID, "the record and count-array pointers must be 8-byte aligned");
+  return SMMC_OK;
+}
+
+// The launch shape of a request, and the refusals that follow from it; both entries ask before any device work.
+struct Geometry {
+  uint32_t grid, half;  // workgroups; where the second record's partials start in the engine's partial array
+  uint32_t n_bins;      // of the launch: 0 when no record is asked for
+};
+int plan(const smmc_engine *e, const smmc::EngineView &view, const smmc_sim *sim, const smmc_excursion_outputs *out, Geometry *g) {
+  const uint32_t group_paths = smmc::excursions_group_paths(sim->mode);
+  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
+  // two records leave two partials per workgroup: the halves of the engine's partial array
+  g->half = view.max_grid / 2u;
+  g->grid = static_cast<uint32_t>(std::min<uint64_t>(n_chunks, std::min(view.compute_units * kExcursionGroupsPerCU, g->half)));
+  if (sim->n_paths && !g->grid) return host_fail(SMMC_ERR_INVALID, "the engine's launch grid is too small for two records");
+  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS counters)
+  if (g->grid && (n_chunks + g->grid - 1) / g->grid * group_paths >= (1ull << 32))
+    return host_fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
+                     static_cast<unsigned long long>(sim->n_paths));
+  g->n_bins = (out->stats || out->drawdown_stats) ? sim->n_bins : 0u;
+  const smmc::KernelArgs a = smmc::host_make_args(e, sim);
+  const size_t lds = smmc::excursions_lds_bytes(a.mode, a.table_len, a.n_periods, g->n_bins);
+  if (lds + 2048 > view.max_lds)
+    return host_fail(SMMC_ERR_INVALID, "table, first-passage counters and histograms need %zu bytes of LDS, device allows %zu", lds,
+                     view.max_lds);
+  return SMMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
+                                    const smmc_excursion_outputs *out) {
+  int rc = check_excursions(e, sim, x, out);
+  if (rc) return rc;
+  rc = check_alignment(out);
+  if (rc) return rc;
+  const smmc::EngineView view = smmc::engine_view(e);
+  Geometry g;
+  rc = plan(e, view, sim, out, &g);
+  if (rc) return rc;
+  const uint32_t grid = g.grid, half = g.half;
+  smmc::KernelArgs a = smmc::host_make_args(e, sim);
+  a.n_bins = g.n_bins;
+  // a value has to be right when it is looked at: the keepdata rule (never SMMC_DIV_CHECKED)
+  const int div = smmc_engine_divide_kind(e, sim, 1);
+  if (div < 0) return div;
+  DeviceGuard guard(view.device);
+  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+
+  smmc::ExcursionArgs xa;
+  std::memset(&xa, 0, sizeof xa);
+  xa.lower = x->lower;
+  xa.target = x->target;
+  xa.drawdown_threshold = x->drawdown_threshold;
+  xa.dd_hist_inv = static_cast<double>(a.n_bins);  // n_bins / (1 - 0)
+  xa.d_peak = out->peak;
+  xa.d_low = out->low;
+  xa.d_drawdown = out->drawdown;
+  xa.d_drawdown_period = out->drawdown_period;
+  xa.d_underwater = out->underwater;
+  xa.d_first_below = out->first_below;
+  xa.d_first_reach = out->first_reach;
+  a.d_final = out->final;
+  unsigned long long *acc = nullptr;
+  const bool use_acc = ((out->stats || out->drawdown_stats) && sim->n_bins) || out->first_below_at || out->first_reach_at;
+  if (use_acc) {  // zero now, and zero again after the finalize launches below
+    rc = smmc::engine_acc_begin(e, &acc);
+    if (rc) return rc;
+  }
+  if (out->stats) {
+    a.partials = view.d_partials;
+    a.d_hist = sim->n_bins ? acc : nullptr;
+  }
+  if (out->drawdown_stats) {
+    xa.dd_partials = view.d_partials + half;
+    xa.d_dd_hist = sim->n_bins ? acc + kAccDrawdownHist : nullptr;
+  }
+  if (out->first_below_at) xa.d_below_at = acc + kAccBelowAt;
+  if (out->first_reach_at) xa.d_reach_at = acc + kAccReachAt;
+  if (grid) {
+    rc = smmc::engine_timing_begin(e);
+    if (rc) return rc;
+    const hipError_t err = smmc::launch_excursions(a, xa, div != SMMC_DIV_FAST, grid, view.stream);
+    if (err != hipSuccess) {
+      (void)smmc::engine_timing_end(e);
+      return host_fail(SMMC_ERR_HIP, "launch_excursions failed: %s", hipGetErrorString(err));
+    }
+    rc = smmc::engine_timing_end(e);
+    if (rc) return rc;
+  }
+  const uint32_t spread = sim->n_bins ? 1u : 0u;
+  if (out->stats)
+    SMMC_EX_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(out->stats), sim->n_bins, view.stream,
+                                      sim->n_bins ? acc : nullptr, spread));
+  if (out->drawdown_stats)
+    SMMC_EX_HIP(smmc::launch_finalize(view.d_partials + half, grid, static_cast<smmc_stats *>(out->drawdown_stats), sim->n_bins,
+                                      view.stream, sim->n_bins ? acc + kAccDrawdownHist : nullptr, spread));
+  if (out->first_below_at)
+    SMMC_EX_HIP(smmc::launch_finalize_depleted(acc + kAccBelowAt, sim->n_periods + 1u,
+                                               reinterpret_cast<unsigned long long *>(out->first_below_at), view.stream));
+  if (out->first_reach_at)
+    SMMC_EX_HIP(smmc::launch_finalize_depleted(acc + kAccReachAt, sim->n_periods + 1u,
+                                               reinterpret_cast<unsigned long long *>(out->first_reach_at), view.stream));
+  if (use_acc) smmc::engine_acc_clean(e);
+  return SMMC_OK;
+}
+
+int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
+                                            const smmc_excursion_outputs *out) {
+  int rc = check_excursions(e, sim, x, out);
+  if (rc) return rc;
+  const smmc::EngineView view = smmc::engine_view(e);
+  Geometry g;
+  rc = plan(e, view, sim, out, &g);
+  if (rc) return rc;
+  DeviceGuard guard(view.device);
+  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  // one device allocation for all outputs, the 8-byte aligned ones first
+  const size_t stats_bytes = static_cast<size_t>(smmc_stats_bytes(sim->n_bins));
+  const size_t at_bytes = sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u);
+  const size_t per_path = sizeof(float) * sim->n_paths;
+  struct Piece { void *host; size_t bytes; size_t offset; };
+  Piece pieces[12] = {{out->stats, stats_bytes, 0},       {out->drawdown_stats, stats_bytes, 0}, {out->first_below_at, at_bytes, 0},
+                      {out->first_reach_at, at_bytes, 0}, {out->final, per_path, 0},             {out->peak, per_path, 0},
+                      {out->low, per_path, 0},            {out->drawdown, per_path, 0},          {out->drawdown_period, per_path, 0},
+                      {out->underwater, per_path, 0},     {out->first_below, per_path, 0},       {out->first_reach, per_path, 0}};
+  size_t total = 0;
+  for (Piece &p : pieces) {
+    if (!p.host) p.bytes = 0;
+    p.offset = total;
+    total += p.bytes;
+  }
+  char *d = nullptr;
+  if (total) SMMC_EX_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
+  auto dev = [&](int i) -> void * { return pieces[i].bytes ? d + pieces[i].offset : nullptr; };
+  smmc_excursion_outputs o;
+  std::memset(&o, 0, sizeof o);
+  o.struct_size = sizeof o;
+  o.stats = dev(0);
+  o.drawdown_stats = dev(1);
+  o.first_below_at = static_cast<uint64_t *>(dev(2));
+  o.first_reach_at = static_cast<uint64_t *>(dev(3));
+  o.final = static_cast<float *>(dev(4));
+  o.peak = static_cast<float *>(dev(5));
+  o.low = static_cast<float *>(dev(6));
+  o.drawdown = static_cast<float *>(dev(7));
+  o.drawdown_period = static_cast<uint32_t *>(dev(8));
+  o.underwater = static_cast<uint32_t *>(dev(9));
+  o.first_below = static_cast<uint32_t *>(dev(10));
+  o.first_reach = static_cast<uint32_t *>(dev(11));
+  rc = smmc_engine_simulate_excursions(e, sim, x, &o);
+  hipError_t err = hipStreamSynchronize(view.stream);  // also after a failure: nothing of the call may outlive its buffer
+  for (const Piece &p : pieces)
+    if (rc == SMMC_OK && err == hipSuccess && p.bytes) err = hipMemcpy(p.host, d + p.offset, p.bytes, hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (rc) return rc;
+  if (err != hipSuccess) return host_fail(SMMC_ERR_HIP, "simulate_excursions_to_host: %s", hipGetErrorString(err));
+  return SMMC_OK;
+}
+
+}  // extern "C"

@@ -166,6 +166,24 @@ hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exac
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream);
 uint32_t cashflow_group_paths(int32_t mode);
 size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
+// excursions_kernel (smmc_engine_simulate_excursions, csrc/smmc_excursions.cpp; counter stream v3 only): the paths of
+// paths_kernel with the running extremes, the deepest relative drawdown, the longest time under water and the first
+// passage of two levels kept per lane ("Excursions").
+struct ExcursionArgs {
+  float lower, target;       // first_below: first t with v < lower; first_reach: first t with v >= target
+  float drawdown_threshold;  // `below` of the drawdown record
+  double dd_hist_inv;        // (double)n_bins: the drawdown histogram spans [0, 1)
+  float *d_peak, *d_low, *d_drawdown;  // nullable, n_paths each (the final values go to KernelArgs::d_final)
+  uint32_t *d_drawdown_period, *d_underwater, *d_first_below, *d_first_reach;  // nullable, n_paths each
+  BlockPartial *dd_partials;        // nullable => no drawdown record; `grid` entries
+  unsigned long long *d_dd_hist;    // nullable; a.n_bins counters, zero before the launch
+  unsigned long long *d_below_at, *d_reach_at;  // nullable; n_periods + 1 counters each, zero before the launch
+};
+// a.partials / a.d_hist: the record of the final values, as launch_cashflow.  a.n_bins applies to both histograms.
+hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
+// (the count arrays are copied out, and the accumulator left zero, by launch_finalize_depleted)
+uint32_t excursions_group_paths(int32_t mode);
+size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0

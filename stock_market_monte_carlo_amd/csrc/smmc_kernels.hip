@@ -1695,6 +1695,204 @@ __global__ __launch_bounds__(kBlock) void finalize_depleted_kernel(unsigned long
   }
 }
 
+// ---- excursions: what happened along a path -------------------------------------------------------
+//
+// smmc_engine_simulate_excursions ("Excursions"): the draws and the compounding of paths_kernel, and
+// after each period's value v = v_t, every operation a binary32 rounding of its own (__fmul_rn: nothing may fuse),
+// every comparison false for NaN (selects on ordered compares, never v_max / v_min: those return the other operand
+// for a NaN and do not keep the sign of a zero):
+//   if (v > peak) peak = v;  if (v < low) low = v
+//   if (fl(v * dd_peak) < fl(dd_low * peak)) dd_peak = peak, dd_low = v, dd_period = t      the peak updated above
+//   run = (v < peak) ? run + 1 : 0;  longest = max(longest, run)
+//   if (first_below == 0 && v < lower) first_below = t;  if (first_reach == 0 && v >= target) first_reach = t
+// and once per path drawdown = fl(fl(dd_peak - dd_low) / dd_peak), an IEEE divide outside the loop.
+// Bound like paths_kernel: VALU issue.  By source 18 VALU instructions per period on top of the compounding chain:
+// two compares and two selects for the extremes, the two cross products, their compare and three selects, a compare,
+// an add, a select and an integer max for the time under water, a compare and a select per level.  The two "not yet
+// hit" flags are lane masks in scalar register pairs, combined with the compares on the scalar unit, as
+// cashflow_step's `alive`; the period index is wave-uniform; control flow stays wave-uniform.
+//
+// Work split, tables, draws and the partial last block: cashflow_kernel's.  Outputs: up to eight coalesced 256-byte
+// stores per wave chunk; TWO records (final value, drawdown), each reduced over the wave per chunk as
+// checkpoint_record does and added to the wave's partial in LDS (wave_record_add), left as one partial per workgroup
+// (k.partials, x.dd_partials; finalize_kernel folds each); one LDS add per lane into each of two histograms and of two [n_periods + 1] first-passage counter arrays behind the
+// draw tables, flushed with 64-bit integer atomics.  u32 counters count paths of ONE workgroup: the host refuses a
+// launch in which a workgroup would get 2^32 or more (smmc_excursions.cpp).
+struct ExcursionLane {
+  float peak, low, dd_peak, dd_low;
+  uint32_t dd_period, run, longest, first_below, first_reach;
+};
+
+template <bool kExactDiv>
+__device__ __forceinline__ void excursion_step(float a, float lower, float target, uint32_t t, float &v, ExcursionLane &s,
+                                               bool &no_below, bool &no_reach) {
+  v = compound<kExactDiv>(v, a);
+  s.peak = v > s.peak ? v : s.peak;
+  s.low = v < s.low ? v : s.low;
+  const bool deeper = __fmul_rn(v, s.dd_peak) < __fmul_rn(s.dd_low, s.peak);  // strict; false for NaN
+  s.dd_peak = deeper ? s.peak : s.dd_peak;
+  s.dd_low = deeper ? v : s.dd_low;
+  s.dd_period = deeper ? t : s.dd_period;
+  s.run = v < s.peak ? s.run + 1u : 0u;
+  s.longest = s.longest > s.run ? s.longest : s.run;
+  const bool hit_below = no_below && v < lower;
+  const bool hit_reach = no_reach && v >= target;
+  s.first_below = hit_below ? t : s.first_below;
+  s.first_reach = hit_reach ? t : s.first_reach;
+  no_below = no_below && !hit_below;
+  no_reach = no_reach && !hit_reach;
+}
+
+// The wave's values v (lanes with !active: none) are added to the wave's own partial record in LDS: the sums,
+// extremes and counts of checkpoint_record, by the same lane movements, then one read-modify-write by lane 0.  Two
+// records' accumulators in registers (20 per lane) would cost the Gaussian kernel its eighth wave per SIMD; here they
+// cost none, and some 70 VALU instructions per wave chunk and record.  The order is fixed: a wave's chunks ascending.
+// Every lane of the wave must be enabled.
+__device__ __forceinline__ void wave_record_add(BlockPartial *part, float v, bool active, uint32_t lane, float below_threshold,
+                                                float lo, float hi, double inv, uint32_t n_bins, uint32_t *lds_hist) {
+  const double dv = static_cast<double>(v);
+  const double s12 = wave_sum_pair(active ? dv : 0.0, active ? dv * dv : 0.0);  // lane 0: sum, lane 32: sum of squares
+  const bool ordered = active && v == v;  // min and max skip NaN, as fminf / fmaxf do
+  const float mm = wave_min_pair(ordered ? v : __builtin_inff(), ordered ? -v : __builtin_inff());  // lane 0: min, lane 32: -max
+  const uint32_t n_count = ballot_count(active);
+  const uint32_t n_below = ballot_count(active && v < below_threshold);
+  uint32_t n_under = 0, n_over = 0;
+  if (n_bins) {  // uniform
+    const bool under = active && v < lo;
+    const bool inside = active && !under && v < hi;
+    n_under = ballot_count(under);
+    n_over = ballot_count(active && !under && !inside);  // >= hi, or NaN
+    if (inside) {
+      int32_t b = static_cast<int32_t>((dv - static_cast<double>(lo)) * inv);
+      b = b < static_cast<int32_t>(n_bins) - 1 ? b : static_cast<int32_t>(n_bins) - 1;
+      atomicAdd(&lds_hist[b], 1u);
+    }
+  }
+  const double w_sum = read_lane(s12, 0), w_sumsq = read_lane(s12, 32);
+  const float w_min = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 0));
+  const float w_max = -__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 32));
+  if (lane == 0) {
+    BlockPartial t = *part;
+    t.sum += w_sum;
+    t.sumsq += w_sumsq;
+    t.count += n_count;
+    t.below += n_below;
+    t.underflow += n_under;
+    t.overflow += n_over;
+    t.min = fminf(t.min, w_min);
+    t.max = fmaxf(t.max, w_max);
+    *part = t;
+  }
+}
+
+template <int kMode, bool kExactDiv, bool kDense>
+__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+void excursions_kernel(const KernelArgs k, const ExcursionArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *lds_table = reinterpret_cast<float *>(lds_raw);
+  const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
+  const uint32_t n_at = k.n_periods + 1u;
+  uint32_t *lds_below_at = reinterpret_cast<uint32_t *>(lds_raw) + table_words;  // [n_periods + 1]
+  uint32_t *lds_reach_at = lds_below_at + n_at;                                  // [n_periods + 1]
+  uint32_t *lds_hist = lds_reach_at + n_at;                                      // [n_bins], the final values
+  uint32_t *lds_dd_hist = lds_hist + k.n_bins;                                   // [n_bins], the drawdowns
+  const uint32_t counter_words = 2u * n_at + 2u * k.n_bins;
+  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(reinterpret_cast<uint32_t *>(lds_raw) +
+                                                             ((table_words + counter_words + 1u) & ~1u));  // [2][kW]
+
+  stage_tables<kMode>(k, lds_table, kGroup);
+  for (uint32_t i = threadIdx.x; i < counter_words; i += kGroup) lds_below_at[i] = 0u;
+  __syncthreads();
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_dd_stats = x.dd_partials != nullptr;
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dd_hist = want_dd_stats && k.n_bins != 0;
+  const bool want_below_at = x.d_below_at != nullptr, want_reach_at = x.d_reach_at != nullptr;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  BlockPartial *part = wave_part + wave, *dd_part = wave_part + kW + wave;  // this wave's own, until the barrier
+  if (lane == 0) {
+    partial_identity(*part);
+    partial_identity(*dd_part);
+  }
+  const DrawRegs dr = make_draw_regs(k);
+
+  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
+  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
+  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
+       wc += static_cast<uint64_t>(gridDim.x) * kW) {
+    const uint64_t i = wc * 64u + lane;
+    const bool active = i < k.n_paths;
+    const uint64_t path = k.first_path + i;
+    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+    float v = k.initial_capital;
+    ExcursionLane s = {v, v, v, v, 0u, 0u, 0u, 0u, 0u};
+    bool no_below = true, no_reach = true;
+    for (uint32_t blk = 0; blk < full; ++blk) {
+      float a[kDraws];
+      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j)
+        excursion_step<kExactDiv>(a[j], x.lower, x.target, blk * kDraws + j + 1u, v, s, no_below, no_reach);
+    }
+    if (rem) {  // wave-uniform: the path's last, partial block
+      float a[kDraws];
+      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
+#pragma unroll
+      for (int j = 0; j < kDraws - 1; ++j)
+        if (static_cast<uint32_t>(j) < rem)
+          excursion_step<kExactDiv>(a[j], x.lower, x.target, full * kDraws + j + 1u, v, s, no_below, no_reach);
+    }
+    const float drawdown = __fdiv_rn(__fsub_rn(s.dd_peak, s.dd_low), s.dd_peak);  // the path's one IEEE divide
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (x.d_peak) x.d_peak[i] = s.peak;
+      if (x.d_low) x.d_low[i] = s.low;
+      if (x.d_drawdown) x.d_drawdown[i] = drawdown;
+      if (x.d_drawdown_period) x.d_drawdown_period[i] = s.dd_period;
+      if (x.d_underwater) x.d_underwater[i] = s.longest;
+      if (x.d_first_below) x.d_first_below[i] = s.first_below;
+      if (x.d_first_reach) x.d_first_reach[i] = s.first_reach;
+      if (want_below_at) atomicAdd(&lds_below_at[s.first_below], 1u);  // first_* <= n_periods
+      if (want_reach_at) atomicAdd(&lds_reach_at[s.first_reach], 1u);
+    }
+    if (want_stats)  // uniform: the whole wave
+      wave_record_add(part, v, active, lane, k.below_threshold, k.hist_lo, k.hist_hi, k.hist_inv, want_hist ? k.n_bins : 0u, lds_hist);
+    if (want_dd_stats)
+      wave_record_add(dd_part, drawdown, active, lane, x.drawdown_threshold, 0.0f, 1.0f, x.dd_hist_inv, want_dd_hist ? k.n_bins : 0u,
+                      lds_dd_hist);
+  }
+
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (threadIdx.x == 0) {
+    if (want_stats) {
+      BlockPartial t = wave_part[0];
+      for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[w]);
+      k.partials[blockIdx.x] = t;
+    }
+    if (want_dd_stats) {
+      BlockPartial t = wave_part[kW];
+      for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[kW + w]);
+      x.dd_partials[blockIdx.x] = t;
+    }
+  }
+  for (uint32_t b = threadIdx.x; b < n_at; b += kGroup) {
+    const uint32_t nb = lds_below_at[b], nr = lds_reach_at[b];
+    if (want_below_at && nb) atomicAdd(&x.d_below_at[b], static_cast<unsigned long long>(nb));
+    if (want_reach_at && nr) atomicAdd(&x.d_reach_at[b], static_cast<unsigned long long>(nr));
+  }
+  for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
+    const uint32_t nf = lds_hist[b], nd = lds_dd_hist[b];
+    if (want_hist && nf) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(nf));
+    if (want_dd_hist && nd) atomicAdd(&x.d_dd_hist[b], static_cast<unsigned long long>(nd));
+  }
+}
+
 }  // namespace
 
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
@@ -1745,6 +1943,8 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, false>),
       reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, true>),
       reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, true>),
+      reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, false, false>),
+      reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, true, false>),
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -1998,6 +2198,41 @@ hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exac
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream) {
   hipLaunchKernelGGL(finalize_depleted_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, acc, n, d_out);
   return hipGetLastError();
+}
+
+// ---- excursions ----
+
+uint32_t excursions_group_paths(int32_t mode) { return checkpoints_group_paths(mode); }
+
+size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
+  // [draw tables][first_below counters n_periods + 1][first_reach counters n_periods + 1][histogram of the final
+  // values][histogram of the drawdowns][pad to 8 bytes][two BlockPartial per wave]
+  const bool table = mode == SMMC_MODE_TABLE;
+  const size_t words = (static_cast<size_t>(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN)) + 2u * (static_cast<size_t>(n_periods) + 1u) +
+                        2u * static_cast<size_t>(n_bins) + 1u) & ~static_cast<size_t>(1);
+  return words * 4u + 2u * checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN) * sizeof(BlockPartial);
+}
+
+template <int kMode, bool kDense>
+static hipError_t launch_excursions_mode(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, size_t lds,
+                                         hipStream_t stream) {
+  const dim3 block(64u * checkpoint_waves(kMode));
+  hipError_t err = exact_div ? allow_lds(excursions_kernel<kMode, true, kDense>, lds)
+                             : allow_lds(excursions_kernel<kMode, false, kDense>, lds);
+  if (err != hipSuccess) return err;
+  if (exact_div)
+    hipLaunchKernelGGL((excursions_kernel<kMode, true, kDense>), dim3(grid), block, lds, stream, a, x);
+  else
+    hipLaunchKernelGGL((excursions_kernel<kMode, false, kDense>), dim3(grid), block, lds, stream, a, x);
+  return hipGetLastError();
+}
+
+hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_EXCURSION_PERIODS) return hipErrorInvalidValue;
+  const size_t lds = excursions_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
+  if (a.mode != SMMC_MODE_TABLE) return launch_excursions_mode<SMMC_MODE_GAUSSIAN, false>(a, x, exact_div, grid, lds, stream);
+  return table_is_dense(a.table_len) ? launch_excursions_mode<SMMC_MODE_TABLE, true>(a, x, exact_div, grid, lds, stream)
+                                     : launch_excursions_mode<SMMC_MODE_TABLE, false>(a, x, exact_div, grid, lds, stream);
 }
 
 }  // namespace smmc

@@ -141,6 +141,47 @@ class CashflowResult:
         return 1.0 - gone / n
 
 
+def _by_period(counts, what):
+    """Cumulative share of paths whose first passage lies at or before each period, from a [n_periods + 1] count
+    array ([0]: never, [t]: first at period t)."""
+    if counts is None:
+        raise ValueError(f"{what}() needs its count array (want_first_{'below' if what == 'ever_below' else 'reach'}_at=True)")
+    d = np.asarray(counts, dtype=np.float64)
+    n = d.sum()
+    if n == 0:
+        return np.full(d.size, np.nan)
+    hit = np.cumsum(d)
+    hit -= d[0]  # [0] counts the paths that never got there
+    return hit / n
+
+
+@dataclasses.dataclass
+class ExcursionResult:
+    """What Engine.simulate_excursions returns: the outputs that were asked for, None for the others."""
+    n_paths: int
+    n_periods: int
+    final: object = None            # torch.float32 [n_paths] on the engine's device
+    peak: object = None             # torch.float32 [n_paths]: the largest value of the path, v_0 included
+    low: object = None              # torch.float32 [n_paths]: the smallest
+    drawdown: object = None         # torch.float32 [n_paths]: the deepest relative drawdown, (peak - trough) / peak
+    drawdown_period: object = None  # torch.int32 [n_paths] holding uint32 values: period of that trough, 0 = none
+    underwater: object = None       # torch.int32 [n_paths]: the longest run of periods below the running peak
+    first_below: object = None      # torch.int32 [n_paths]: first period with value < lower, 0 = never
+    first_reach: object = None      # torch.int32 [n_paths]: first period with value >= target, 0 = never
+    stats: Stats = None             # record of the final values
+    drawdown_stats: Stats = None    # record of the drawdowns: buckets over [0, 1), below = drawdown < drawdown_threshold
+    first_below_at: np.ndarray = None  # uint64 [n_periods + 1]: [0] never below, [t] first below at period t
+    first_reach_at: np.ndarray = None  # uint64 [n_periods + 1]: the same for the target
+
+    def ever_below(self):
+        """Share of paths that have been below `lower` by each period: [0] = 0, non-decreasing, n_periods + 1 entries."""
+        return _by_period(self.first_below_at, "ever_below")
+
+    def reached_by(self):
+        """Share of paths that have reached `target` by each period; n_periods + 1 entries."""
+        return _by_period(self.first_reach_at, "reached_by")
+
+
 class Engine:
     """One engine per (process, device): table, workspace and stream stay resident."""
 
@@ -433,6 +474,96 @@ class Engine:
         if rc < 0:
             _lib.check(rc)
         return rc
+
+    # -- excursions: drawdown, running extremes, first passage of levels (smmc_engine_simulate_excursions) --------
+    _EXCURSION_WANTS = dict(final=True, peak=False, low=False, drawdown=False, drawdown_period=False, underwater=False,
+                            first_below=False, first_reach=False, stats=False, drawdown_stats=True, first_below_at=True,
+                            first_reach_at=True)
+
+    @staticmethod
+    def make_excursions(lower, target, drawdown_threshold=0.2):
+        x = _lib.Excursions()
+        x.struct_size = C.sizeof(_lib.Excursions)
+        x.lower, x.target, x.drawdown_threshold = float(lower), float(target), float(drawdown_threshold)
+        return x
+
+    def _excursion_wants(self, wants):
+        full = dict(self._EXCURSION_WANTS)
+        for key, val in wants.items():
+            if not key.startswith("want_") or key[5:] not in full:
+                raise TypeError(f"unknown argument {key!r}")
+            full[key[5:]] = bool(val)
+        return full
+
+    def simulate_excursions(self, sim, lower, target, drawdown_threshold=0.2, **wants):
+        """One simulation reduced ALONG every path: running peak and low, the deepest relative drawdown and its
+        period, the longest run of periods under water, the first period below `lower` and the first at or above
+        `target`.  want_<name>=True / False selects the outputs (names: the fields of ExcursionResult; by default
+        final, drawdown_stats and the two count arrays).  Per-path outputs stay on the device; the records and count
+        arrays are read back (that waits).  include/smmc.h states the arithmetic."""
+        full = self._excursion_wants(wants)
+        raw = self.simulate_excursions_raw(sim, lower, target, drawdown_threshold, **wants)
+        res = ExcursionResult(int(sim.n_paths), int(sim.n_periods),
+                              **{k: raw[k] for k in _lib.EXCURSION_OUTPUTS[:8]})
+        if any(full[k] for k in _lib.EXCURSION_OUTPUTS[8:]):
+            self.sync()
+        if full["stats"]:
+            res.stats = stats_from_bytes(raw["stats"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if full["drawdown_stats"]:
+            res.drawdown_stats = stats_from_bytes(raw["drawdown_stats"].cpu().numpy().tobytes())
+            res.drawdown_stats.hist_lo, res.drawdown_stats.hist_hi = 0.0, 1.0
+        for k in ("first_below_at", "first_reach_at"):
+            if full[k]:
+                setattr(res, k, raw[k].cpu().numpy().view(np.uint64).copy())
+        return res
+
+    def simulate_excursions_raw(self, sim, lower, target, drawdown_threshold=0.2, **wants):
+        """Enqueues the call and returns its device tensors without waiting: a dict keyed by the fields of
+        smmc_excursion_outputs -- float32 / int32 (holding uint32 values) [n_paths], uint8 packed records, int64
+        (holding uint64 counts) [n_periods + 1]; None for what was not asked for."""
+        torch = self._torch
+        full = self._excursion_wants(wants)
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        rec = int(self._L.smmc_stats_bytes(sim.n_bins))
+        shape = {"final": (n, torch.float32), "peak": (n, torch.float32), "low": (n, torch.float32),
+                 "drawdown": (n, torch.float32), "drawdown_period": (n, torch.int32), "underwater": (n, torch.int32),
+                 "first_below": (n, torch.int32), "first_reach": (n, torch.int32), "stats": (rec, torch.uint8),
+                 "drawdown_stats": (rec, torch.uint8), "first_below_at": (p + 1, torch.int64),
+                 "first_reach_at": (p + 1, torch.int64)}
+        out = {k: (torch.empty(shape[k][0], dtype=shape[k][1], device=self.tdevice) if full[k] else None)
+               for k in _lib.EXCURSION_OUTPUTS}
+        x = self.make_excursions(lower, target, drawdown_threshold)
+        o = _lib.ExcursionOutputs()
+        o.struct_size = C.sizeof(_lib.ExcursionOutputs)
+        for k, t in out.items():
+            setattr(o, k, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_excursions(self._h, C.byref(sim), C.byref(x), C.byref(o)))
+        self._leave(cur, *out.values())
+        return out
+
+    def simulate_excursions_to_host(self, sim, lower, target, drawdown_threshold=0.2, **wants):
+        """The same through smmc_engine_simulate_excursions_to_host: a dict of numpy arrays (the records: bytes)."""
+        full = self._excursion_wants(wants)
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        rec = int(self._L.smmc_stats_bytes(sim.n_bins)) // 8
+        shape = {"final": (n, np.float32), "peak": (n, np.float32), "low": (n, np.float32), "drawdown": (n, np.float32),
+                 "drawdown_period": (n, np.uint32), "underwater": (n, np.uint32), "first_below": (n, np.uint32),
+                 "first_reach": (n, np.uint32), "stats": (rec, np.uint64), "drawdown_stats": (rec, np.uint64),
+                 "first_below_at": (p + 1, np.uint64), "first_reach_at": (p + 1, np.uint64)}
+        out = {k: (np.zeros(shape[k][0], dtype=shape[k][1]) if full[k] else None) for k in _lib.EXCURSION_OUTPUTS}
+        x = self.make_excursions(lower, target, drawdown_threshold)
+        o = _lib.ExcursionOutputs()
+        o.struct_size = C.sizeof(_lib.ExcursionOutputs)
+        for k, a in out.items():
+            setattr(o, k, a.ctypes.data if a is not None and a.size else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_excursions_to_host(self._h, C.byref(sim), C.byref(x), C.byref(o)))
+        for k in ("stats", "drawdown_stats"):
+            if out[k] is not None:
+                out[k] = out[k].tobytes()
+        return out
 
     def read_stats(self, stats_raw):
         """Copies a device record to the host after the engine stream has drained."""
