@@ -344,6 +344,52 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
 int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
                                             const smmc_excursion_outputs *out);
 
+/* ---- block bootstrap: table paths drawn in runs of consecutive months --------------------------- */
+
+/* SMMC_MODE_TABLE draws every period on its own, which keeps nothing of what lies between neighbouring months of
+ * the table (volatility clustering, momentum, the shape of a crash and its recovery).  The circular block bootstrap
+ * builds a path from runs of L = block_len consecutive table entries.  Counter stream v3, table mode only; with the
+ * table a[i] = 100.0f + r[i] (one binary32 addition at smmc_engine_set_table) of T entries:
+ *   block b = 0, 1, ... of path id starts at table index s_b, which is EXACTLY the index the SMMC_MODE_TABLE stream
+ *     draws for that path at period b: Philox4x32-10 block b / D with the key (seed lo, seed hi) and the counter
+ *     (b / D, id lo, id hi, 0) of table mode, digit b % D; D = 8 for T <= 2048 -- the four base-T digits of the
+ *     64-bit fraction (out[0] : out[1]), then the four of (out[2] : out[3]) -- and D = 4 above, digit j =
+ *     floor(out[j] * T / 2^32).  No new random-number construction: the starts of a path over P periods are the
+ *     table-mode indices of the same path over ceil(P / L) periods.
+ *   period t = 0 .. n_periods - 1 uses entry (s_{t div L} + t mod L) mod T: a block that runs past the end of the
+ *     table continues at its beginning.  L may exceed T or n_periods.
+ *   the step is smmc_update_fund's: total = fl(fl(total * a) / 100.0f), two binary32 roundings after the one in a.
+ * A path depends only on (seed, global path id, table, L); the launch shape and the sharding are invisible, and the
+ * value after p periods does not depend on n_periods (a run with n_periods = p yields column p of a longer run).
+ * With block_len = 1 every output is bit-identical to smmc_engine_simulate's in table mode. */
+#define SMMC_BLOCKS_CIRCULAR 0 /* the only kind for now; anything else is SMMC_ERR_INVALID */
+typedef struct smmc_blocks {
+  uint32_t struct_size; /* = sizeof(smmc_blocks) */
+  uint32_t block_len;   /* L >= 1 */
+  uint32_t kind;        /* SMMC_BLOCKS_CIRCULAR */
+  uint32_t reserved;    /* 0 */
+} smmc_blocks;
+
+/* smmc_engine_simulate with block draws: the same outputs with the same meaning (DEVICE pointers, any may be NULL),
+ * enqueued on the engine stream; n_periods == 0 and n_paths == 0 behave as there.
+ * SMMC_ERR_INVALID with a text: mode != SMMC_MODE_TABLE; no table set; SMMC_FLAG_STREAM_V2 or SMMC_FLAG_STREAM_REF;
+ * NULL blocks, a wrong struct_size, block_len == 0, kind != SMMC_BLOCKS_CIRCULAR, reserved != 0; table, its circular
+ * extension and the histogram beyond the device's LDS; the other argument errors of smmc_engine_simulate.
+ * Divide by 100: smmc_engine_blocks_divide_kind; the result does not depend on it. */
+int smmc_engine_simulate_blocks(smmc_engine *e, const smmc_sim *sim, const smmc_blocks *blocks, float *d_final,
+                                float *d_chunk_mean, float *d_chunk_var, void *d_stats);
+/* smmc_engine_simulate_to_host with block draws: HOST pointers, the same chunked pipeline, pinning rules
+ * (SMMC_PIN_HOST, SMMC_FLAG_HOST_NOPIN), progress reports and merged record. */
+int smmc_engine_simulate_blocks_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_blocks *blocks, float *host_final,
+                                        float *host_chunk_mean, float *host_chunk_var, volatile int64_t *progress,
+                                        smmc_stats *stats, uint64_t *hist);
+/* SMMC_DIV_FAST, SMMC_DIV_CHECKED or SMMC_DIV_EXACT: the divide a smmc_engine_simulate_blocks of (sim, blocks) uses,
+ * or an error of that call's argument checks.  The bounds on a product come from the table's smallest and largest
+ * entry, the capital and n_periods, never from the order of the draws, so the rule is smmc_engine_divide_kind(e, sim,
+ * 0)'s: the kernel tests the checked window at least once every 8 periods and redoes a path that ever leaves it with
+ * the IEEE divide. */
+int smmc_engine_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_blocks *blocks);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

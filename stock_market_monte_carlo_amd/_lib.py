@@ -91,6 +91,18 @@ class Excursions(C.Structure):
     ]
 
 
+class Blocks(C.Structure):
+    """smmc_blocks"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("block_len", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+BLOCKS_CIRCULAR = 0
+
 # the pointer fields of smmc_excursion_outputs, in the order of the structure
 EXCURSION_OUTPUTS = ("final", "peak", "low", "drawdown", "drawdown_period", "underwater", "first_below", "first_reach",
                      "stats", "drawdown_stats", "first_below_at", "first_reach_at")
@@ -138,6 +150,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Excursions), C.POINTER(ExcursionOutputs)]),
     ("smmc_engine_simulate_excursions_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Excursions), C.POINTER(ExcursionOutputs)]),
+    ("smmc_engine_simulate_blocks", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_blocks_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+      C.c_void_p]),
+    ("smmc_engine_blocks_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -1144,6 +1144,19 @@ int smmc_host_unregister(void *host_ptr) {
 int smmc_engine_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final,
                                  float *host_chunk_mean, float *host_chunk_var, volatile int64_t *progress,
                                  smmc_stats *stats, uint64_t *hist) {
+  return smmc::host_simulate_to_host(
+      e, sim, host_final, host_chunk_mean, host_chunk_var, progress, stats, hist,
+      [](smmc_engine *eng, const smmc_sim *part, float *d_final, float *d_cm, float *d_cv, void *d_rec, const void *) {
+        return enqueue_simulation(eng, part, d_final, d_cm, d_cv, d_rec);
+      },
+      nullptr);
+}
+
+}  // extern "C"
+
+int smmc::host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final, float *host_chunk_mean,
+                                float *host_chunk_var, volatile int64_t *progress, smmc_stats *stats, uint64_t *hist,
+                                HostEnqueue enqueue, const void *ctx) {
   int rc = check_sim(e, sim);
   if (rc) return rc;
   DeviceGuard guard(e->device);
@@ -1260,7 +1273,7 @@ int smmc_engine_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *hos
     void *d_rec = want_stats ? static_cast<char *>(e->d_stage_stats) + rec * c : nullptr;
     float *d_cm = want_cs ? e->d_stage_cs[b] : nullptr;
     float *d_cv = want_cs ? e->d_stage_cs[b] + cs_per_chunk : nullptr;
-    rc = enqueue_simulation(e, &part, host_final ? e->d_stage[b] : nullptr, d_cm, d_cv, d_rec);
+    rc = enqueue(e, &part, host_final ? e->d_stage[b] : nullptr, d_cm, d_cv, d_rec, ctx);
     if (rc) return rc;
     if (copies) {
       SMMC_HIP(hipEventRecord(e->ev_compute[b], e->stream));
@@ -1324,6 +1337,8 @@ int smmc_engine_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *hos
   report(n);
   return SMMC_OK;
 }
+
+extern "C" {
 
 int smmc_engine_simulate_keepdata_to_host(smmc_engine *e, const smmc_sim *sim, float *host_traj, float *host_final) {
   int rc = check_sim(e, sim);
@@ -1694,7 +1709,8 @@ bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_
 }
 KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s) { return make_args(e, s); }
 EngineView engine_view(const smmc_engine *e) {
-  return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials};
+  return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials,
+                    e->timing ? e->d_clock : nullptr};
 }
 EngineExt *engine_ext(smmc_engine *e) { return &e->ext; }
 int engine_acc_begin(smmc_engine *e, unsigned long long **acc) {
@@ -1707,5 +1723,8 @@ int engine_acc_begin(smmc_engine *e, unsigned long long **acc) {
 void engine_acc_clean(smmc_engine *e) { e->hist_dirty = false; }
 int engine_timing_begin(smmc_engine *e) { return timing_begin(e); }
 int engine_timing_end(smmc_engine *e) { return timing_end(e); }
+int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi) {
+  return divide_kind(e, s, allow_checked, chk_lo, chk_hi);
+}
 
 }  // namespace smmc

@@ -184,6 +184,12 @@ hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool e
 // (the count arrays are copied out, and the accumulator left zero, by launch_finalize_depleted)
 uint32_t excursions_group_paths(int32_t mode);
 size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
+// blocks_kernel (smmc_engine_simulate_blocks, csrc/smmc_blocks.cpp; counter stream v3, table mode): the outputs of
+// launch_paths for paths drawn in runs of block_len consecutive table entries ("Block bootstrap").
+// `wide`: four shifted copies of the table in LDS, read 16 bytes at a time; else one copy read 4 bytes at a time.
+// `grid` workgroups of kBlock threads, one partial each.
+hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int div, uint32_t grid, hipStream_t stream);
+size_t blocks_lds_bytes(uint32_t table_len, uint32_t n_bins, bool wide);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
@@ -212,6 +218,7 @@ struct EngineView {  // what a launch needs to know of an engine
   uint32_t compute_units, max_grid;
   size_t max_lds;
   BlockPartial *d_partials;  // max_grid entries
+  unsigned long long *clock_probe;  // KernelArgs::clock_probe of a launch now: null unless smmc_engine_timing is on
 };
 struct EngineExt {  // one slot of state owned by another translation unit: smmc_engine_destroy calls release(state)
   void *state;
@@ -230,5 +237,14 @@ int engine_acc_begin(smmc_engine *e, unsigned long long **acc);
 void engine_acc_clean(smmc_engine *e);
 int engine_timing_begin(smmc_engine *e);
 int engine_timing_end(smmc_engine *e);
+// smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
+int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
+// smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around
+// another enqueue: `enqueue` is called with the device current, once per chunk, with that chunk's smmc_sim and
+// device buffers (any may be null), and enqueues on the engine stream as smmc_engine_simulate does.
+typedef int (*HostEnqueue)(smmc_engine *e, const smmc_sim *part, float *d_final, float *d_chunk_mean, float *d_chunk_var,
+                           void *d_stats, const void *ctx);
+int host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final, float *host_chunk_mean, float *host_chunk_var,
+                          volatile int64_t *progress, smmc_stats *stats, uint64_t *hist, HostEnqueue enqueue, const void *ctx);
 
 }  // namespace smmc

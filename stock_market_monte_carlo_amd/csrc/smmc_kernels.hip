@@ -772,6 +772,334 @@ __global__ __launch_bounds__(kFinalizeBlock) void finalize_kernel(const BlockPar
   }
 }
 
+// ---- block bootstrap: table paths drawn in runs of consecutive months ------------------------------
+//
+// smmc_engine_simulate_blocks (csrc/smmc_blocks.cpp; DESIGN.md, "Block bootstrap").  Block b of a path starts at the
+// table index the i.i.d. table stream draws for that path at period b -- Philox block b / D, digit b % D, the key,
+// counter layout and mode tag of SMMC_MODE_TABLE -- and period t reads entry (s_{t div L} + t mod L) mod T.  All
+// lanes of a wave share t, L and the block boundaries: the control flow is wave-uniform, only addresses differ.
+//
+// The period loop walks a block in segments of kBlockSeg = 8 consecutive periods.  The table is staged with its
+// beginning repeated behind its end, so that a segment reads `base + j` with j in the instruction's offset field: no
+// address arithmetic and no wrap test per period; between segments the base advances by 8 mod T and wraps once, and
+// the checked window is tested (a segment is at most 8 periods: the window smmc_capi.cpp derives for "at most 8
+// periods until the next test" holds).  Two layouts (BlockLayout):
+//   narrow  one copy, lds[i] = a[i mod T] for i < T + 7; a segment is eight 4-byte reads (the compiler pairs them
+//           into ds_read2_b32), each half-wave hitting 32 random banks;
+//   wide    four copies, copy c holding a[(i + c) mod T] at slot i < round4(T) + 8: a lane whose base is s reads
+//           copy s & 3 at slot s & ~3, which is 16-byte aligned, so a segment is two ds_read_b128 (64 banks, 16
+//           lanes per LDS cycle).  18 KiB at T = 1127; the host picks it while eight workgroups per CU still fit.
+constexpr int kBlockSeg = 8;
+constexpr uint32_t kBlockCopies = 4;
+struct BlockLayout {  // wave-uniform
+  uint32_t block_len;   // L
+  uint32_t copy_words;  // words per staged copy
+  uint32_t step;        // kBlockSeg mod T: what a base advances by between segments
+};
+constexpr uint32_t blocks_copy_words(uint32_t table_len, bool wide) {
+  return wide ? ((table_len + 3u) & ~3u) + kBlockSeg : table_len + kBlockSeg - 1u;
+}
+constexpr uint32_t blocks_table_words(uint32_t table_len, bool wide) {
+  return blocks_copy_words(table_len, wide) * (wide ? kBlockCopies : 1u);
+}
+
+template <bool kWide>
+__device__ __forceinline__ void stage_block_table(const KernelArgs &k, const BlockLayout &g, float *lds, uint32_t threads) {
+  const uint32_t T = k.table_len;
+  for (uint32_t c = 0; c < (kWide ? kBlockCopies : 1u); ++c)
+    for (uint32_t i = threadIdx.x; i < g.copy_words; i += threads) lds[c * g.copy_words + i] = k.table_a[(i + c) % T];
+}
+
+// The D block starts of Philox block `blk` of a path: exactly the table indices block_multipliers draws there, in its
+// order ia[0..3], ib[0..3] (D = 8, T <= 2048) or the four __umulhi digits (D = 4).  The device-side draw of the block
+// bootstrap, for whichever kernel walks blocks.
+template <bool kDense>
+__device__ __forceinline__ void block_starts(const KernelArgs &k, const DrawRegs &dr, uint32_t path_lo, uint32_t path_hi, uint32_t blk,
+                                             uint32_t (&s)[Draws<SMMC_MODE_TABLE, kDense>::value]) {
+  uint32_t u[4];
+  philox4x32_10<true>(blk, path_lo, path_hi, mode_tag(SMMC_MODE_TABLE), k.key0, k.key1, dr, u);
+  if constexpr (kDense) {
+    uint32_t ia[4], ib[4];
+    digits4(u[0], u[1], k.table_len, ia);
+    digits4(u[2], u[3], k.table_len, ib);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s[j] = ia[j];
+      s[4 + j] = ib[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = __umulhi(u[j], k.table_len);
+  }
+}
+
+// Where the segment that begins at table index s < T lies in LDS (word index).
+template <bool kWide>
+__device__ __forceinline__ uint32_t block_segment_at(const BlockLayout &g, uint32_t s) {
+  if constexpr (kWide) return (s & 3u) * g.copy_words + (s & ~3u);
+  return s;
+}
+
+// `len` >= 1 consecutive periods (wave-uniform) from table index s < T, wrapping at the end of the table.
+template <bool kExactDiv, bool kChecked, bool kWide>
+__device__ __forceinline__ void block_run(const KernelArgs &k, const BlockLayout &g, const float *lds, uint32_t s, uint32_t len,
+                                          float &total, bool &left_window) {
+  uint32_t rem = len;
+  for (; rem >= kBlockSeg; rem -= kBlockSeg) {
+    const float *at = lds + block_segment_at<kWide>(g, s);
+    float a[kBlockSeg];
+    if constexpr (kWide) {
+      const f32x4_t q0 = *reinterpret_cast<const f32x4_t *>(at), q1 = *reinterpret_cast<const f32x4_t *>(at + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        a[j] = q0[j];
+        a[4 + j] = q1[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kBlockSeg; ++j) a[j] = at[j];
+    }
+#pragma unroll
+    for (int j = 0; j < kBlockSeg; ++j) total = compound<kExactDiv>(total, a[j]);
+    if constexpr (kChecked) left_window |= !(total > k.chk_lo && total < k.chk_hi);  // NaN leaves too
+    s += g.step;  // < 2 T
+    s = s >= k.table_len ? s - k.table_len : s;
+  }
+  if (rem) {  // wave-uniform: the block's last 1 .. 7 periods
+    const float *at = lds + block_segment_at<kWide>(g, s);
+    if constexpr (kWide) {
+      const f32x4_t q0 = *reinterpret_cast<const f32x4_t *>(at);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (static_cast<uint32_t>(j) < rem) total = compound<kExactDiv>(total, q0[j]);
+      if (rem > 4) {
+        const f32x4_t q1 = *reinterpret_cast<const f32x4_t *>(at + 4);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (static_cast<uint32_t>(4 + j) < rem) total = compound<kExactDiv>(total, q1[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kBlockSeg - 1; ++j)
+        if (static_cast<uint32_t>(j) < rem) total = compound<kExactDiv>(total, at[j]);
+    }
+    if constexpr (kChecked) left_window |= !(total > k.chk_lo && total < k.chk_hi);
+  }
+}
+
+template <int kDiv, bool kDense, bool kWide>
+__device__ __forceinline__ float simulate_block_path(const KernelArgs &k, const BlockLayout &g, const DrawRegs &dr, const float *lds,
+                                                     uint64_t path) {
+  constexpr int kDraws = Draws<SMMC_MODE_TABLE, kDense>::value;
+  constexpr bool kExactDiv = kDiv == kDivExact;
+  const uint32_t path_lo = static_cast<uint32_t>(path);
+  const uint32_t path_hi = static_cast<uint32_t>(path >> 32);
+  float total = k.initial_capital;
+  bool left_window = false;
+  uint32_t t = 0;  // periods done; the block in hand covers [t, t + L)
+  for (uint32_t blk = 0; t < k.n_periods; ++blk) {
+    uint32_t s[kDraws];
+    block_starts<kDense>(k, dr, path_lo, path_hi, blk, s);
+#pragma unroll
+    for (int d = 0; d < kDraws; ++d) {
+      if (t < k.n_periods) {  // wave-uniform
+        const uint32_t left = k.n_periods - t;
+        const uint32_t len = left < g.block_len ? left : g.block_len;
+        block_run<kExactDiv, kDiv == kDivChecked, kWide>(k, g, lds, s[d], len, total, left_window);
+        t += len;
+      }
+    }
+  }
+  if constexpr (kDiv == kDivChecked) {
+    if (left_window) total = simulate_block_path<kDivExact, kDense, kWide>(k, g, dr, lds, path);
+  }
+  return total;
+}
+
+// paths_kernel's chunk walk, outputs and epilogue for a 256-thread workgroup, as a function of what is staged in front
+// of the histogram and of how a lane walks its path: `Walk` names both in static functions -- table_words(k, aux),
+// stage(k, aux, lds_table, threads per workgroup), simulate(k, aux, dr, lds_table, path) -- and `aux` is a launch
+// parameter of the walk's own (the block length).
+//
+// The statements are paths_kernel's (without its two-halves form), and they are here a second time because
+// paths_kernel has to stay the instruction sequence its counters were taken on (profiles/pmc_traffic.json: 1047
+// instructions in Gaussian mode, 1143 in table mode; tools/pmc_traffic.py --restamp compares the fingerprints).  Every
+// way of calling shared code from paths_kernel that was built moved that sequence, although each computes the same
+// values (same flags, same compiler; instructions Gaussian / table, "reordered" = same count, other order):
+//   the whole body as this function, walk passed as lambdas or as a static-function struct     1043 / 1146
+//   three pieces (per-path statistics + histogram, chunk mean/variance, partial fold + flush)   1046 / 1144
+//   only the per-path statistics + histogram, accumulators in a struct                          reordered / reordered
+//   only the per-path statistics + histogram, accumulators as reference arguments               unchanged / reordered
+//   only the chunk mean / variance block                                                        1046 / 1144
+//   only the partial fold + histogram flush (struct, or eight scalar arguments)                 reordered / reordered
+//   only the accumulators gathered in a struct, no function at all                              reordered / reordered
+//   only the histogram flush loop                                                               reordered / reordered
+// A change to one copy belongs in the other; tests/test_blocks_gpu.py holds block length 1 to paths_kernel's bytes.
+template <typename Walk>
+__device__ __forceinline__ void blocks_body(const KernelArgs &k, const uint32_t vgrid, const uint32_t aux, unsigned char *lds_raw) {
+  const uint32_t table_words = Walk::table_words(k, aux);
+  constexpr uint32_t kGroup = kBlock;  // threads per workgroup
+  float *lds_table = reinterpret_cast<float *>(lds_raw);  // returns table, or the Box-Muller tables
+  uint32_t *lds_hist = reinterpret_cast<uint32_t *>(lds_raw) + table_words;
+  // The reduction scratch lives BEHIND the tables in the dynamic allocation (paths_lds_bytes), not in
+  // static __shared__ arrays: static LDS is placed first, and a draw table that does not start at LDS
+  // address 0 costs one address add per gather (two VALU instructions per Philox block in Gaussian mode).
+  const uint32_t scratch_words = (table_words + ((k.partials != nullptr) ? k.n_bins : 0u) + 1u) & ~1u;  // 8-byte aligned
+  double *red_scratch = reinterpret_cast<double *>(reinterpret_cast<uint32_t *>(lds_raw) + scratch_words);  // [4 * kWaves]
+  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(red_scratch + 4 * kWaves);  // [kWaves]
+
+  const uint32_t tid = threadIdx.x;
+  bool parity = false;
+  unsigned long long clk0 = 0, real0 = 0;
+  if (k.clock_probe) {  // uniform; timing instrumentation only
+    clk0 = __builtin_amdgcn_s_memtime();
+    real0 = __builtin_amdgcn_s_memrealtime();
+  }
+  Walk::stage(k, aux, lds_table, kGroup);
+  const bool want_stats = k.partials != nullptr;
+  const bool want_hist = want_stats && k.n_bins != 0;
+  if (want_hist) {
+    for (uint32_t i = threadIdx.x; i < k.n_bins; i += kGroup) lds_hist[i] = 0u;
+  }
+  __syncthreads();
+
+  double sum = 0.0, sumsq = 0.0;
+  uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
+  float vmin = __builtin_inff(), vmax = -__builtin_inff();
+  const DrawRegs dr = make_draw_regs(k);
+
+  const uint64_t n_chunks = (k.n_paths + kBlock - 1) / kBlock;
+  // workgroup-uniform: every wave of the workgroup makes the same trips and meets the same barriers
+  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += vgrid) {
+    const uint64_t i = chunk * kBlock + tid;
+    const bool active = i < k.n_paths;
+    float v = 0.0f;
+    if (active) {
+      v = Walk::simulate(k, aux, dr, lds_table, k.first_path + i);
+      if (k.d_final) k.d_final[i] = v;
+    }
+    if (want_stats && active) {
+      const double dv = static_cast<double>(v);
+      sum += dv;
+      sumsq += dv * dv;
+      n_count += 1;
+      n_below += (v < k.below_threshold) ? 1u : 0u;
+      vmin = fminf(vmin, v);
+      vmax = fmaxf(vmax, v);
+      if (want_hist) {
+        if (v < k.hist_lo) {
+          n_under += 1;
+        } else if (v < k.hist_hi) {
+          int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
+          b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
+          atomicAdd(&lds_hist[b], 1u);
+        } else {
+          n_over += 1;
+        }
+      }
+    }
+    if (k.d_chunk_mean || k.d_chunk_var) {  // uniform over the workgroup
+      // mean and population variance of this chunk from one pass (sum and sum of squares in
+      // double: the cancellation in E[x^2] - mean^2 costs ~1e-15 relative here), one barrier:
+      // the scratch slots alternate with the iteration's parity
+      const double dv = active ? static_cast<double>(v) : 0.0;
+      const double s12 = wave_sum_pair(dv, dv * dv);  // lane 0: the wave's sum, lane 32: its sum of squares
+      double *slot = red_scratch + (parity ? 2 * kWaves : 0);
+      parity = !parity;
+      const int lane = tid & 63, wave = tid >> 6;
+      if ((lane & 31) == 0) slot[(lane ? kWaves : 0) + wave] = s12;
+      __syncthreads();
+      if (tid == 0) {
+        double t1 = slot[0], t2 = slot[kWaves];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) {
+          t1 += slot[w];
+          t2 += slot[kWaves + w];
+        }
+        // A full chunk -- every chunk but the last one of a launch -- needs no divide: t * 2^-8 and t / 256 are the
+        // same binary64 for every sum of binary32 values or of their squares (no subnormal double arises; inf and
+        // NaN go through alike).  The IEEE divides stay for the one chunk that may be ragged.
+        double mean, var;
+        if (chunk + 1 < n_chunks) {
+          static_assert(kBlock == 256, "the full chunk's reciprocal is 2^-8");
+          mean = t1 * 0x1p-8;
+          var = t2 * 0x1p-8 - mean * mean;
+        } else {
+          const double n_in = static_cast<double>(k.n_paths - chunk * kBlock);  // 1 .. kBlock
+          mean = t1 / n_in;
+          var = t2 / n_in - mean * mean;
+        }
+        if (k.d_chunk_mean) k.d_chunk_mean[chunk] = static_cast<float>(mean);
+        if (k.d_chunk_var) k.d_chunk_var[chunk] = static_cast<float>(var > 0.0 ? var : 0.0);
+      }
+    }
+  }
+
+  if (k.clock_probe && threadIdx.x == 0) {
+    atomicAdd(&k.clock_probe[0], __builtin_amdgcn_s_memtime() - clk0);
+    atomicAdd(&k.clock_probe[1], __builtin_amdgcn_s_memrealtime() - real0);
+  }
+  if (want_stats) {
+    // per-lane u32 counters cannot overflow: a lane sees < 2^32 chunks
+    BlockPartial p;
+    p.sum = wave_sum(sum);
+    p.sumsq = wave_sum(sumsq);
+    p.count = wave_sum(static_cast<unsigned long long>(n_count));
+    p.below = wave_sum(static_cast<unsigned long long>(n_below));
+    p.underflow = wave_sum(static_cast<unsigned long long>(n_under));
+    p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
+    p.min = wave_min(vmin);
+    p.max = wave_max(vmax);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) wave_part[wave] = p;
+    __syncthreads();
+    if (tid == 0) {  // one partial per workgroup
+      BlockPartial t = wave_part[0];
+#pragma unroll
+      for (int w = 1; w < kWaves; ++w) {
+        t.sum += wave_part[w].sum;
+        t.sumsq += wave_part[w].sumsq;
+        t.count += wave_part[w].count;
+        t.below += wave_part[w].below;
+        t.underflow += wave_part[w].underflow;
+        t.overflow += wave_part[w].overflow;
+        t.min = fminf(t.min, wave_part[w].min);
+        t.max = fmaxf(t.max, wave_part[w].max);
+      }
+      k.partials[blockIdx.x] = t;
+    }
+    if (want_hist) {  // LDS atomics of all waves are complete after the barrier above
+      for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
+        const uint32_t c = lds_hist[b];
+        if (c) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(c));
+      }
+    }
+  }
+}
+
+template <int kDiv, bool kDense, bool kWide>
+struct BlocksWalk {  // aux: the block length
+  static __device__ __forceinline__ BlockLayout layout(const KernelArgs &k, uint32_t block_len) {
+    return {block_len, blocks_copy_words(k.table_len, kWide), static_cast<uint32_t>(kBlockSeg) % k.table_len};
+  }
+  static __device__ __forceinline__ uint32_t table_words(const KernelArgs &k, uint32_t) { return blocks_table_words(k.table_len, kWide); }
+  static __device__ __forceinline__ void stage(const KernelArgs &k, uint32_t block_len, float *lds_table, uint32_t threads) {
+    stage_block_table<kWide>(k, layout(k, block_len), lds_table, threads);
+  }
+  static __device__ __forceinline__ float simulate(const KernelArgs &k, uint32_t block_len, const DrawRegs &dr, const float *lds_table,
+                                                   uint64_t path) {
+    return simulate_block_path<kDiv, kDense, kWide>(k, layout(k, block_len), dr, lds_table, path);
+  }
+};
+// The block walk inside blocks_body.  Eight waves per SIMD: the loop holds a base, a value and eight multipliers
+// beside the Philox state.
+template <int kDiv, bool kDense, bool kWide>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8)))
+void blocks_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t block_len) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  blocks_body<BlocksWalk<kDiv, kDense, kWide>>(k, vgrid, block_len, lds_raw);
+}
+
 // ---- checkpoints: the value distribution at chosen periods ---------------------------------------
 //
 // smmc_engine_simulate_checkpoints: the paths of paths_kernel, reduced not only at the end but after each of
@@ -2198,6 +2526,41 @@ hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exac
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream) {
   hipLaunchKernelGGL(finalize_depleted_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, acc, n, d_out);
   return hipGetLastError();
+}
+
+// ---- block bootstrap ----
+
+size_t blocks_lds_bytes(uint32_t table_len, uint32_t n_bins, bool wide) {
+  // paths_lds_bytes with the staged copies in the table's place
+  const size_t words = (static_cast<size_t>(blocks_table_words(table_len, wide)) + n_bins + 1u) & ~static_cast<size_t>(1);
+  return words * 4u + 4u * kWaves * sizeof(double) + kWaves * sizeof(BlockPartial);
+}
+
+template <int kDiv, bool kDense, bool kWide>
+static hipError_t launch_blocks_variant(const KernelArgs &a, uint32_t block_len, uint32_t grid, size_t lds, hipStream_t stream) {
+  hipError_t err = allow_lds(blocks_kernel<kDiv, kDense, kWide>, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((blocks_kernel<kDiv, kDense, kWide>), dim3(grid), dim3(kBlock), lds, stream, a, grid, block_len);
+  return hipGetLastError();
+}
+
+template <bool kDense, bool kWide>
+static hipError_t launch_blocks_layout(const KernelArgs &a, uint32_t block_len, int div, uint32_t grid, size_t lds, hipStream_t stream) {
+  switch (div) {
+    case SMMC_DIV_FAST: return launch_blocks_variant<kDivFast, kDense, kWide>(a, block_len, grid, lds, stream);
+    case SMMC_DIV_CHECKED: return launch_blocks_variant<kDivChecked, kDense, kWide>(a, block_len, grid, lds, stream);
+    default: return launch_blocks_variant<kDivExact, kDense, kWide>(a, block_len, grid, lds, stream);
+  }
+}
+
+hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int div, uint32_t grid, hipStream_t stream) {
+  if (a.mode != SMMC_MODE_TABLE || a.stream != 3 || !a.table_len || !block_len) return hipErrorInvalidValue;
+  const size_t lds = blocks_lds_bytes(a.table_len, a.partials ? a.n_bins : 0u, wide);
+  if (!table_is_dense(a.table_len))
+    return wide ? launch_blocks_layout<false, true>(a, block_len, div, grid, lds, stream)
+                : launch_blocks_layout<false, false>(a, block_len, div, grid, lds, stream);
+  return wide ? launch_blocks_layout<true, true>(a, block_len, div, grid, lds, stream)
+              : launch_blocks_layout<true, false>(a, block_len, div, grid, lds, stream);
 }
 
 // ---- excursions ----

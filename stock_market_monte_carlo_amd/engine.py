@@ -565,6 +565,76 @@ class Engine:
                 out[k] = out[k].tobytes()
         return out
 
+    # -- block bootstrap: table paths drawn in runs of consecutive months (smmc_engine_simulate_blocks) ----------
+    @staticmethod
+    def make_blocks(block_len, kind=_lib.BLOCKS_CIRCULAR):
+        b = _lib.Blocks()
+        b.struct_size, b.block_len, b.kind, b.reserved = C.sizeof(_lib.Blocks), int(block_len), kind, 0
+        return b
+
+    def simulate_blocks(self, sim, block_len, want_final=True, want_chunk_stats=False, want_stats=False, out=None):
+        """simulate() with the circular block bootstrap: a path is built from runs of block_len consecutive entries
+        of the returns table, each run starting where the table stream would have drawn a single month (table mode,
+        counter stream v3; include/smmc.h states the draw).  block_len = 1 is simulate() bit for bit.  Returns the
+        same SimResult of device tensors."""
+        raw = self.simulate_blocks_raw(sim, block_len, want_final, want_chunk_stats, want_stats, out)
+        res = SimResult()
+        res.final, res.chunk_mean, res.chunk_var, res.stats_raw = (raw["final"], raw["chunk_mean"], raw["chunk_var"],
+                                                                   raw["stats_raw"])
+        return res
+
+    def simulate_blocks_raw(self, sim, block_len, want_final=True, want_chunk_stats=False, want_stats=False, out=None):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, chunk_mean, chunk_var
+        (float32) and stats_raw (uint8, the packed record); None for what was not asked for."""
+        torch = self._torch
+        n = int(sim.n_paths)
+        blocks = self.make_blocks(block_len)
+        new = lambda want, count, dtype: torch.empty(count, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        nc = (n + _lib.CHUNK - 1) // _lib.CHUNK
+        res = {"final": out if (want_final and out is not None) else new(want_final, n, torch.float32),
+               "chunk_mean": new(want_chunk_stats, nc, torch.float32), "chunk_var": new(want_chunk_stats, nc, torch.float32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8)}
+        if res["final"] is not None:
+            assert res["final"].numel() >= n and res["final"].dtype == torch.float32 and res["final"].is_contiguous()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_blocks(self._h, C.byref(sim), C.byref(blocks), ptr(res["final"]),
+                                                       ptr(res["chunk_mean"]), ptr(res["chunk_var"]), ptr(res["stats_raw"])))
+        self._leave(cur, *res.values())
+        return res
+
+    def simulate_blocks_to_host(self, sim, block_len, out=None, want_stats=False, want_chunk_stats=False, progress=None):
+        """simulate_to_host() with block draws: (final, stats, (means, vars)) in host memory."""
+        n = int(sim.n_paths)
+        blocks = self.make_blocks(block_len)
+        host = out if out is not None else np.empty(n, dtype=np.float32)
+        assert host.dtype == np.float32 and host.size >= n and host.flags.c_contiguous
+        st = _lib.Stats()
+        hist = np.zeros(max(int(sim.n_bins), 1), dtype=np.uint64)
+        nc = (n + _lib.CHUNK - 1) // _lib.CHUNK
+        cm = np.empty(nc, dtype=np.float32) if want_chunk_stats else None
+        cv = np.empty(nc, dtype=np.float32) if want_chunk_stats else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._enter()  # synchronous: returns with both of its streams drained
+        _lib.check(self._L.smmc_engine_simulate_blocks_to_host(
+            self._h, C.byref(sim), C.byref(blocks), vp(host), vp(cm), vp(cv),
+            C.byref(progress) if progress is not None else None, C.byref(st) if want_stats else None,
+            vp(hist) if want_stats else None))
+        stats = None
+        if want_stats:
+            stats = Stats(st.count, st.below, st.underflow, st.overflow, st.sum, st.sumsq, st.min, st.max,
+                          hist[: int(sim.n_bins)])
+        return host, stats, (cm, cv)
+
+    def blocks_divide_kind(self, sim, block_len):
+        """DIV_FAST / DIV_EXACT / DIV_CHECKED: the divide simulate_blocks uses for this request (results never depend
+        on it)."""
+        blocks = self.make_blocks(block_len)
+        rc = self._L.smmc_engine_blocks_divide_kind(self._h, C.byref(sim), C.byref(blocks))
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
     def read_stats(self, stats_raw):
         """Copies a device record to the host after the engine stream has drained."""
         self.sync()
