@@ -3,7 +3,8 @@
 //
 // A translation unit of its own, as smmc_cashflow.cpp and smmc_excursions.cpp: smmc_capi.cpp owns struct smmc_engine
 // and never calls into this file; what is needed of an engine comes through smmc_internal.h.  It keeps no state per
-// engine: the partials and the bucket accumulator are the engine's, used as smmc_engine_simulate uses them.
+// engine: the partials and the bucket accumulator are the engine's, used as smmc_engine_simulate uses them; the
+// stream refusal, the timed launch and the HIP check are the shared host_require_v3, host_timed_launch and SMMC_HIP.
 // The reference resamples single months (src/simulations.cpp:240-252); it has no block draw.
 #include <hip/hip_runtime_api.h>
 
@@ -26,9 +27,8 @@ int check_blocks(const smmc_engine *e, const smmc_sim *sim, const smmc_blocks *b
     return host_fail(SMMC_ERR_INVALID, "smmc_blocks.struct_size is %u, this library expects %zu", b->struct_size, sizeof(smmc_blocks));
   if (sim->mode != SMMC_MODE_TABLE)
     return host_fail(SMMC_ERR_INVALID, "the block bootstrap resamples the returns table: mode must be SMMC_MODE_TABLE (got %d)", sim->mode);
-  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
-    return host_fail(SMMC_ERR_INVALID, "the block bootstrap supports counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
-                     (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  rc = smmc::host_require_v3(sim, "the block bootstrap supports");
+  if (rc) return rc;
   if (b->block_len == 0) return host_fail(SMMC_ERR_INVALID, "block_len is 0: a block holds at least one period");
   if (b->kind != SMMC_BLOCKS_CIRCULAR)
     return host_fail(SMMC_ERR_INVALID, "smmc_blocks.kind is %u: SMMC_BLOCKS_CIRCULAR (0) is the only kind", b->kind);
@@ -86,20 +86,12 @@ int enqueue_blocks(smmc_engine *e, const smmc_sim *s, const smmc_blocks *b, floa
   a.clock_probe = view.clock_probe;
   if (grid > 0) {
     const int div = smmc::host_divide_kind(e, s, true, &a.chk_lo, &a.chk_hi);
-    rc = smmc::engine_timing_begin(e);
-    if (rc) return rc;
-    const hipError_t err = smmc::launch_blocks(a, b->block_len, p.wide, div, grid, view.stream);
-    if (err != hipSuccess) {
-      (void)smmc::engine_timing_end(e);
-      return host_fail(SMMC_ERR_HIP, "launch_blocks failed: %s", hipGetErrorString(err));
-    }
-    rc = smmc::engine_timing_end(e);
+    rc = smmc::host_timed_launch(e, "launch_blocks", [&] { return smmc::launch_blocks(a, b->block_len, p.wide, div, grid, view.stream); });
     if (rc) return rc;
   }
   if (d_stats) {
-    const hipError_t err = smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, acc,
-                                                 s->n_bins ? 1u : 0u);
-    if (err != hipSuccess) return host_fail(SMMC_ERR_HIP, "launch_finalize failed: %s", hipGetErrorString(err));
+    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, acc,
+                                   s->n_bins ? 1u : 0u));
     if (acc) smmc::engine_acc_clean(e);
   }
   return SMMC_OK;

@@ -29,7 +29,6 @@
 namespace smmc {
 extern __attribute__((weak)) decltype(launch_checkpoints) launch_checkpoints;
 extern __attribute__((weak)) decltype(launch_finalize_checkpoints) launch_finalize_checkpoints;
-extern __attribute__((weak)) decltype(checkpoints_group_paths) checkpoints_group_paths;
 extern __attribute__((weak)) decltype(checkpoints_lds_bytes) checkpoints_lds_bytes;
 }  // namespace smmc
 
@@ -47,13 +46,7 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-#define SMMC_HIP(call)                                                                         \
-  do {                                                                                         \
-    hipError_t err__ = (call);                                                                 \
-    if (err__ != hipSuccess)                                                                   \
-      return fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__),     \
-                  __FILE__, __LINE__);                                                         \
-  } while (0)
+// SMMC_HIP: smmc_internal.h
 
 // Inside an open timing pair (timing_begin .. timing_end): a failure closes the pair before it returns,
 // so that smmc_engine_kernel_ms never reads a start event without its stop.
@@ -495,14 +488,7 @@ int enqueue_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, float 
     if (lds + 2048 > e->max_lds)
       return fail(SMMC_ERR_INVALID, "table + histogram need %zu bytes of LDS, device allows %zu", lds, e->max_lds);
     const int div = divide_kind(e, s, true, &a.chk_lo, &a.chk_hi);
-    int rc = timing_begin(e);
-    if (rc) return rc;
-    const hipError_t err = smmc::launch_paths(a, div, grid, lds, e->stream);
-    if (err != hipSuccess) {
-      (void)timing_end(e);
-      return fail(SMMC_ERR_HIP, "launch_paths failed: %s", hipGetErrorString(err));
-    }
-    rc = timing_end(e);
+    const int rc = smmc::host_timed_launch(e, "launch_paths", [&] { return smmc::launch_paths(a, div, grid, lds, e->stream); });
     if (rc) return rc;
   }
   if (d_stats) {
@@ -912,9 +898,8 @@ static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const ui
   if (n_checkpoints == 0) return fail(SMMC_ERR_INVALID, "n_checkpoints is 0");
   if (n_checkpoints > SMMC_MAX_CHECKPOINTS)
     return fail(SMMC_ERR_INVALID, "n_checkpoints %u exceeds SMMC_MAX_CHECKPOINTS %d", n_checkpoints, SMMC_MAX_CHECKPOINTS);
-  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
-    return fail(SMMC_ERR_INVALID, "checkpoint statistics support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
-                (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  rc = smmc::host_require_v3(sim, "checkpoint statistics support");
+  if (rc) return rc;
   for (uint32_t i = 0; i < n_checkpoints; ++i) {
     if (periods[i] == 0) return fail(SMMC_ERR_INVALID, "periods[%u] is 0: checkpoints are periods 1 .. n_periods", i);
     if (periods[i] > sim->n_periods)
@@ -928,8 +913,7 @@ static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const ui
                 sim->n_bins, SMMC_MAX_CHECKPOINT_BINS);
   if (reinterpret_cast<uintptr_t>(final_ptr) & 3u) return fail(SMMC_ERR_INVALID, "the final-value pointer must be 4-byte aligned");
   if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(SMMC_ERR_INVALID, "the records pointer must be 8-byte aligned");
-  if (!smmc::launch_checkpoints || !smmc::launch_finalize_checkpoints || !smmc::checkpoints_group_paths ||
-      !smmc::checkpoints_lds_bytes)
+  if (!smmc::launch_checkpoints || !smmc::launch_finalize_checkpoints || !smmc::checkpoints_lds_bytes)
     return fail(SMMC_ERR_HIP, "this build carries no checkpoint kernel");
   return SMMC_OK;
 }
@@ -938,15 +922,10 @@ int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const 
                                      float *d_final, void *d_records) {
   int rc = check_checkpoints(e, sim, periods, n_checkpoints, d_final, d_records);
   if (rc) return rc;
-  // launch geometry: a workgroup walks chunks of group_paths consecutive paths
-  const uint32_t group_paths = smmc::checkpoints_group_paths(sim->mode);
-  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
-  const uint32_t grid = static_cast<uint32_t>(
-      std::min<uint64_t>(n_chunks, std::min(e->compute_units * kCheckpointGroupsPerCU, e->max_grid)));
-  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS buckets)
-  if (grid && (n_chunks + grid - 1) / grid * group_paths >= (1ull << 32))
-    return fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
-                static_cast<unsigned long long>(sim->n_paths));
+  uint32_t grid = 0;
+  rc = smmc::host_wave_walk_grid(smmc::engine_view(e), sim->n_paths, smmc::wave_walk_group_paths(sim->mode), kCheckpointGroupsPerCU,
+                                 e->max_grid, &grid);
+  if (rc) return rc;
   smmc::KernelArgs a = make_args(e, sim);
   const size_t lds = smmc::checkpoints_lds_bytes(a.mode, a.table_len, n_checkpoints, a.n_bins);
   if (lds + 2048 > e->max_lds)
@@ -973,14 +952,8 @@ int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const 
   if (grid) {
     float unused_lo, unused_hi;
     const bool exact_div = divide_kind(e, sim, false, &unused_lo, &unused_hi) != SMMC_DIV_FAST;
-    rc = timing_begin(e);
-    if (rc) return rc;
-    const hipError_t err = smmc::launch_checkpoints(a, periods, n_checkpoints, exact_div, grid, e->stream);
-    if (err != hipSuccess) {
-      (void)timing_end(e);
-      return fail(SMMC_ERR_HIP, "launch_checkpoints failed: %s", hipGetErrorString(err));
-    }
-    rc = timing_end(e);
+    rc = smmc::host_timed_launch(e, "launch_checkpoints",
+                                 [&] { return smmc::launch_checkpoints(a, periods, n_checkpoints, exact_div, grid, e->stream); });
     if (rc) return rc;
   }
   SMMC_HIP(smmc::launch_finalize_checkpoints(e->d_ck_partials, grid, n_checkpoints, d_records, sim->n_bins,
@@ -995,24 +968,11 @@ int smmc_engine_simulate_checkpoints_to_host(smmc_engine *e, const smmc_sim *sim
   if (rc) return rc;
   DeviceGuard guard(e->device);
   if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-  const size_t rec_bytes = static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) * n_checkpoints;
-  const size_t final_bytes = host_final ? sizeof(float) * sim->n_paths : 0;
-  void *d_records = nullptr;
-  float *d_final = nullptr;
-  SMMC_HIP(hipMalloc(&d_records, rec_bytes));
-  hipError_t err = final_bytes ? hipMalloc(reinterpret_cast<void **>(&d_final), final_bytes) : hipSuccess;
-  if (err == hipSuccess) {
-    rc = smmc_engine_simulate_checkpoints(e, sim, periods, n_checkpoints, d_final, d_records);
-    if (rc == SMMC_OK) err = hipStreamSynchronize(e->stream);
-    if (rc == SMMC_OK && err == hipSuccess) err = hipMemcpy(host_records, d_records, rec_bytes, hipMemcpyDeviceToHost);
-    if (rc == SMMC_OK && err == hipSuccess && final_bytes) err = hipMemcpy(host_final, d_final, final_bytes, hipMemcpyDeviceToHost);
-  }
-  if (rc != SMMC_OK) (void)hipStreamSynchronize(e->stream);  // nothing of the call may outlive its buffers
-  (void)hipFree(d_records);
-  if (d_final) (void)hipFree(d_final);
-  if (rc) return rc;
-  if (err != hipSuccess) return fail(SMMC_ERR_HIP, "simulate_checkpoints_to_host: %s", hipGetErrorString(err));
-  return SMMC_OK;
+  const smmc::HostPiece pieces[2] = {{host_records, static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) * n_checkpoints},
+                                     {host_final, sizeof(float) * sim->n_paths}};
+  return smmc::host_outputs_to_host(e, "simulate_checkpoints_to_host", pieces, 2, [&](void *const *dev) {
+    return smmc_engine_simulate_checkpoints(e, sim, periods, n_checkpoints, static_cast<float *>(dev[1]), dev[0]);
+  });
 }
 
 int smmc_engine_sync(smmc_engine *e) {
@@ -1721,8 +1681,55 @@ int engine_acc_begin(smmc_engine *e, unsigned long long **acc) {
   return SMMC_OK;
 }
 void engine_acc_clean(smmc_engine *e) { e->hist_dirty = false; }
-int engine_timing_begin(smmc_engine *e) { return timing_begin(e); }
-int engine_timing_end(smmc_engine *e) { return timing_end(e); }
+int host_require_v3(const smmc_sim *s, const char *feature) {
+  if (s->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
+    return fail(SMMC_ERR_INVALID, "%s counter stream v3 only (not SMMC_FLAG_STREAM_%s)", feature,
+                (s->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  return SMMC_OK;
+}
+int host_wave_walk_grid(const EngineView &v, uint64_t n_paths, uint32_t group_paths, uint32_t groups_per_cu, uint32_t grid_cap,
+                        uint32_t *grid) {
+  const uint64_t n_chunks = (n_paths + group_paths - 1) / group_paths;
+  *grid = static_cast<uint32_t>(std::min<uint64_t>(n_chunks, std::min(v.compute_units * groups_per_cu, grid_cap)));
+  // the kernels count a workgroup's paths in 32 bits (lane accumulators, LDS counters)
+  if (*grid && (n_chunks + *grid - 1) / *grid * group_paths >= (1ull << 32))
+    return fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
+                static_cast<unsigned long long>(n_paths));
+  return SMMC_OK;
+}
+int host_timed_launch(smmc_engine *e, const char *name, hipError_t (*launch)(void *ctx), void *ctx) {
+  int rc = timing_begin(e);
+  if (rc) return rc;
+  const hipError_t err = launch(ctx);
+  if (err != hipSuccess) {
+    (void)timing_end(e);
+    return fail(SMMC_ERR_HIP, "%s failed: %s", name, hipGetErrorString(err));
+  }
+  return timing_end(e);
+}
+int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces,
+                         int (*run)(void *const *dev, void *ctx), void *ctx) {
+  if (n_pieces > kMaxHostPieces) return fail(SMMC_ERR_INVALID, "%s: %d output pieces, at most %d", what, n_pieces, kMaxHostPieces);
+  size_t total = 0;
+  for (int i = 0; i < n_pieces; ++i) total += pieces[i].host ? pieces[i].bytes : 0;
+  char *d = nullptr;
+  if (total) SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
+  void *dev[kMaxHostPieces];
+  size_t at = 0;
+  for (int i = 0; i < n_pieces; ++i) {
+    const size_t bytes = pieces[i].host ? pieces[i].bytes : 0;
+    dev[i] = bytes ? d + at : nullptr;
+    at += bytes;
+  }
+  const int rc = run(dev, ctx);
+  hipError_t err = hipStreamSynchronize(e->stream);  // also after a failure: nothing of the call may outlive its buffer
+  for (int i = 0; i < n_pieces; ++i)
+    if (rc == SMMC_OK && err == hipSuccess && dev[i]) err = hipMemcpy(pieces[i].host, dev[i], pieces[i].bytes, hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (rc) return rc;
+  if (err != hipSuccess) return fail(SMMC_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
+  return SMMC_OK;
+}
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi) {
   return divide_kind(e, s, allow_checked, chk_lo, chk_hi);
 }

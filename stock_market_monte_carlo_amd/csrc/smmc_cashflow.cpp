@@ -4,7 +4,9 @@
 // A translation unit of its own: smmc_capi.cpp owns struct smmc_engine and never calls into this file; what is
 // needed of an engine comes through smmc_internal.h (engine_view, engine_acc_begin, ...), and what this file keeps
 // per engine -- the staged schedule -- hangs in the engine's extension slot (engine_ext), released by
-// smmc_engine_destroy.  The reference has no counterpart: its README lists withdrawal strategies as open.
+// smmc_engine_destroy.  The launch is a wave walk, and its host side is the shared one: host_require_v3,
+// host_wave_walk_grid, host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in
+// smmc_capi.cpp).  The reference has no counterpart: its README lists withdrawal strategies as open.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -18,13 +20,6 @@ namespace {
 
 using smmc::DeviceGuard;
 using smmc::host_fail;
-
-#define SMMC_CF_HIP(call)                                                                                          \
-  do {                                                                                                             \
-    hipError_t err__ = (call);                                                                                     \
-    if (err__ != hipSuccess)                                                                                       \
-      return host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-  } while (0)
 
 // Workgroups per CU, as checkpoints_kernel (smmc_capi.cpp): a workgroup flushes n_periods + 1 + n_bins counters.
 constexpr uint32_t kCashflowGroupsPerCU = 32;
@@ -67,9 +62,9 @@ int state_of(smmc_engine *e, CashflowState **out) {
     ext->state = st;
     ext->release = release_state;
     const size_t bytes = sizeof(float) * 2u * kStrideMax;
-    SMMC_CF_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->h_slots), bytes * kSlots, hipHostMallocDefault));
-    SMMC_CF_HIP(hipMalloc(reinterpret_cast<void **>(&st->d_schedule), bytes));
-    for (hipEvent_t &ev : st->uploaded) SMMC_CF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    SMMC_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->h_slots), bytes * kSlots, hipHostMallocDefault));
+    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&st->d_schedule), bytes));
+    for (hipEvent_t &ev : st->uploaded) SMMC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
   *out = static_cast<CashflowState *>(ext->state);
   if (!(*out)->h_slots || !(*out)->d_schedule || !(*out)->uploaded[kSlots - 1])
@@ -88,9 +83,8 @@ int check_cashflow(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflo
   if (cf->struct_size != sizeof(smmc_cashflow))
     return host_fail(SMMC_ERR_INVALID, "smmc_cashflow.struct_size is %u, this library expects %zu", cf->struct_size,
                      sizeof(smmc_cashflow));
-  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
-    return host_fail(SMMC_ERR_INVALID, "cash flows support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
-                     (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  rc = smmc::host_require_v3(sim, "cash flows support");
+  if (rc) return rc;
   if (sim->n_periods == 0) return host_fail(SMMC_ERR_INVALID, "n_periods is 0: a cash flow needs at least one period");
   if (sim->n_periods > SMMC_MAX_CASHFLOW_PERIODS)
     return host_fail(SMMC_ERR_INVALID, "n_periods %u exceeds SMMC_MAX_CASHFLOW_PERIODS %d", sim->n_periods,
@@ -144,11 +138,6 @@ int cashflow_divide(const smmc_engine *e, const smmc_sim *sim, const smmc_cashfl
   return SMMC_DIV_FAST;
 }
 
-uint32_t launch_grid(const smmc::EngineView &v, const smmc_sim *sim, uint32_t group_paths) {
-  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
-  return static_cast<uint32_t>(std::min<uint64_t>(n_chunks, std::min(v.compute_units * kCashflowGroupsPerCU, v.max_grid)));
-}
-
 int check_outputs(const void *fin, const void *paid, const void *ruin, const void *stats, const void *dep) {
   if ((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(paid) | reinterpret_cast<uintptr_t>(ruin)) & 3u)
     return host_fail(SMMC_ERR_INVALID, "the final-value, paid and ruin-period pointers must be 4-byte aligned");
@@ -174,12 +163,9 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   rc = check_outputs(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
   if (rc) return rc;
   const smmc::EngineView view = smmc::engine_view(e);
-  const uint32_t group_paths = smmc::cashflow_group_paths(sim->mode);
-  const uint32_t grid = launch_grid(view, sim, group_paths);
-  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS counters)
-  if (grid && ((sim->n_paths + group_paths - 1) / group_paths + grid - 1) / grid * group_paths >= (1ull << 32))
-    return host_fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
-                     static_cast<unsigned long long>(sim->n_paths));
+  uint32_t grid = 0;
+  rc = smmc::host_wave_walk_grid(view, sim->n_paths, smmc::wave_walk_group_paths(sim->mode), kCashflowGroupsPerCU, view.max_grid, &grid);
+  if (rc) return rc;
   smmc::KernelArgs a = smmc::host_make_args(e, sim);
   if (!d_stats) a.n_bins = 0;
   const size_t lds = smmc::cashflow_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
@@ -201,7 +187,7 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
     rc = state_of(e, &st);
     if (rc) return rc;
     const int slot = st->next;
-    if (st->in_flight[slot]) SMMC_CF_HIP(hipEventSynchronize(st->uploaded[slot]));
+    if (st->in_flight[slot]) SMMC_HIP(hipEventSynchronize(st->uploaded[slot]));
     st->in_flight[slot] = false;
     const uint32_t stride = (sim->n_periods + 7u) & ~7u;
     float *h = st->h_slots + static_cast<size_t>(slot) * 2u * kStrideMax;
@@ -209,8 +195,8 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
       h[t] = t < sim->n_periods ? amount_at(cf, t) : 0.0f;
       h[stride + t] = t < sim->n_periods ? fraction_at(cf, t) : 0.0f;
     }
-    SMMC_CF_HIP(hipMemcpyAsync(st->d_schedule, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
-    SMMC_CF_HIP(hipEventRecord(st->uploaded[slot], view.stream));
+    SMMC_HIP(hipMemcpyAsync(st->d_schedule, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
+    SMMC_HIP(hipEventRecord(st->uploaded[slot], view.stream));
     st->in_flight[slot] = true;
     st->next = (slot + 1) % kSlots;
     c.schedule = st->d_schedule;
@@ -230,21 +216,14 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   if (d_depleted_at) c.d_depleted = acc + kDepletedAt;
   if (grid) {
     const bool exact_div = cashflow_divide(e, sim, cf) != SMMC_DIV_FAST;
-    rc = smmc::engine_timing_begin(e);
-    if (rc) return rc;
-    const hipError_t err = smmc::launch_cashflow(a, c, exact_div, grid, view.stream);
-    if (err != hipSuccess) {
-      (void)smmc::engine_timing_end(e);
-      return host_fail(SMMC_ERR_HIP, "launch_cashflow failed: %s", hipGetErrorString(err));
-    }
-    rc = smmc::engine_timing_end(e);
+    rc = smmc::host_timed_launch(e, "launch_cashflow", [&] { return smmc::launch_cashflow(a, c, exact_div, grid, view.stream); });
     if (rc) return rc;
   }
   if (d_stats)
-    SMMC_CF_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), sim->n_bins, view.stream,
+    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), sim->n_bins, view.stream,
                                       sim->n_bins ? acc : nullptr, sim->n_bins ? 1u : 0u));
   if (d_depleted_at)
-    SMMC_CF_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
+    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
                                                reinterpret_cast<unsigned long long *>(d_depleted_at), view.stream));
   if (use_acc) smmc::engine_acc_clean(e);
   return SMMC_OK;
@@ -258,31 +237,14 @@ int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, c
   const smmc::EngineView view = smmc::engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-  // one device allocation for all outputs, the 8-byte aligned ones first
-  const size_t stats_bytes = host_stats ? static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) : 0;
-  const size_t dep_bytes = host_depleted_at ? sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u) : 0;
   const size_t per_path = sizeof(float) * sim->n_paths;
-  const size_t final_bytes = host_final ? per_path : 0, paid_bytes = host_paid ? per_path : 0,
-               ruin_bytes = host_ruin_period ? per_path : 0;
-  const size_t total = stats_bytes + dep_bytes + final_bytes + paid_bytes + ruin_bytes;
-  char *d = nullptr;
-  if (total) SMMC_CF_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
-  char *d_stats = d, *d_dep = d_stats + stats_bytes, *d_fin = d_dep + dep_bytes, *d_paid = d_fin + final_bytes,
-       *d_ruin = d_paid + paid_bytes;
-  rc = smmc_engine_simulate_cashflow(e, sim, cf, final_bytes ? reinterpret_cast<float *>(d_fin) : nullptr,
-                                     paid_bytes ? reinterpret_cast<float *>(d_paid) : nullptr,
-                                     ruin_bytes ? reinterpret_cast<uint32_t *>(d_ruin) : nullptr, stats_bytes ? d_stats : nullptr,
-                                     dep_bytes ? reinterpret_cast<uint64_t *>(d_dep) : nullptr);
-  hipError_t err = hipStreamSynchronize(view.stream);  // also after a failure: nothing of the call may outlive its buffer
-  struct Piece { void *host; const char *dev; size_t bytes; };
-  const Piece pieces[5] = {{host_stats, d_stats, stats_bytes}, {host_depleted_at, d_dep, dep_bytes}, {host_final, d_fin, final_bytes},
-                           {host_paid, d_paid, paid_bytes}, {host_ruin_period, d_ruin, ruin_bytes}};
-  for (const Piece &p : pieces)
-    if (rc == SMMC_OK && err == hipSuccess && p.bytes) err = hipMemcpy(p.host, p.dev, p.bytes, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (rc) return rc;
-  if (err != hipSuccess) return host_fail(SMMC_ERR_HIP, "simulate_cashflow_to_host: %s", hipGetErrorString(err));
-  return SMMC_OK;
+  const smmc::HostPiece pieces[5] = {{host_stats, static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
+                                     {host_depleted_at, sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u)},
+                                     {host_final, per_path}, {host_paid, per_path}, {host_ruin_period, per_path}};
+  return smmc::host_outputs_to_host(e, "simulate_cashflow_to_host", pieces, 5, [&](void *const *dev) {
+    return smmc_engine_simulate_cashflow(e, sim, cf, static_cast<float *>(dev[2]), static_cast<float *>(dev[3]),
+                                         static_cast<uint32_t *>(dev[4]), dev[0], static_cast<uint64_t *>(dev[1]));
+  });
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 // A translation unit of its own, as smmc_cashflow.cpp: smmc_capi.cpp owns struct smmc_engine and never calls into
 // this file; what is needed of an engine comes through smmc_internal.h.  It keeps no state per engine: the two
 // records use the halves of the engine's partial array, the four counter arrays the engine's zeroed accumulator.
+// The launch is a wave walk, and its host side is the shared one: host_require_v3, host_wave_walk_grid,
+// host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in smmc_capi.cpp).
 // The reference draws the MINIMUM and TARGET levels across its trajectory plot
 // (examples/visualize_returns_cpu_v2.cpp:397-411) and counts final values below the minimum (:125-138); what
 // happened along a path it can only read off the stored trajectories.
@@ -19,13 +21,6 @@ namespace {
 
 using smmc::DeviceGuard;
 using smmc::host_fail;
-
-#define SMMC_EX_HIP(call)                                                                                          \
-  do {                                                                                                             \
-    hipError_t err__ = (call);                                                                                     \
-    if (err__ != hipSuccess)                                                                                       \
-      return host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-  } while (0)
 
 // Workgroups per CU, as cashflow_kernel: a workgroup flushes 2 (n_periods + 1) + 2 n_bins counters.
 constexpr uint32_t kExcursionGroupsPerCU = 32;
@@ -48,9 +43,8 @@ int check_excursions(const smmc_engine *e, const smmc_sim *sim, const smmc_excur
   if (out->struct_size != sizeof(smmc_excursion_outputs))
     return host_fail(SMMC_ERR_INVALID, "smmc_excursion_outputs.struct_size is %u, this library expects %zu", out->struct_size,
                      sizeof(smmc_excursion_outputs));
-  if (sim->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
-    return host_fail(SMMC_ERR_INVALID, "excursions support counter stream v3 only (not SMMC_FLAG_STREAM_%s)",
-                     (sim->flags & SMMC_FLAG_STREAM_REF) ? "REF" : "V2");
+  rc = smmc::host_require_v3(sim, "excursions support");
+  if (rc) return rc;
   if (sim->n_periods == 0) return host_fail(SMMC_ERR_INVALID, "n_periods is 0: an excursion needs at least one period");
   if (sim->n_periods > SMMC_MAX_EXCURSION_PERIODS)
     return host_fail(SMMC_ERR_INVALID, "n_periods %u exceeds SMMC_MAX_EXCURSION_PERIODS %d", sim->n_periods,
@@ -79,16 +73,12 @@ struct Geometry {
   uint32_t n_bins;      // of the launch: 0 when no record is asked for
 };
 int plan(const smmc_engine *e, const smmc::EngineView &view, const smmc_sim *sim, const smmc_excursion_outputs *out, Geometry *g) {
-  const uint32_t group_paths = smmc::excursions_group_paths(sim->mode);
-  const uint64_t n_chunks = (sim->n_paths + group_paths - 1) / group_paths;
   // two records leave two partials per workgroup: the halves of the engine's partial array
   g->half = view.max_grid / 2u;
-  g->grid = static_cast<uint32_t>(std::min<uint64_t>(n_chunks, std::min(view.compute_units * kExcursionGroupsPerCU, g->half)));
+  const int rc = smmc::host_wave_walk_grid(view, sim->n_paths, smmc::wave_walk_group_paths(sim->mode), kExcursionGroupsPerCU, g->half,
+                                           &g->grid);
   if (sim->n_paths && !g->grid) return host_fail(SMMC_ERR_INVALID, "the engine's launch grid is too small for two records");
-  // the kernel counts a workgroup's paths in 32 bits (lane accumulators, LDS counters)
-  if (g->grid && (n_chunks + g->grid - 1) / g->grid * group_paths >= (1ull << 32))
-    return host_fail(SMMC_ERR_INVALID, "n_paths %llu gives a workgroup 2^32 paths or more: shard the request",
-                     static_cast<unsigned long long>(sim->n_paths));
+  if (rc) return rc;
   g->n_bins = (out->stats || out->drawdown_stats) ? sim->n_bins : 0u;
   const smmc::KernelArgs a = smmc::host_make_args(e, sim);
   const size_t lds = smmc::excursions_lds_bytes(a.mode, a.table_len, a.n_periods, g->n_bins);
@@ -152,28 +142,22 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
   if (out->first_below_at) xa.d_below_at = acc + kAccBelowAt;
   if (out->first_reach_at) xa.d_reach_at = acc + kAccReachAt;
   if (grid) {
-    rc = smmc::engine_timing_begin(e);
-    if (rc) return rc;
-    const hipError_t err = smmc::launch_excursions(a, xa, div != SMMC_DIV_FAST, grid, view.stream);
-    if (err != hipSuccess) {
-      (void)smmc::engine_timing_end(e);
-      return host_fail(SMMC_ERR_HIP, "launch_excursions failed: %s", hipGetErrorString(err));
-    }
-    rc = smmc::engine_timing_end(e);
+    rc = smmc::host_timed_launch(e, "launch_excursions",
+                                 [&] { return smmc::launch_excursions(a, xa, div != SMMC_DIV_FAST, grid, view.stream); });
     if (rc) return rc;
   }
   const uint32_t spread = sim->n_bins ? 1u : 0u;
   if (out->stats)
-    SMMC_EX_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(out->stats), sim->n_bins, view.stream,
+    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(out->stats), sim->n_bins, view.stream,
                                       sim->n_bins ? acc : nullptr, spread));
   if (out->drawdown_stats)
-    SMMC_EX_HIP(smmc::launch_finalize(view.d_partials + half, grid, static_cast<smmc_stats *>(out->drawdown_stats), sim->n_bins,
+    SMMC_HIP(smmc::launch_finalize(view.d_partials + half, grid, static_cast<smmc_stats *>(out->drawdown_stats), sim->n_bins,
                                       view.stream, sim->n_bins ? acc + kAccDrawdownHist : nullptr, spread));
   if (out->first_below_at)
-    SMMC_EX_HIP(smmc::launch_finalize_depleted(acc + kAccBelowAt, sim->n_periods + 1u,
+    SMMC_HIP(smmc::launch_finalize_depleted(acc + kAccBelowAt, sim->n_periods + 1u,
                                                reinterpret_cast<unsigned long long *>(out->first_below_at), view.stream));
   if (out->first_reach_at)
-    SMMC_EX_HIP(smmc::launch_finalize_depleted(acc + kAccReachAt, sim->n_periods + 1u,
+    SMMC_HIP(smmc::launch_finalize_depleted(acc + kAccReachAt, sim->n_periods + 1u,
                                                reinterpret_cast<unsigned long long *>(out->first_reach_at), view.stream));
   if (use_acc) smmc::engine_acc_clean(e);
   return SMMC_OK;
@@ -189,47 +173,31 @@ int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim,
   if (rc) return rc;
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-  // one device allocation for all outputs, the 8-byte aligned ones first
   const size_t stats_bytes = static_cast<size_t>(smmc_stats_bytes(sim->n_bins));
   const size_t at_bytes = sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u);
   const size_t per_path = sizeof(float) * sim->n_paths;
-  struct Piece { void *host; size_t bytes; size_t offset; };
-  Piece pieces[12] = {{out->stats, stats_bytes, 0},       {out->drawdown_stats, stats_bytes, 0}, {out->first_below_at, at_bytes, 0},
-                      {out->first_reach_at, at_bytes, 0}, {out->final, per_path, 0},             {out->peak, per_path, 0},
-                      {out->low, per_path, 0},            {out->drawdown, per_path, 0},          {out->drawdown_period, per_path, 0},
-                      {out->underwater, per_path, 0},     {out->first_below, per_path, 0},       {out->first_reach, per_path, 0}};
-  size_t total = 0;
-  for (Piece &p : pieces) {
-    if (!p.host) p.bytes = 0;
-    p.offset = total;
-    total += p.bytes;
-  }
-  char *d = nullptr;
-  if (total) SMMC_EX_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
-  auto dev = [&](int i) -> void * { return pieces[i].bytes ? d + pieces[i].offset : nullptr; };
-  smmc_excursion_outputs o;
-  std::memset(&o, 0, sizeof o);
-  o.struct_size = sizeof o;
-  o.stats = dev(0);
-  o.drawdown_stats = dev(1);
-  o.first_below_at = static_cast<uint64_t *>(dev(2));
-  o.first_reach_at = static_cast<uint64_t *>(dev(3));
-  o.final = static_cast<float *>(dev(4));
-  o.peak = static_cast<float *>(dev(5));
-  o.low = static_cast<float *>(dev(6));
-  o.drawdown = static_cast<float *>(dev(7));
-  o.drawdown_period = static_cast<uint32_t *>(dev(8));
-  o.underwater = static_cast<uint32_t *>(dev(9));
-  o.first_below = static_cast<uint32_t *>(dev(10));
-  o.first_reach = static_cast<uint32_t *>(dev(11));
-  rc = smmc_engine_simulate_excursions(e, sim, x, &o);
-  hipError_t err = hipStreamSynchronize(view.stream);  // also after a failure: nothing of the call may outlive its buffer
-  for (const Piece &p : pieces)
-    if (rc == SMMC_OK && err == hipSuccess && p.bytes) err = hipMemcpy(p.host, d + p.offset, p.bytes, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (rc) return rc;
-  if (err != hipSuccess) return host_fail(SMMC_ERR_HIP, "simulate_excursions_to_host: %s", hipGetErrorString(err));
-  return SMMC_OK;
+  const smmc::HostPiece pieces[12] = {
+      {out->stats, stats_bytes}, {out->drawdown_stats, stats_bytes}, {out->first_below_at, at_bytes}, {out->first_reach_at, at_bytes},
+      {out->final, per_path},    {out->peak, per_path},              {out->low, per_path},            {out->drawdown, per_path},
+      {out->drawdown_period, per_path}, {out->underwater, per_path}, {out->first_below, per_path},    {out->first_reach, per_path}};
+  return smmc::host_outputs_to_host(e, "simulate_excursions_to_host", pieces, 12, [&](void *const *dev) {
+    smmc_excursion_outputs o;
+    std::memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.stats = dev[0];
+    o.drawdown_stats = dev[1];
+    o.first_below_at = static_cast<uint64_t *>(dev[2]);
+    o.first_reach_at = static_cast<uint64_t *>(dev[3]);
+    o.final = static_cast<float *>(dev[4]);
+    o.peak = static_cast<float *>(dev[5]);
+    o.low = static_cast<float *>(dev[6]);
+    o.drawdown = static_cast<float *>(dev[7]);
+    o.drawdown_period = static_cast<uint32_t *>(dev[8]);
+    o.underwater = static_cast<uint32_t *>(dev[9]);
+    o.first_below = static_cast<uint32_t *>(dev[10]);
+    o.first_reach = static_cast<uint32_t *>(dev[11]);
+    return smmc_engine_simulate_excursions(e, sim, x, &o);
+  });
 }
 
 }  // extern "C"

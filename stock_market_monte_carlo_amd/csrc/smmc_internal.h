@@ -140,13 +140,15 @@ hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count
 size_t paths_lds_bytes(uint32_t table_len, uint32_t n_bins, int stream);
 // checkpoints_kernel (smmc_engine_simulate_checkpoints; counter stream v3 only).  a.partials: n_checkpoints x grid
 // entries, [checkpoint][workgroup]; a.d_hist: n_checkpoints x a.n_bins counters, zero before the launch.  A workgroup
-// walks chunks of checkpoints_group_paths(mode) consecutive paths.  launch_finalize_checkpoints folds both into the
+// walks chunks of wave_walk_group_paths(mode) consecutive paths.  launch_finalize_checkpoints folds both into the
 // n_checkpoints packed records at d_records and leaves the counters zero.
 hipError_t launch_checkpoints(const KernelArgs &a, const uint32_t *periods, uint32_t n_checkpoints, bool exact_div,
                               uint32_t grid, hipStream_t stream);
 hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_partials, uint32_t n_checkpoints,
                                        void *d_records, uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream);
-uint32_t checkpoints_group_paths(int32_t mode);
+// Paths per workgroup of checkpoints_kernel, cashflow_kernel and excursions_kernel alike: 64 per wave, eight waves in
+// Gaussian mode (on one copy of the draw tables), four in table mode.
+constexpr uint32_t wave_walk_group_paths(int32_t mode) { return mode == SMMC_MODE_TABLE ? 256u : 512u; }
 size_t checkpoints_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_checkpoints, uint32_t n_bins);
 // cashflow_kernel (smmc_engine_simulate_cashflow, csrc/smmc_cashflow.cpp; counter stream v3 only): the paths of
 // paths_kernel with a withdrawal / contribution step after every period's return ("Cash flows").
@@ -160,11 +162,10 @@ struct CashflowArgs {
   unsigned long long *d_depleted;  // nullable: n_periods + 1 counters, zero before the launch ([0]: never depleted)
 };
 // a.partials: `grid` entries (one per workgroup) or null; a.d_hist: a.n_bins counters, zero before the launch.  A
-// workgroup walks chunks of cashflow_group_paths(mode) consecutive paths.
+// workgroup walks chunks of wave_walk_group_paths(mode) consecutive paths.
 hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, hipStream_t stream);
 // d_out[i] = acc[i] for i < n, and leaves acc zero (the engine's accumulator between launches)
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream);
-uint32_t cashflow_group_paths(int32_t mode);
 size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
 // excursions_kernel (smmc_engine_simulate_excursions, csrc/smmc_excursions.cpp; counter stream v3 only): the paths of
 // paths_kernel with the running extremes, the deepest relative drawdown, the longest time under water and the first
@@ -182,7 +183,6 @@ struct ExcursionArgs {
 // a.partials / a.d_hist: the record of the final values, as launch_cashflow.  a.n_bins applies to both histograms.
 hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
 // (the count arrays are copied out, and the accumulator left zero, by launch_finalize_depleted)
-uint32_t excursions_group_paths(int32_t mode);
 size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
 // blocks_kernel (smmc_engine_simulate_blocks, csrc/smmc_blocks.cpp; counter stream v3, table mode): the outputs of
 // launch_paths for paths drawn in runs of block_len consecutive table entries ("Block bootstrap").
@@ -194,7 +194,7 @@ size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
 
-// ---- what smmc_capi.cpp shares with the library's other host translation units (smmc_cashflow.cpp) ----------
+// ---- what smmc_capi.cpp shares with the library's other host translation units (smmc_cashflow.cpp, ...) -----
 // Defined in smmc_capi.cpp, which owns struct smmc_engine; a unit that adds an entry point goes through these and
 // keeps what it needs per engine in its own state (engine_ext), so that smmc_capi.cpp never calls into it.
 
@@ -225,6 +225,42 @@ struct EngineExt {  // one slot of state owned by another translation unit: smmc
   void (*release)(void *state);
 };
 int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));  // sets smmc_last_error()
+// Returns SMMC_ERR_HIP with the call's text and place out of the enclosing function when a HIP call fails.
+#define SMMC_HIP(call)                                                                                                   \
+  do {                                                                                                                   \
+    hipError_t err__ = (call);                                                                                           \
+    if (err__ != hipSuccess)                                                                                             \
+      return smmc::host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
+  } while (0)
+// "<feature> counter stream v3 only": the refusal of SMMC_FLAG_STREAM_REF and SMMC_FLAG_STREAM_V2; `feature` ends in
+// its verb ("cash flows support").
+int host_require_v3(const smmc_sim *s, const char *feature);
+// The grid of a wave-walk launch (wave_walk_group_paths): the chunks of group_paths, at most groups_per_cu workgroups
+// per CU and at most grid_cap.  Refuses a request that would give a workgroup 2^32 paths or more (u32 counters).
+int host_wave_walk_grid(const EngineView &v, uint64_t n_paths, uint32_t group_paths, uint32_t groups_per_cu, uint32_t grid_cap,
+                        uint32_t *grid);
+// The engine's timing pair around launch(ctx) -- begun before, closed on both paths; a failed launch is
+// "<name> failed: <HIP's text>".  The template takes any callable returning hipError_t.
+int host_timed_launch(smmc_engine *e, const char *name, hipError_t (*launch)(void *ctx), void *ctx);
+template <typename F>
+int host_timed_launch(smmc_engine *e, const char *name, F launch) {
+  return host_timed_launch(e, name, [](void *f) { return (*static_cast<F *>(f))(); }, &launch);
+}
+// The _to_host form of an entry: one device allocation for all pieces (host == null: left out; the 8-byte aligned
+// ones come first), run(dev, ctx) with the pieces' device pointers (null for one left out) enqueues on the engine
+// stream; the stream is synchronised also after a failure (nothing of the call may outlive the buffer), the pieces
+// are copied if all went well.  A HIP failure after a successful run is "<what>: <HIP's text>".  Device must be current.
+struct HostPiece {
+  void *host;
+  size_t bytes;
+};
+constexpr int kMaxHostPieces = 12;  // the most any entry has: the twelve outputs of smmc_excursion_outputs
+int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces,
+                         int (*run)(void *const *dev, void *ctx), void *ctx);
+template <typename F>  // any callable int(void *const *dev), as host_timed_launch
+int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces, F run) {
+  return host_outputs_to_host(e, what, pieces, n_pieces, [](void *const *dev, void *f) { return (*static_cast<F *>(f))(dev); }, &run);
+}
 int host_check_sim(const smmc_engine *e, const smmc_sim *s);
 // bounds on a = 100 + r of one period; false if there are none (smmc_capi.cpp, divide_kind)
 bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
@@ -235,8 +271,6 @@ EngineExt *engine_ext(smmc_engine *e);
 // finalize put it back to zero): *acc is ready, and marked dirty until engine_acc_clean says the finalize is queued.
 int engine_acc_begin(smmc_engine *e, unsigned long long **acc);
 void engine_acc_clean(smmc_engine *e);
-int engine_timing_begin(smmc_engine *e);
-int engine_timing_end(smmc_engine *e);
 // smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
 // smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around

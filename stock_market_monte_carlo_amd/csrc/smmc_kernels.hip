@@ -1100,51 +1100,96 @@ void blocks_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t bloc
   blocks_body<BlocksWalk<kDiv, kDense, kWide>>(k, vgrid, block_len, lds_raw);
 }
 
-// ---- checkpoints: the value distribution at chosen periods ---------------------------------------
+// ---- the wave walk: the skeleton of checkpoints_kernel, cashflow_kernel and excursions_kernel ------
 //
-// smmc_engine_simulate_checkpoints: the paths of paths_kernel, reduced not only at the end but after each of
-// c.n chosen periods -- one statistics record per checkpoint instead of a trajectory per path.  Bound like
-// paths_kernel: VALU issue; HBM sees 4 B per path (d_final) or nothing.
+// Three kernels are one program with another step in the middle: the paths of paths_kernel, looked at after every
+// period (cash flows, excursions) or after chosen ones (checkpoints).  What they share is written here once; a
+// further path statistic is a per-period step and what it emits per chunk, not a fourth copy.  Bound like
+// paths_kernel: VALU issue.
 //
-// Work.  A WAVE owns a chunk of 64 consecutive paths (one 256-byte final-value store) and walks the chunks
-// wc = blockIdx.x * kW + wave, + gridDim.x * kW, ...; there is no barrier inside the walk.  Every lane of a wave
-// runs a path, also beyond n_paths in the launch's last chunk (the wave reductions want the whole wave; such a
-// lane contributes nothing), so control flow is wave-uniform throughout.
+// Work (wave_chunks).  A WAVE owns a chunk of 64 consecutive paths (one 256-byte store per output) and walks the
+// chunks wc = blockIdx.x * kW + wave, + gridDim.x * kW, ...; there is no barrier inside the walk.  Every lane of a
+// wave runs a path, also beyond n_paths in the launch's last chunk (the wave reductions want the whole wave; such a
+// lane stores and counts nothing), so control flow is wave-uniform throughout.
 //
-// Where the checkpoint test sits.  The sorted periods are kernel arguments, read with scalar loads; `next_p`, the
-// next one, lives in an SGPR.  One scalar compare per Philox block decides between the block of simulate_path
-// (no checkpoint inside: the same instructions) and the slow form, which keeps the block's kDraws prefix values
-// and records those next_p names.  The path's last, partial block takes the slow form too.
+// LDS (walk_setup).  The draw tables sit at address 0 (a table elsewhere costs an address add per gather), the
+// kernel's u32 counters -- histograms, per-period counts -- behind them, zeroed here, and behind those, 8-byte
+// aligned, the waves' BlockPartial records.  The counters count paths of ONE workgroup: the host refuses a launch in
+// which a workgroup would get 2^32 or more (host_wave_walk_grid, smmc_capi.cpp).
 //
-// A record (checkpoint_record).  Two double sums by wave_sum_pair, min and -max by the same lane movements
-// (wave_min_pair), the four counters by ballots and scalar population counts, one LDS add per live lane into the
-// [checkpoint][bucket] u32 histogram behind the draw tables.  The wave's totals are then ADDED BY LANE ck to the
-// accumulators it holds in registers: lane k of a wave keeps checkpoint k (SMMC_MAX_CHECKPOINTS is the wave
-// size), ten registers per lane for any number of checkpoints, no LDS, and a fixed order -- a wave's chunks in
-// ascending order.  At the end the waves put their partials over the draw tables (no longer needed), thread k
-// folds the kW of checkpoint k in wave order and writes partials[k][blockIdx.x]; finalize_checkpoints_kernel folds
-// those in a fixed order, one workgroup per record.
+// Periods (walk_periods).  k.n_periods / kDraws whole Philox blocks, then the path's partial block, whose draws
+// past the last period are dropped; `prefetch(blk)` runs before a block's Philox rounds, `step(j, a, t)` after
+// them for draw j, multiplier a, period t (1-based; j is a constant after unrolling).  checkpoints_kernel has a
+// block loop of its own (a fast and a slow form per block) and takes the other pieces.
 //
-// u32 counters (lane accumulators, LDS buckets) count paths of ONE workgroup: the host refuses a launch in which
-// a workgroup would get 2^32 or more (smmc_capi.cpp).
-struct CheckpointArgs {
-  uint32_t n;                              // 1 .. SMMC_MAX_CHECKPOINTS
-  uint32_t periods[SMMC_MAX_CHECKPOINTS];  // strictly increasing, 1 .. n_periods
-};
-static_assert(SMMC_MAX_CHECKPOINTS <= 64, "lane k of a wave accumulates checkpoint k");
+// Records.  wave_record reduces the wave's 64 values to the wave-uniform sums, extremes and counts of one record
+// and makes the LDS bucket adds; where the totals go is the kernel's (checkpoint_record, wave_record_add).  At the
+// end fold_wave_partials leaves one BlockPartial per workgroup and record for finalize_kernel, and flush_counters
+// adds the non-zero LDS counters to the engine's accumulator with 64-bit atomics.
+constexpr uint32_t walk_waves(int mode) { return mode == SMMC_MODE_GAUSSIAN ? 8u : 4u; }  // per workgroup
 
-constexpr uint32_t checkpoint_waves(int mode) { return mode == SMMC_MODE_GAUSSIAN ? 8u : 4u; }  // per workgroup
-// LDS words in front of the histogram: the draw tables, later the waves' partials [kW][n]
-constexpr uint32_t checkpoint_front_words(uint32_t table_words, uint32_t waves, uint32_t n) {
-  const uint32_t part_words = waves * n * static_cast<uint32_t>(sizeof(BlockPartial) / 4u);
-  return ((table_words > part_words ? table_words : part_words) + 1u) & ~1u;
+struct WalkLds {  // wave-uniform
+  float *table;             // the draw tables, LDS address 0
+  uint32_t *counters;       // [counter_words], zero
+  BlockPartial *wave_part;  // behind the counters, 8-byte aligned; as many as the launch's LDS size provides
+  uint32_t lane, wave;
+};
+template <int kMode>
+__device__ __forceinline__ uint32_t walk_table_words(const KernelArgs &k) {
+  return is_table(kMode) ? k.table_len : bm_lds_words(kMode);
+}
+// Carves the dynamic LDS ([front_words, the draw tables first][counters][pad][partials]), stages the tables, zeroes
+// the counters; ends with a barrier.
+template <int kMode>
+__device__ __forceinline__ WalkLds walk_setup(const KernelArgs &k, unsigned char *lds_raw, uint32_t front_words, uint32_t counter_words) {
+  constexpr uint32_t kGroup = 64u * walk_waves(kMode);
+  WalkLds s;
+  s.table = reinterpret_cast<float *>(lds_raw);
+  s.counters = reinterpret_cast<uint32_t *>(lds_raw) + front_words;
+  s.wave_part = reinterpret_cast<BlockPartial *>(reinterpret_cast<uint32_t *>(lds_raw) + ((front_words + counter_words + 1u) & ~1u));
+  stage_tables<kMode>(k, s.table, kGroup);
+  for (uint32_t i = threadIdx.x; i < counter_words; i += kGroup) s.counters[i] = 0u;
+  __syncthreads();
+  s.lane = threadIdx.x & 63u;
+  s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return s;
 }
 
-struct CheckpointAcc {  // what lane k holds for checkpoint k
-  double sum, sumsq;
-  uint32_t count, below, under, over;
-  float min, max;
-};
+// body(i, active, path_lo, path_hi) for every chunk of this wave: path index i of the launch, whether it is below
+// n_paths, and the halves of the path's id.
+template <int kMode, typename Body>
+__device__ __forceinline__ void wave_chunks(const KernelArgs &k, const WalkLds &s, Body body) {
+  constexpr uint32_t kW = walk_waves(kMode);
+  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
+  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + s.wave; wc < n_wave_chunks;
+       wc += static_cast<uint64_t>(gridDim.x) * kW) {
+    const uint64_t i = wc * 64u + s.lane;
+    const uint64_t path = k.first_path + i;
+    body(i, i < k.n_paths, static_cast<uint32_t>(path), static_cast<uint32_t>(path >> 32));
+  }
+}
+
+template <int kMode, bool kDense, typename Prefetch, typename Step>
+__device__ __forceinline__ void walk_periods(const KernelArgs &k, const DrawRegs &dr, const float *lds_table, uint32_t path_lo,
+                                             uint32_t path_hi, Prefetch prefetch, Step step) {
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
+  for (uint32_t blk = 0; blk < full; ++blk) {
+    prefetch(blk);
+    float a[kDraws];
+    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+#pragma unroll
+    for (int j = 0; j < kDraws; ++j) step(j, a[j], blk * kDraws + j + 1u);
+  }
+  if (rem) {  // wave-uniform: the path's last, partial block
+    prefetch(full);
+    float a[kDraws];
+    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
+#pragma unroll
+    for (int j = 0; j < kDraws - 1; ++j)
+      if (static_cast<uint32_t>(j) < rem) step(j, a[j], full * kDraws + j + 1u);
+  }
+}
 
 template <int kShift>
 __device__ __forceinline__ float row_shl_min(float v) {  // v[i] = min(v[i], v[i + kShift]) inside each row of 16 lanes
@@ -1170,40 +1215,108 @@ __device__ __forceinline__ uint32_t ballot_count(bool pred) {
   return static_cast<uint32_t>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(pred)));
 }
 
-// The wave's values v (lanes with !active: none) go into checkpoint ck: the record values_stats forms of them.
-// Every lane of the wave must be enabled; ck is wave-uniform.
-__device__ __forceinline__ void checkpoint_record(const KernelArgs &k, uint32_t ck, float v, bool active, uint32_t lane,
-                                                  uint32_t *lds_hist, CheckpointAcc &acc) {
+// What the wave's values v (lanes with !active: none) add to a record, the record values_stats forms of them; every
+// member is wave-uniform.  Two double sums by wave_sum_pair, min and -max by the same lane movements
+// (wave_min_pair), the four counters by ballots and scalar population counts, one LDS add per lane inside
+// [lo, hi) into the n_bins buckets at lds_hist (n_bins 0: no buckets).  Some 70 VALU instructions.  Every lane of
+// the wave must be enabled.
+struct WaveRecord {
+  double sum, sumsq;
+  uint32_t count, below, under, over;
+  float min, max;
+};
+__device__ __forceinline__ WaveRecord wave_record(float v, bool active, float below_threshold, float lo, float hi, double inv,
+                                                  uint32_t n_bins, uint32_t *lds_hist) {
   const double dv = static_cast<double>(v);
   const double s12 = wave_sum_pair(active ? dv : 0.0, active ? dv * dv : 0.0);  // lane 0: sum, lane 32: sum of squares
   const bool ordered = active && v == v;  // min and max skip NaN, as fminf / fmaxf do
   const float mm = wave_min_pair(ordered ? v : __builtin_inff(), ordered ? -v : __builtin_inff());  // lane 0: min, lane 32: -max
-  const uint32_t n_count = ballot_count(active);
-  const uint32_t n_below = ballot_count(active && v < k.below_threshold);
-  uint32_t n_under = 0, n_over = 0;
-  if (k.n_bins) {  // uniform
-    const bool under = active && v < k.hist_lo;
-    const bool inside = active && !under && v < k.hist_hi;
-    n_under = ballot_count(under);
-    n_over = ballot_count(active && !under && !inside);  // >= hist_hi, or NaN
+  WaveRecord r;
+  r.count = ballot_count(active);
+  r.below = ballot_count(active && v < below_threshold);
+  r.under = r.over = 0;
+  if (n_bins) {  // uniform
+    const bool under = active && v < lo;
+    const bool inside = active && !under && v < hi;
+    r.under = ballot_count(under);
+    r.over = ballot_count(active && !under && !inside);  // >= hi, or NaN
     if (inside) {
-      int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
-      b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
-      atomicAdd(&lds_hist[ck * k.n_bins + static_cast<uint32_t>(b)], 1u);
+      int32_t b = static_cast<int32_t>((dv - static_cast<double>(lo)) * inv);
+      b = b < static_cast<int32_t>(n_bins) - 1 ? b : static_cast<int32_t>(n_bins) - 1;
+      atomicAdd(&lds_hist[b], 1u);
     }
   }
-  const double w_sum = read_lane(s12, 0), w_sumsq = read_lane(s12, 32);
-  const float w_min = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 0));
-  const float w_max = -__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 32));
+  r.sum = read_lane(s12, 0);
+  r.sumsq = read_lane(s12, 32);
+  r.min = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 0));
+  r.max = -__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 32));
+  return r;
+}
+
+// After the barrier that ends the walk: the kW partials of one record, in wave order, as the workgroup's.
+template <uint32_t kW>
+__device__ __forceinline__ void fold_wave_partials(const BlockPartial *wave_part, BlockPartial *out) {
+  BlockPartial t = wave_part[0];
+  for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[w]);
+  *out = t;
+}
+// After that barrier too (the LDS adds of all waves are complete): out[b] += counters[b] for the non-zero ones.
+template <uint32_t kGroup>
+__device__ __forceinline__ void flush_counters(const uint32_t *counters, uint32_t n, unsigned long long *out) {
+  for (uint32_t b = threadIdx.x; b < n; b += kGroup) {
+    const uint32_t c = counters[b];
+    if (c) atomicAdd(&out[b], static_cast<unsigned long long>(c));
+  }
+}
+
+// ---- checkpoints: the value distribution at chosen periods ---------------------------------------
+//
+// smmc_engine_simulate_checkpoints: the paths of paths_kernel, reduced not only at the end but after each of
+// c.n chosen periods -- one statistics record per checkpoint instead of a trajectory per path.  A wave walk (above);
+// HBM sees 4 B per path (d_final) or nothing.
+//
+// Where the checkpoint test sits.  The sorted periods are kernel arguments, read with scalar loads; `next_p`, the
+// next one, lives in an SGPR.  One scalar compare per Philox block decides between the block of simulate_path
+// (no checkpoint inside: the same instructions) and the slow form, which keeps the block's kDraws prefix values
+// and records those next_p names.  The path's last, partial block takes the slow form too.
+//
+// A record (checkpoint_record).  wave_record's totals, with the buckets in the [checkpoint][bucket] u32 histogram
+// behind the draw tables, are ADDED BY LANE ck to the accumulators it holds in registers: lane k of a wave keeps
+// checkpoint k (SMMC_MAX_CHECKPOINTS is the wave size), ten registers per lane for any number of checkpoints, no
+// LDS, and a fixed order -- a wave's chunks in ascending order.  At the end the waves put their partials over the
+// draw tables (no longer needed), thread k folds the kW of checkpoint k in wave order and writes
+// partials[k][blockIdx.x]; finalize_checkpoints_kernel folds those in a fixed order, one workgroup per record.
+struct CheckpointArgs {
+  uint32_t n;                              // 1 .. SMMC_MAX_CHECKPOINTS
+  uint32_t periods[SMMC_MAX_CHECKPOINTS];  // strictly increasing, 1 .. n_periods
+};
+static_assert(SMMC_MAX_CHECKPOINTS <= 64, "lane k of a wave accumulates checkpoint k");
+
+// LDS words in front of the histogram: the draw tables, later the waves' partials [kW][n]
+constexpr uint32_t checkpoint_front_words(uint32_t table_words, uint32_t waves, uint32_t n) {
+  const uint32_t part_words = waves * n * static_cast<uint32_t>(sizeof(BlockPartial) / 4u);
+  return ((table_words > part_words ? table_words : part_words) + 1u) & ~1u;
+}
+
+struct CheckpointAcc {  // what lane k holds for checkpoint k
+  double sum, sumsq;
+  uint32_t count, below, under, over;
+  float min, max;
+};
+
+// The wave's values v go into checkpoint ck (wave-uniform): lane ck adds the wave's totals to its registers.
+__device__ __forceinline__ void checkpoint_record(const KernelArgs &k, uint32_t ck, float v, bool active, uint32_t lane,
+                                                  uint32_t *lds_hist, CheckpointAcc &acc) {
+  const WaveRecord r = wave_record(v, active, k.below_threshold, k.hist_lo, k.hist_hi, k.hist_inv, k.n_bins, lds_hist + ck * k.n_bins);
   if (lane == ck) {
-    acc.sum += w_sum;
-    acc.sumsq += w_sumsq;
-    acc.count += n_count;
-    acc.below += n_below;
-    acc.under += n_under;
-    acc.over += n_over;
-    acc.min = fminf(acc.min, w_min);
-    acc.max = fmaxf(acc.max, w_max);
+    acc.sum += r.sum;
+    acc.sumsq += r.sumsq;
+    acc.count += r.count;
+    acc.below += r.below;
+    acc.under += r.under;
+    acc.over += r.over;
+    acc.min = fminf(acc.min, r.min);
+    acc.max = fmaxf(acc.max, r.max);
   }
 }
 
@@ -1219,24 +1332,17 @@ __device__ __forceinline__ float pick(const float (&t)[N], uint32_t j) {  // t[j
 }
 
 template <int kMode, bool kExactDiv, bool kDense>
-__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+__global__ __launch_bounds__(64 * walk_waves(kMode))
 void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
   static_assert(counter_v3(kMode), "counter stream v3 only");
-  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kW = walk_waves(kMode);
   constexpr uint32_t kGroup = 64u * kW;
   constexpr int kDraws = Draws<kMode, kDense>::value;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  float *lds_table = reinterpret_cast<float *>(lds_raw);
-  const uint32_t front_words = checkpoint_front_words(is_table(kMode) ? k.table_len : bm_lds_words(kMode), kW, c.n);
-  uint32_t *lds_hist = reinterpret_cast<uint32_t *>(lds_raw) + front_words;  // [c.n][k.n_bins]
   const uint32_t hist_words = c.n * k.n_bins;
-
-  stage_tables<kMode>(k, lds_table, kGroup);
-  for (uint32_t i = threadIdx.x; i < hist_words; i += kGroup) lds_hist[i] = 0u;
-  __syncthreads();
-
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const WalkLds s = walk_setup<kMode>(k, lds_raw, checkpoint_front_words(walk_table_words<kMode>(k), kW, c.n), hist_words);
+  uint32_t *lds_hist = s.counters;  // [c.n][k.n_bins]; s.wave_part is not used: this launch's LDS ends with the histogram
+  const uint32_t lane = s.lane, wave = s.wave;
   CheckpointAcc acc;
   acc.sum = acc.sumsq = 0.0;
   acc.count = acc.below = acc.under = acc.over = 0u;
@@ -1246,18 +1352,12 @@ void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
 
   const uint32_t n_blocks = (k.n_periods + kDraws - 1) / kDraws;  // >= 1: a checkpoint is a period >= 1
   const uint32_t last_j = k.n_periods - (n_blocks - 1) * kDraws - 1;  // the final value's place in the last block
-  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
-  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
-       wc += static_cast<uint64_t>(gridDim.x) * kW) {
-    const uint64_t i = wc * 64u + lane;
-    const bool active = i < k.n_paths;
-    const uint64_t path = k.first_path + i;
-    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
     float total = k.initial_capital;
     uint32_t ck = 0, next_p = c.periods[0];
     for (uint32_t blk = 0; blk < n_blocks; ++blk) {
       float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+      block_multipliers<kMode, kDense, true>(k, dr, s.table, path_lo, path_hi, blk, a);
       const uint32_t p_end = (blk + 1) * kDraws;  // periods done after this block
       if (next_p > p_end && p_end <= k.n_periods) {  // uniform: no checkpoint inside, not the partial block
 #pragma unroll
@@ -1278,7 +1378,7 @@ void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
       }
     }
     if (active && k.d_final) k.d_final[i] = total;
-  }
+  });
 
   __syncthreads();  // every wave is through with the draw tables, and its LDS adds are complete
   BlockPartial *part = reinterpret_cast<BlockPartial *>(lds_raw);  // [kW][c.n]
@@ -1300,10 +1400,7 @@ void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
     for (uint32_t w = 1; w < kW; ++w) partial_add(t, part[w * c.n + threadIdx.x]);
     k.partials[static_cast<size_t>(threadIdx.x) * gridDim.x + blockIdx.x] = t;
   }
-  for (uint32_t b = threadIdx.x; b < hist_words; b += kGroup) {
-    const uint32_t n = lds_hist[b];
-    if (n) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(n));
-  }
+  flush_counters<kGroup>(lds_hist, hist_words, k.d_hist);
 }
 
 // One workgroup per checkpoint: folds its bucket counts out of the accumulator (left zero, as finalize_kernel
@@ -1854,20 +1951,17 @@ __global__ __launch_bounds__(kBlock) void selftest_kernel(uint32_t lo, uint32_t 
 // its divide (either form: 0 * a is exact in both) stay 0; the mask, not the arithmetic, keeps it from coming back
 // when a contribution (amount < 0) would lift v' above the floor.
 //
-// Work split, as checkpoints_kernel: a WAVE owns a chunk of 64 consecutive paths and walks the chunks
-// wc = blockIdx.x * kW + wave, + gridDim.x * kW, ... without a barrier; every lane runs a path, also beyond
-// n_paths in the launch's last chunk (such a lane stores and counts nothing).
+// A wave walk (the skeleton above checkpoints_kernel): work split, LDS layout, the period walk and the epilogue
+// pieces are its.
 //
 // Schedule.  kVarying = false: amount and fraction are kernel arguments, two scalar registers, no loads.
 // kVarying = true: the period index is wave-uniform, so the entries of a Philox block are read with scalar loads
-// through the constant address space (one wide load per array and block, issued before the block's Philox rounds);
-// the host pads both arrays to whole blocks.  No per-lane global load in the loop.
+// through the constant address space (one wide load per array and block, the walk's prefetch: issued before the
+// block's Philox rounds); the host pads both arrays to whole blocks.  No per-lane global load in the loop.
 //
 // Outputs.  A lane adds its final value to per-lane statistics accumulators as paths_kernel does (one partial per
-// workgroup, folded by finalize_kernel), one LDS add into the final-value histogram and one into the
-// [n_periods + 1] depletion counters behind the draw tables; both are flushed with 64-bit integer atomics at the
-// end.  The u32 counters count paths of ONE workgroup: the host refuses a launch in which a workgroup would get
-// 2^32 or more (smmc_cashflow.cpp).
+// workgroup, folded by finalize_kernel; they stay per lane: a wave record per chunk would add the doubles in another
+// order), one LDS add into the final-value histogram and one into the [n_periods + 1] depletion counters.
 typedef const __attribute__((address_space(4))) float *const_float_ptr;  // scalar (uniform) loads
 
 template <bool kExactDiv>
@@ -1885,30 +1979,20 @@ __device__ __forceinline__ void cashflow_step(float a, float amount, float fract
 }
 
 template <int kMode, bool kExactDiv, bool kDense, bool kVarying>
-__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+__global__ __launch_bounds__(64 * walk_waves(kMode))
 void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
   static_assert(counter_v3(kMode), "counter stream v3 only");
-  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kW = walk_waves(kMode);
   constexpr uint32_t kGroup = 64u * kW;
   constexpr int kDraws = Draws<kMode, kDense>::value;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  float *lds_table = reinterpret_cast<float *>(lds_raw);
-  const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
-  uint32_t *lds_dep = reinterpret_cast<uint32_t *>(lds_raw) + table_words;  // [n_periods + 1]
-  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);                        // [n_bins]
-  const uint32_t counter_words = k.n_periods + 1u + k.n_bins;
-  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(reinterpret_cast<uint32_t *>(lds_raw) +
-                                                             ((table_words + counter_words + 1u) & ~1u));  // [kW]
-
-  stage_tables<kMode>(k, lds_table, kGroup);
-  for (uint32_t i = threadIdx.x; i < counter_words; i += kGroup) lds_dep[i] = 0u;
-  __syncthreads();
+  const WalkLds s = walk_setup<kMode>(k, lds_raw, walk_table_words<kMode>(k), k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
 
   const bool want_stats = k.partials != nullptr;  // all uniform
   const bool want_hist = want_stats && k.n_bins != 0;
   const bool want_dep = c.d_depleted != nullptr;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double sum = 0.0, sumsq = 0.0;
   uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
   float vmin = __builtin_inff(), vmax = -__builtin_inff();
@@ -1916,44 +2000,21 @@ void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
   const const_float_ptr amounts = (const_float_ptr)(c.schedule);
   const const_float_ptr fractions = amounts + c.stride;
 
-  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
-  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
-  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
-       wc += static_cast<uint64_t>(gridDim.x) * kW) {
-    const uint64_t i = wc * 64u + lane;
-    const bool active = i < k.n_paths;
-    const uint64_t path = k.first_path + i;
-    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
     float v = k.initial_capital, paid = 0.0f;
     uint32_t ruin = 0u;
     bool alive = true;
-    for (uint32_t blk = 0; blk < full; ++blk) {
-      float am[kDraws], fr[kDraws];
+    float am[kDraws], fr[kDraws];
+    walk_periods<kMode, kDense>(
+        k, dr, s.table, path_lo, path_hi,
+        [&](uint32_t blk) {  // the block's schedule entries (padded to whole blocks)
 #pragma unroll
-      for (int j = 0; j < kDraws; ++j) {
-        am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
-        fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
-      }
-      float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
-#pragma unroll
-      for (int j = 0; j < kDraws; ++j)
-        cashflow_step<kExactDiv>(a[j], am[j], fr[j], c.floor, blk * kDraws + j + 1u, v, paid, ruin, alive);
-    }
-    if (rem) {  // wave-uniform: the path's last, partial block (the schedule is padded to whole blocks)
-      float am[kDraws], fr[kDraws];
-#pragma unroll
-      for (int j = 0; j < kDraws; ++j) {
-        am[j] = kVarying ? amounts[full * kDraws + j] : c.amount;
-        fr[j] = kVarying ? fractions[full * kDraws + j] : c.fraction;
-      }
-      float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
-#pragma unroll
-      for (int j = 0; j < kDraws - 1; ++j)
-        if (static_cast<uint32_t>(j) < rem)
-          cashflow_step<kExactDiv>(a[j], am[j], fr[j], c.floor, full * kDraws + j + 1u, v, paid, ruin, alive);
-    }
+          for (int j = 0; j < kDraws; ++j) {
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+        },
+        [&](int j, float a, uint32_t t) { cashflow_step<kExactDiv>(a, am[j], fr[j], c.floor, t, v, paid, ruin, alive); });
     if (active) {
       if (k.d_final) k.d_final[i] = v;
       if (c.d_paid) c.d_paid[i] = paid;
@@ -1980,7 +2041,7 @@ void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
         }
       }
     }
-  }
+  });
 
   if (want_stats) {
     BlockPartial p;
@@ -1992,26 +2053,12 @@ void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
     p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
     p.min = wave_min(vmin);
     p.max = wave_max(vmax);
-    if (lane == 0) wave_part[wave] = p;
+    if (s.lane == 0) s.wave_part[s.wave] = p;
   }
   __syncthreads();  // the waves' partials are written and their LDS adds complete
-  if (want_stats && threadIdx.x == 0) {
-    BlockPartial t = wave_part[0];
-    for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[w]);
-    k.partials[blockIdx.x] = t;
-  }
-  if (want_dep) {
-    for (uint32_t b = threadIdx.x; b <= k.n_periods; b += kGroup) {
-      const uint32_t n = lds_dep[b];
-      if (n) atomicAdd(&c.d_depleted[b], static_cast<unsigned long long>(n));
-    }
-  }
-  if (want_hist) {
-    for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
-      const uint32_t n = lds_hist[b];
-      if (n) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(n));
-    }
-  }
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
 // d_out[i] = acc[i], and acc is left zero for the next launch (as finalize_kernel leaves the bucket accumulator).
@@ -2040,12 +2087,11 @@ __global__ __launch_bounds__(kBlock) void finalize_depleted_kernel(unsigned long
 // hit" flags are lane masks in scalar register pairs, combined with the compares on the scalar unit, as
 // cashflow_step's `alive`; the period index is wave-uniform; control flow stays wave-uniform.
 //
-// Work split, tables, draws and the partial last block: cashflow_kernel's.  Outputs: up to eight coalesced 256-byte
-// stores per wave chunk; TWO records (final value, drawdown), each reduced over the wave per chunk as
-// checkpoint_record does and added to the wave's partial in LDS (wave_record_add), left as one partial per workgroup
-// (k.partials, x.dd_partials; finalize_kernel folds each); one LDS add per lane into each of two histograms and of two [n_periods + 1] first-passage counter arrays behind the
-// draw tables, flushed with 64-bit integer atomics.  u32 counters count paths of ONE workgroup: the host refuses a
-// launch in which a workgroup would get 2^32 or more (smmc_excursions.cpp).
+// A wave walk (the skeleton above checkpoints_kernel).  Outputs: up to eight coalesced 256-byte stores per wave chunk;
+// TWO records (final value, drawdown), each reduced over the wave per chunk (wave_record) and added to the wave's
+// partial in LDS (wave_record_add), left as one partial per workgroup (k.partials, x.dd_partials; finalize_kernel
+// folds each); one LDS add per lane into each of two histograms and of two [n_periods + 1] first-passage counter
+// arrays.
 struct ExcursionLane {
   float peak, low, dd_peak, dd_low;
   uint32_t dd_period, run, longest, first_below, first_reach;
@@ -2071,144 +2117,86 @@ __device__ __forceinline__ void excursion_step(float a, float lower, float targe
   no_reach = no_reach && !hit_reach;
 }
 
-// The wave's values v (lanes with !active: none) are added to the wave's own partial record in LDS: the sums,
-// extremes and counts of checkpoint_record, by the same lane movements, then one read-modify-write by lane 0.  Two
-// records' accumulators in registers (20 per lane) would cost the Gaussian kernel its eighth wave per SIMD; here they
-// cost none, and some 70 VALU instructions per wave chunk and record.  The order is fixed: a wave's chunks ascending.
-// Every lane of the wave must be enabled.
+// The wave's values v are added to the wave's own partial record in LDS: wave_record's totals, then one
+// read-modify-write by lane 0.  Two records' accumulators in registers (20 per lane) would cost the Gaussian kernel
+// its eighth wave per SIMD; here they cost none.  The order is fixed: a wave's chunks ascending.
 __device__ __forceinline__ void wave_record_add(BlockPartial *part, float v, bool active, uint32_t lane, float below_threshold,
                                                 float lo, float hi, double inv, uint32_t n_bins, uint32_t *lds_hist) {
-  const double dv = static_cast<double>(v);
-  const double s12 = wave_sum_pair(active ? dv : 0.0, active ? dv * dv : 0.0);  // lane 0: sum, lane 32: sum of squares
-  const bool ordered = active && v == v;  // min and max skip NaN, as fminf / fmaxf do
-  const float mm = wave_min_pair(ordered ? v : __builtin_inff(), ordered ? -v : __builtin_inff());  // lane 0: min, lane 32: -max
-  const uint32_t n_count = ballot_count(active);
-  const uint32_t n_below = ballot_count(active && v < below_threshold);
-  uint32_t n_under = 0, n_over = 0;
-  if (n_bins) {  // uniform
-    const bool under = active && v < lo;
-    const bool inside = active && !under && v < hi;
-    n_under = ballot_count(under);
-    n_over = ballot_count(active && !under && !inside);  // >= hi, or NaN
-    if (inside) {
-      int32_t b = static_cast<int32_t>((dv - static_cast<double>(lo)) * inv);
-      b = b < static_cast<int32_t>(n_bins) - 1 ? b : static_cast<int32_t>(n_bins) - 1;
-      atomicAdd(&lds_hist[b], 1u);
-    }
-  }
-  const double w_sum = read_lane(s12, 0), w_sumsq = read_lane(s12, 32);
-  const float w_min = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 0));
-  const float w_max = -__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mm), 32));
+  const WaveRecord r = wave_record(v, active, below_threshold, lo, hi, inv, n_bins, lds_hist);
   if (lane == 0) {
     BlockPartial t = *part;
-    t.sum += w_sum;
-    t.sumsq += w_sumsq;
-    t.count += n_count;
-    t.below += n_below;
-    t.underflow += n_under;
-    t.overflow += n_over;
-    t.min = fminf(t.min, w_min);
-    t.max = fmaxf(t.max, w_max);
+    t.sum += r.sum;
+    t.sumsq += r.sumsq;
+    t.count += r.count;
+    t.below += r.below;
+    t.underflow += r.under;
+    t.overflow += r.over;
+    t.min = fminf(t.min, r.min);
+    t.max = fmaxf(t.max, r.max);
     *part = t;
   }
 }
 
 template <int kMode, bool kExactDiv, bool kDense>
-__global__ __launch_bounds__(64 * checkpoint_waves(kMode))
+__global__ __launch_bounds__(64 * walk_waves(kMode))
 void excursions_kernel(const KernelArgs k, const ExcursionArgs x) {
   static_assert(counter_v3(kMode), "counter stream v3 only");
-  constexpr uint32_t kW = checkpoint_waves(kMode);
+  constexpr uint32_t kW = walk_waves(kMode);
   constexpr uint32_t kGroup = 64u * kW;
-  constexpr int kDraws = Draws<kMode, kDense>::value;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  float *lds_table = reinterpret_cast<float *>(lds_raw);
-  const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
   const uint32_t n_at = k.n_periods + 1u;
-  uint32_t *lds_below_at = reinterpret_cast<uint32_t *>(lds_raw) + table_words;  // [n_periods + 1]
-  uint32_t *lds_reach_at = lds_below_at + n_at;                                  // [n_periods + 1]
-  uint32_t *lds_hist = lds_reach_at + n_at;                                      // [n_bins], the final values
-  uint32_t *lds_dd_hist = lds_hist + k.n_bins;                                   // [n_bins], the drawdowns
-  const uint32_t counter_words = 2u * n_at + 2u * k.n_bins;
-  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(reinterpret_cast<uint32_t *>(lds_raw) +
-                                                             ((table_words + counter_words + 1u) & ~1u));  // [2][kW]
-
-  stage_tables<kMode>(k, lds_table, kGroup);
-  for (uint32_t i = threadIdx.x; i < counter_words; i += kGroup) lds_below_at[i] = 0u;
-  __syncthreads();
+  const WalkLds s = walk_setup<kMode>(k, lds_raw, walk_table_words<kMode>(k), 2u * n_at + 2u * k.n_bins);  // wave_part: [2][kW]
+  uint32_t *lds_below_at = s.counters;           // [n_periods + 1]
+  uint32_t *lds_reach_at = lds_below_at + n_at;  // [n_periods + 1]
+  uint32_t *lds_hist = lds_reach_at + n_at;      // [n_bins], the final values
+  uint32_t *lds_dd_hist = lds_hist + k.n_bins;   // [n_bins], the drawdowns
 
   const bool want_stats = k.partials != nullptr;  // all uniform
   const bool want_dd_stats = x.dd_partials != nullptr;
   const bool want_hist = want_stats && k.n_bins != 0;
   const bool want_dd_hist = want_dd_stats && k.n_bins != 0;
   const bool want_below_at = x.d_below_at != nullptr, want_reach_at = x.d_reach_at != nullptr;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  BlockPartial *part = wave_part + wave, *dd_part = wave_part + kW + wave;  // this wave's own, until the barrier
+  const uint32_t lane = s.lane;
+  BlockPartial *part = s.wave_part + s.wave, *dd_part = s.wave_part + kW + s.wave;  // this wave's own, until the barrier
   if (lane == 0) {
     partial_identity(*part);
     partial_identity(*dd_part);
   }
   const DrawRegs dr = make_draw_regs(k);
 
-  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
-  const uint64_t n_wave_chunks = (k.n_paths + 63u) / 64u;
-  for (uint64_t wc = static_cast<uint64_t>(blockIdx.x) * kW + wave; wc < n_wave_chunks;
-       wc += static_cast<uint64_t>(gridDim.x) * kW) {
-    const uint64_t i = wc * 64u + lane;
-    const bool active = i < k.n_paths;
-    const uint64_t path = k.first_path + i;
-    const uint32_t path_lo = static_cast<uint32_t>(path), path_hi = static_cast<uint32_t>(path >> 32);
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
     float v = k.initial_capital;
-    ExcursionLane s = {v, v, v, v, 0u, 0u, 0u, 0u, 0u};
+    ExcursionLane e = {v, v, v, v, 0u, 0u, 0u, 0u, 0u};
     bool no_below = true, no_reach = true;
-    for (uint32_t blk = 0; blk < full; ++blk) {
-      float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
-#pragma unroll
-      for (int j = 0; j < kDraws; ++j)
-        excursion_step<kExactDiv>(a[j], x.lower, x.target, blk * kDraws + j + 1u, v, s, no_below, no_reach);
-    }
-    if (rem) {  // wave-uniform: the path's last, partial block
-      float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
-#pragma unroll
-      for (int j = 0; j < kDraws - 1; ++j)
-        if (static_cast<uint32_t>(j) < rem)
-          excursion_step<kExactDiv>(a[j], x.lower, x.target, full * kDraws + j + 1u, v, s, no_below, no_reach);
-    }
-    const float drawdown = __fdiv_rn(__fsub_rn(s.dd_peak, s.dd_low), s.dd_peak);  // the path's one IEEE divide
+    walk_periods<kMode, kDense>(
+        k, dr, s.table, path_lo, path_hi, [](uint32_t) {},
+        [&](int, float a, uint32_t t) { excursion_step<kExactDiv>(a, x.lower, x.target, t, v, e, no_below, no_reach); });
+    const float drawdown = __fdiv_rn(__fsub_rn(e.dd_peak, e.dd_low), e.dd_peak);  // the path's one IEEE divide
     if (active) {
       if (k.d_final) k.d_final[i] = v;
-      if (x.d_peak) x.d_peak[i] = s.peak;
-      if (x.d_low) x.d_low[i] = s.low;
+      if (x.d_peak) x.d_peak[i] = e.peak;
+      if (x.d_low) x.d_low[i] = e.low;
       if (x.d_drawdown) x.d_drawdown[i] = drawdown;
-      if (x.d_drawdown_period) x.d_drawdown_period[i] = s.dd_period;
-      if (x.d_underwater) x.d_underwater[i] = s.longest;
-      if (x.d_first_below) x.d_first_below[i] = s.first_below;
-      if (x.d_first_reach) x.d_first_reach[i] = s.first_reach;
-      if (want_below_at) atomicAdd(&lds_below_at[s.first_below], 1u);  // first_* <= n_periods
-      if (want_reach_at) atomicAdd(&lds_reach_at[s.first_reach], 1u);
+      if (x.d_drawdown_period) x.d_drawdown_period[i] = e.dd_period;
+      if (x.d_underwater) x.d_underwater[i] = e.longest;
+      if (x.d_first_below) x.d_first_below[i] = e.first_below;
+      if (x.d_first_reach) x.d_first_reach[i] = e.first_reach;
+      if (want_below_at) atomicAdd(&lds_below_at[e.first_below], 1u);  // first_* <= n_periods
+      if (want_reach_at) atomicAdd(&lds_reach_at[e.first_reach], 1u);
     }
     if (want_stats)  // uniform: the whole wave
       wave_record_add(part, v, active, lane, k.below_threshold, k.hist_lo, k.hist_hi, k.hist_inv, want_hist ? k.n_bins : 0u, lds_hist);
     if (want_dd_stats)
       wave_record_add(dd_part, drawdown, active, lane, x.drawdown_threshold, 0.0f, 1.0f, x.dd_hist_inv, want_dd_hist ? k.n_bins : 0u,
                       lds_dd_hist);
-  }
+  });
 
   __syncthreads();  // the waves' partials are written and their LDS adds complete
   if (threadIdx.x == 0) {
-    if (want_stats) {
-      BlockPartial t = wave_part[0];
-      for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[w]);
-      k.partials[blockIdx.x] = t;
-    }
-    if (want_dd_stats) {
-      BlockPartial t = wave_part[kW];
-      for (uint32_t w = 1; w < kW; ++w) partial_add(t, wave_part[kW + w]);
-      x.dd_partials[blockIdx.x] = t;
-    }
+    if (want_stats) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+    if (want_dd_stats) fold_wave_partials<kW>(s.wave_part + kW, &x.dd_partials[blockIdx.x]);
   }
+  // two arrays share a loop, as before the kernels shared a skeleton (flush_counters takes one array)
   for (uint32_t b = threadIdx.x; b < n_at; b += kGroup) {
     const uint32_t nb = lds_below_at[b], nr = lds_reach_at[b];
     if (want_below_at && nb) atomicAdd(&x.d_below_at[b], static_cast<unsigned long long>(nb));
@@ -2437,31 +2425,49 @@ hipError_t launch_keepdata(const KernelArgs &a, bool exact_div, int tile, int wa
                                      : launch_keepdata_mode<SMMC_MODE_TABLE, false>(a, exact_div, tile, waves, grid, stream);
 }
 
-// ---- checkpoints ----
+// ---- the wave-walk kernels: checkpoints, cash flows, excursions ----
 
-uint32_t checkpoints_group_paths(int32_t mode) { return 64u * checkpoint_waves(mode == SMMC_MODE_TABLE ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN); }
+static_assert(wave_walk_group_paths(SMMC_MODE_TABLE) == 64u * walk_waves(SMMC_MODE_TABLE) &&
+                  wave_walk_group_paths(SMMC_MODE_GAUSSIAN) == 64u * walk_waves(SMMC_MODE_GAUSSIAN),
+              "smmc_internal.h states the workgroup sizes the kernels are compiled for");
+
+// walk_setup's layout: [draw tables][counter_words u32 counters][pad to 8 bytes][partials_per_wave BlockPartial per wave]
+static size_t wave_walk_lds_bytes(int32_t mode, uint32_t table_len, size_t counter_words, uint32_t partials_per_wave) {
+  const bool table = mode == SMMC_MODE_TABLE;
+  const size_t words = (static_cast<size_t>(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN)) + counter_words + 1u) & ~static_cast<size_t>(1);
+  return words * 4u + partials_per_wave * static_cast<size_t>(wave_walk_group_paths(mode) / 64u) * sizeof(BlockPartial);
+}
+
+// One ladder for the three: Gaussian | dense table | four-draw table, times exact | fast divide.  `Family` names a
+// kernel's instantiations: Family::get<kMode, kExactDiv, kDense>(x) is the one to launch for the arguments x.
+template <typename Args>
+using WalkKernel = void (*)(const KernelArgs, const Args);
+template <typename Family, bool kExactDiv, typename Args>
+static WalkKernel<Args> wave_walk_kernel(const KernelArgs &a, const Args &x) {
+  if (a.mode != SMMC_MODE_TABLE) return Family::template get<SMMC_MODE_GAUSSIAN, kExactDiv, false>(x);
+  return table_is_dense(a.table_len) ? Family::template get<SMMC_MODE_TABLE, kExactDiv, true>(x)
+                                     : Family::template get<SMMC_MODE_TABLE, kExactDiv, false>(x);
+}
+template <typename Family, typename Args>
+static hipError_t launch_wave_walk(const KernelArgs &a, const Args &x, bool exact_div, uint32_t grid, size_t lds, hipStream_t stream) {
+  const WalkKernel<Args> kernel = exact_div ? wave_walk_kernel<Family, true>(a, x) : wave_walk_kernel<Family, false>(a, x);
+  const hipError_t err = allow_lds(kernel, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(a.mode)), lds, stream, a, x);
+  return hipGetLastError();
+}
 
 size_t checkpoints_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_checkpoints, uint32_t n_bins) {
   const bool table = mode == SMMC_MODE_TABLE;
   const uint32_t front = checkpoint_front_words(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN),
-                                                checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN), n_checkpoints);
+                                                walk_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN), n_checkpoints);
   return (static_cast<size_t>(front) + static_cast<size_t>(n_checkpoints) * n_bins) * 4u;
 }
 
-template <int kMode, bool kDense>
-static hipError_t launch_checkpoints_mode(const KernelArgs &a, const CheckpointArgs &c, bool exact_div, uint32_t grid, size_t lds,
-                                          hipStream_t stream) {
-  const dim3 block(64u * checkpoint_waves(kMode));
-  hipError_t err = exact_div ? allow_lds(checkpoints_kernel<kMode, true, kDense>, lds)
-                             : allow_lds(checkpoints_kernel<kMode, false, kDense>, lds);
-  if (err != hipSuccess) return err;
-  if (exact_div)
-    hipLaunchKernelGGL((checkpoints_kernel<kMode, true, kDense>), dim3(grid), block, lds, stream, a, c);
-  else
-    hipLaunchKernelGGL((checkpoints_kernel<kMode, false, kDense>), dim3(grid), block, lds, stream, a, c);
-  return hipGetLastError();
-}
-
+struct CheckpointsFamily {
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<CheckpointArgs> get(const CheckpointArgs &) { return checkpoints_kernel<kMode, kExactDiv, kDense>; }
+};
 // a.partials: n_checkpoints x grid entries ([checkpoint][workgroup]); a.d_hist: n_checkpoints x a.n_bins zeroed counters
 hipError_t launch_checkpoints(const KernelArgs &a, const uint32_t *periods, uint32_t n_checkpoints, bool exact_div, uint32_t grid,
                               hipStream_t stream) {
@@ -2469,10 +2475,7 @@ hipError_t launch_checkpoints(const KernelArgs &a, const uint32_t *periods, uint
   CheckpointArgs c;
   c.n = n_checkpoints;
   for (uint32_t i = 0; i < SMMC_MAX_CHECKPOINTS; ++i) c.periods[i] = i < n_checkpoints ? periods[i] : 0xffffffffu;
-  const size_t lds = checkpoints_lds_bytes(a.mode, a.table_len, n_checkpoints, a.n_bins);
-  if (a.mode != SMMC_MODE_TABLE) return launch_checkpoints_mode<SMMC_MODE_GAUSSIAN, false>(a, c, exact_div, grid, lds, stream);
-  return table_is_dense(a.table_len) ? launch_checkpoints_mode<SMMC_MODE_TABLE, true>(a, c, exact_div, grid, lds, stream)
-                                     : launch_checkpoints_mode<SMMC_MODE_TABLE, false>(a, c, exact_div, grid, lds, stream);
+  return launch_wave_walk<CheckpointsFamily>(a, c, exact_div, grid, checkpoints_lds_bytes(a.mode, a.table_len, n_checkpoints, a.n_bins), stream);
 }
 
 hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_partials, uint32_t n_checkpoints, void *d_records,
@@ -2484,43 +2487,21 @@ hipError_t launch_finalize_checkpoints(const BlockPartial *partials, uint32_t n_
 
 // ---- cash flows ----
 
-uint32_t cashflow_group_paths(int32_t mode) { return checkpoints_group_paths(mode); }
-
 size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
-  // [draw tables][depletion counters n_periods + 1][histogram][pad to 8 bytes][one BlockPartial per wave]
-  const bool table = mode == SMMC_MODE_TABLE;
-  const size_t words = (static_cast<size_t>(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN)) + n_periods + 1u + n_bins + 1u) &
-                       ~static_cast<size_t>(1);
-  return words * 4u + checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN) * sizeof(BlockPartial);
+  // counters: depletion [n_periods + 1], histogram [n_bins]; one partial per wave
+  return wave_walk_lds_bytes(mode, table_len, static_cast<size_t>(n_periods) + 1u + n_bins, 1u);
 }
 
-template <int kMode, bool kDense, bool kExactDiv>
-static hipError_t launch_cashflow_variant(const KernelArgs &a, const CashflowArgs &c, uint32_t grid, size_t lds, hipStream_t stream) {
-  const dim3 block(64u * checkpoint_waves(kMode));
-  hipError_t err = c.schedule ? allow_lds(cashflow_kernel<kMode, kExactDiv, kDense, true>, lds)
-                              : allow_lds(cashflow_kernel<kMode, kExactDiv, kDense, false>, lds);
-  if (err != hipSuccess) return err;
-  if (c.schedule)
-    hipLaunchKernelGGL((cashflow_kernel<kMode, kExactDiv, kDense, true>), dim3(grid), block, lds, stream, a, c);
-  else
-    hipLaunchKernelGGL((cashflow_kernel<kMode, kExactDiv, kDense, false>), dim3(grid), block, lds, stream, a, c);
-  return hipGetLastError();
-}
-
-template <int kMode, bool kDense>
-static hipError_t launch_cashflow_mode(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, size_t lds,
-                                       hipStream_t stream) {
-  return exact_div ? launch_cashflow_variant<kMode, kDense, true>(a, c, grid, lds, stream)
-                   : launch_cashflow_variant<kMode, kDense, false>(a, c, grid, lds, stream);
-}
-
+struct CashflowFamily {
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<CashflowArgs> get(const CashflowArgs &c) {
+    return c.schedule ? cashflow_kernel<kMode, kExactDiv, kDense, true> : cashflow_kernel<kMode, kExactDiv, kDense, false>;
+  }
+};
 hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exact_div, uint32_t grid, hipStream_t stream) {
   if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
   if (c.schedule && (c.stride % 8u != 0u || c.stride < a.n_periods)) return hipErrorInvalidValue;
-  const size_t lds = cashflow_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
-  if (a.mode != SMMC_MODE_TABLE) return launch_cashflow_mode<SMMC_MODE_GAUSSIAN, false>(a, c, exact_div, grid, lds, stream);
-  return table_is_dense(a.table_len) ? launch_cashflow_mode<SMMC_MODE_TABLE, true>(a, c, exact_div, grid, lds, stream)
-                                     : launch_cashflow_mode<SMMC_MODE_TABLE, false>(a, c, exact_div, grid, lds, stream);
+  return launch_wave_walk<CashflowFamily>(a, c, exact_div, grid, cashflow_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins), stream);
 }
 
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream) {
@@ -2565,37 +2546,19 @@ hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int
 
 // ---- excursions ----
 
-uint32_t excursions_group_paths(int32_t mode) { return checkpoints_group_paths(mode); }
-
 size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
-  // [draw tables][first_below counters n_periods + 1][first_reach counters n_periods + 1][histogram of the final
-  // values][histogram of the drawdowns][pad to 8 bytes][two BlockPartial per wave]
-  const bool table = mode == SMMC_MODE_TABLE;
-  const size_t words = (static_cast<size_t>(table ? table_len : bm_lds_words(SMMC_MODE_GAUSSIAN)) + 2u * (static_cast<size_t>(n_periods) + 1u) +
-                        2u * static_cast<size_t>(n_bins) + 1u) & ~static_cast<size_t>(1);
-  return words * 4u + 2u * checkpoint_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN) * sizeof(BlockPartial);
+  // counters: first_below and first_reach [n_periods + 1] each, the histograms of the final values and of the
+  // drawdowns [n_bins] each; two partials per wave
+  return wave_walk_lds_bytes(mode, table_len, 2u * (static_cast<size_t>(n_periods) + 1u) + 2u * static_cast<size_t>(n_bins), 2u);
 }
 
-template <int kMode, bool kDense>
-static hipError_t launch_excursions_mode(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, size_t lds,
-                                         hipStream_t stream) {
-  const dim3 block(64u * checkpoint_waves(kMode));
-  hipError_t err = exact_div ? allow_lds(excursions_kernel<kMode, true, kDense>, lds)
-                             : allow_lds(excursions_kernel<kMode, false, kDense>, lds);
-  if (err != hipSuccess) return err;
-  if (exact_div)
-    hipLaunchKernelGGL((excursions_kernel<kMode, true, kDense>), dim3(grid), block, lds, stream, a, x);
-  else
-    hipLaunchKernelGGL((excursions_kernel<kMode, false, kDense>), dim3(grid), block, lds, stream, a, x);
-  return hipGetLastError();
-}
-
+struct ExcursionsFamily {
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<ExcursionArgs> get(const ExcursionArgs &) { return excursions_kernel<kMode, kExactDiv, kDense>; }
+};
 hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
   if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_EXCURSION_PERIODS) return hipErrorInvalidValue;
-  const size_t lds = excursions_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins);
-  if (a.mode != SMMC_MODE_TABLE) return launch_excursions_mode<SMMC_MODE_GAUSSIAN, false>(a, x, exact_div, grid, lds, stream);
-  return table_is_dense(a.table_len) ? launch_excursions_mode<SMMC_MODE_TABLE, true>(a, x, exact_div, grid, lds, stream)
-                                     : launch_excursions_mode<SMMC_MODE_TABLE, false>(a, x, exact_div, grid, lds, stream);
+  return launch_wave_walk<ExcursionsFamily>(a, x, exact_div, grid, excursions_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins), stream);
 }
 
 }  // namespace smmc

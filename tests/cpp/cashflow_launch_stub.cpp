@@ -6,7 +6,6 @@
 namespace smmc {
 hipError_t launch_cashflow(const KernelArgs &, const CashflowArgs &, bool, uint32_t, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_finalize_depleted(unsigned long long *, uint32_t, unsigned long long *, hipStream_t) { return hipErrorNoDevice; }
-uint32_t cashflow_group_paths(int32_t mode) { return mode == SMMC_MODE_TABLE ? 256u : 512u; }
 size_t cashflow_lds_bytes(int32_t, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
   return (static_cast<size_t>(table_len) + n_periods + 1u + n_bins) * 4u;
 }

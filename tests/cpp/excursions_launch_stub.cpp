@@ -6,7 +6,6 @@
 
 namespace smmc {
 hipError_t launch_excursions(const KernelArgs &, const ExcursionArgs &, bool, uint32_t, hipStream_t) { return hipErrorNoDevice; }
-uint32_t excursions_group_paths(int32_t mode) { return mode == SMMC_MODE_TABLE ? 256u : 512u; }
 size_t excursions_lds_bytes(int32_t, uint32_t table_len, uint32_t n_periods, uint32_t n_bins) {
   return (static_cast<size_t>(table_len) + 2u * (static_cast<size_t>(n_periods) + 1u) + 2u * static_cast<size_t>(n_bins)) * 4u;
 }
