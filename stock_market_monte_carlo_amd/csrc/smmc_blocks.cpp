@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "smmc_host.h"
 #include "smmc_internal.h"
 
 namespace {
@@ -74,13 +75,13 @@ int enqueue_blocks(smmc_engine *e, const smmc_sim *s, const smmc_blocks *b, floa
   Plan p = {false, 0};
   int rc = grid ? plan(view, a, d_stats ? s->n_bins : 0u, &p) : SMMC_OK;  // nothing is launched for n_paths == 0
   if (rc) return rc;
-  unsigned long long *acc = nullptr;
+  smmc::ZeroLease lease;
   if (d_stats) {  // no memset: finalize_kernel writes the whole record and leaves the accumulator zero again
     a.partials = view.d_partials;
     if (s->n_bins) {
-      rc = smmc::engine_acc_begin(e, &acc);
+      rc = smmc::engine_acc_lease(e, &lease);
       if (rc) return rc;
-      a.d_hist = acc;
+      a.d_hist = lease.acc();
     }
   }
   a.clock_probe = view.clock_probe;
@@ -90,9 +91,9 @@ int enqueue_blocks(smmc_engine *e, const smmc_sim *s, const smmc_blocks *b, floa
     if (rc) return rc;
   }
   if (d_stats) {
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, acc,
+    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, lease.acc(),
                                    s->n_bins ? 1u : 0u));
-    if (acc) smmc::engine_acc_clean(e);
+    lease.finalize_queued();
   }
   return SMMC_OK;
 }

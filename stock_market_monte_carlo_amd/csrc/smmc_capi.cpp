@@ -79,6 +79,15 @@ struct PhaseLog {
 
 using smmc::DeviceGuard;  // smmc_internal.h
 
+// A range-checked integer knob: *value is left alone when the variable is unset or outside [lo, hi].  Every knob
+// is read where it is used -- tests and tools change them between calls of one process.
+template <typename T>
+void env_long(const char *name, long lo, long hi, T *value) {
+  const char *env = std::getenv(name);
+  const long v = env ? std::strtol(env, nullptr, 10) : lo - 1;
+  if (env && v >= lo && v <= hi) *value = static_cast<T>(v);
+}
+
 // Workgroups launched per CU.  About 6 are resident (SGPR-limited); the rest queue and
 // are handed out as others finish, which evens out CU/XCD speed differences: measured
 // 1e8 x 360 table paths: 13.1 ms at 6 per CU, 12.6 at 8, 11.7 at 16, 11.1 at 64..256.
@@ -102,52 +111,43 @@ struct smmc_engine {
   uint32_t keepdata_blocks_per_cu = 0;  // 0: as many keepdata workgroups as are resident
   size_t max_lds = 0;
 
-  float *d_table = nullptr;  // 100.0f + r
+  smmc::DeviceBuffer<float> d_table;  // 100.0f + r
   uint32_t table_len = 0;
   float table_min_a = 0.f, table_max_a = 0.f;
   bool table_finite = false;
 
-  float *d_bm_tables = nullptr;  // Box-Muller radius + trig tables (Gaussian mode)
-  smmc::BlockPartial *d_partials = nullptr;  // max_grid entries
-  unsigned long long *d_clock = nullptr;     // timing: [shader clocks, 100 MHz ticks] summed over paths_kernel's workgroups
+  // Device memory is owned by DeviceBuffer members (smmc_host.h): smmc_engine_destroy frees them by destroying the
+  // engine, with the device current and before the owned stream goes.
+  smmc::DeviceBuffer<float> d_bm_tables;  // Box-Muller radius + trig tables (Gaussian mode)
+  smmc::DeviceBuffer<smmc::BlockPartial> d_partials;  // max_grid entries
+  smmc::DeviceBuffer<unsigned long long> d_clock;     // timing: [shader clocks, 100 MHz ticks] summed over paths_kernel's workgroups
 
-  // simulate_to_host staging
-  float *d_stage[2] = {nullptr, nullptr};
-  uint64_t stage_paths = 0;
-  float *d_stage_cs[2] = {nullptr, nullptr};  // chunk means then variances
-  uint64_t stage_cs = 0;
-  void *d_stage_stats = nullptr;
-  size_t stage_stats_bytes = 0;
+  // simulate_to_host staging, grown on demand
+  smmc::DeviceBuffer<float> d_stage[2];
+  smmc::DeviceBuffer<float> d_stage_cs[2];  // chunk means then variances
+  smmc::DeviceBuffer<> d_stage_stats;
   hipEvent_t ev_compute[2] = {nullptr, nullptr};
   hipEvent_t ev_copy[2] = {nullptr, nullptr};
   hipEvent_t ev_order = nullptr;  // smmc_engine_set_stream / wait_stream / release_to_stream
 
   // order statistics workspace
-  smmc::SelectState *d_select = nullptr;
-  unsigned long long *d_radix_hist = nullptr;  // kMaxRanks x 2048; zero between passes and calls (radix_pick_kernel
-                                               // clears what a pass counted); radix_dirty: an enqueue failed in between
-  bool radix_dirty = false;
-  smmc::SelectState *h_select = nullptr;       // page-locked: the call's ranks go up from here without a sync
-  float *d_select_out = nullptr;               // kMaxRanks
-  void *d_scratch_stats = nullptr;             // one packed record with SMMC_MAX_BINS buckets
-  unsigned long long *d_work_counter = nullptr;  // the comb keepdata kernel's chunk queue
+  smmc::DeviceBuffer<smmc::SelectState> d_select;
+  smmc::ZeroedArray radix_hist;  // kMaxRanks x 2048; zero between passes and calls (radix_pick_kernel clears what a pass counted)
+  smmc::PinnedBuffer<smmc::SelectState> h_select;  // page-locked: the call's ranks go up from here without a sync
+  smmc::DeviceBuffer<float> d_select_out;          // kMaxRanks
+  smmc::DeviceBuffer<> d_scratch_stats;            // one packed record with SMMC_MAX_BINS buckets
+  smmc::DeviceBuffer<unsigned long long> d_work_counter;  // the comb keepdata kernel's chunk queue
   // Bucket counts of the launch in flight: paths_kernel adds into copy 0, values_stats into kHistSpread copies;
   // finalize_kernel folds them into the caller's record and zeroes them again, so the array is ZERO between
-  // launches and neither it nor the record is memset per call.  hist_dirty: an enqueue failed between the kernel
-  // and its finalize -- the next user clears the whole array first (hist_acc_ready).
-  unsigned long long *d_hist_spread = nullptr;
-  bool hist_dirty = false;
-  smmc::BlockPartial *d_ck_partials = nullptr;  // checkpoints_kernel: [checkpoint][workgroup], grown on demand
-  size_t ck_partials_cap = 0;
+  // launches and neither it nor the record is memset per call.  Taken through a ZeroLease (engine_acc_lease).
+  smmc::ZeroedArray hist_acc;
+  smmc::DeviceBuffer<smmc::BlockPartial> d_ck_partials;  // checkpoints_kernel: [checkpoint][workgroup], grown on demand
   smmc::EngineExt ext = {nullptr, nullptr};     // state of another translation unit (smmc_internal.h: engine_ext)
 
   // SMMC_FLAG_STREAM_REF (smmc_ref_kernels.hip)
-  float *d_ref_final = nullptr;     // final values of a launch that asked for none (statistics are formed from them)
-  uint64_t ref_final_cap = 0;
-  uint32_t *d_ref_redo = nullptr;   // [0]: count, [4 ..): paths the windowed kernel left to the generic one
-  uint64_t ref_redo_cap = 0;
-  uint32_t *d_ref_ws = nullptr;     // the generic kernel's generator states
-  uint32_t ref_ws_grid = 0;
+  smmc::DeviceBuffer<float> d_ref_final;    // final values of a launch that asked for none (statistics are formed from them)
+  smmc::DeviceBuffer<uint32_t> d_ref_redo;  // [0]: count, [4 ..): paths the windowed kernel left to the generic one
+  smmc::DeviceBuffer<uint32_t> d_ref_ws;    // the generic kernel's generator states
   int ref_kernel = 0;               // SMMC_REF_KERNEL: 0 auto (also "tree", read by the launcher), 1 windowed (where it can), 2 generic
   // SMMC_REF_GENERIC_BLOCKS_PER_CU.  2e7 x 1000 paths (profiles/r03/ref_generic_sweep.txt): 1 per CU 85.8 ms, 2 60.0,
   // 4 48.3, 8 35.0 -- the chains that now supply the seed words want the occupancy; the 1.3 GB of generator
@@ -246,11 +246,11 @@ smmc::KernelArgs make_args(const smmc_engine *e, const smmc_sim *s) {
   smmc::KernelArgs a;
   std::memset(&a, 0, sizeof a);
   a.mode = s->mode;
-  a.table_a = s->mode == SMMC_MODE_TABLE ? e->d_table : nullptr;
+  a.table_a = s->mode == SMMC_MODE_TABLE ? e->d_table.p : nullptr;
   a.table_len = s->mode == SMMC_MODE_TABLE ? e->table_len : 0u;
   a.stream = (s->flags & SMMC_FLAG_STREAM_V2) ? 2 : 3;
   // d_bm_tables holds v2's radius + trig tables, then v3's
-  a.bm_tables = a.stream == 2 ? e->d_bm_tables : e->d_bm_tables + smmc::bm_tables_bytes(2) / sizeof(float);
+  a.bm_tables = a.stream == 2 ? e->d_bm_tables.p : e->d_bm_tables.p + smmc::bm_tables_bytes(2) / sizeof(float);
   a.key0 = static_cast<uint32_t>(s->seed);
   a.key1 = static_cast<uint32_t>(s->seed >> 32);
   a.first_path = s->first_path;
@@ -289,22 +289,19 @@ int timing_end(smmc_engine *e) {
   return SMMC_OK;
 }
 
-// One pass over n device floats -> packed statistics record (smmc_engine_values_stats after its argument
-// checks; also the statistics of a SMMC_FLAG_STREAM_REF launch).  Device must be current.
-// The engine's bucket accumulator, allocated and cleared on first use and cleared again after a failed enqueue.
-int hist_acc_ready(smmc_engine *e) {
-  const size_t bytes = sizeof(unsigned long long) * smmc::kHistSpread * SMMC_MAX_BINS;
-  if (!e->d_hist_spread) {
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_hist_spread), bytes));
-    e->hist_dirty = true;
+// The side stream of the two host pipelines and the four events that order it against the engine stream: brought
+// up by smmc_engine_create; the pipelines ask again, which costs nothing once they exist.  Device must be current.
+hipError_t side_ready(smmc_engine *e) {
+  hipError_t err = e->copy_stream ? hipSuccess : hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
+  for (int i = 0; i < 2; ++i) {
+    if (err == hipSuccess && !e->ev_compute[i]) err = hipEventCreateWithFlags(&e->ev_compute[i], hipEventDisableTiming);
+    if (err == hipSuccess && !e->ev_copy[i]) err = hipEventCreateWithFlags(&e->ev_copy[i], hipEventDisableTiming);
   }
-  if (e->hist_dirty) {
-    SMMC_HIP(hipMemsetAsync(e->d_hist_spread, 0, bytes, e->stream));
-    e->hist_dirty = false;
-  }
-  return SMMC_OK;
+  return err;
 }
 
+// One pass over n device floats -> packed statistics record (smmc_engine_values_stats after its argument
+// checks; also the statistics of a SMMC_FLAG_STREAM_REF launch).  Device must be current.
 int values_stats_enqueue(smmc_engine *e, const float *d_values, uint64_t n, float below_threshold, uint32_t n_bins,
                          float hist_lo, float hist_hi, void *d_stats, bool timed) {
   smmc::ValuesArgs a;
@@ -317,12 +314,13 @@ int values_stats_enqueue(smmc_engine *e, const float *d_values, uint64_t n, floa
   a.hist_lo = hist_lo;
   a.hist_hi = hist_hi;
   a.hist_inv = n_bins ? static_cast<double>(n_bins) / (static_cast<double>(hist_hi) - static_cast<double>(hist_lo)) : 0.0;
-  a.partials = e->d_partials;
+  a.partials = e->d_partials.p;
   a.d_hist = reinterpret_cast<unsigned long long *>(static_cast<char *>(d_stats) + sizeof(smmc_stats));
+  smmc::ZeroLease lease;
   if (n_bins) {  // spread copies of the bucket array (see ValuesArgs), zero now and zero again after finalize_kernel
-    const int rc = hist_acc_ready(e);
+    const int rc = smmc::engine_acc_lease(e, &lease);
     if (rc) return rc;
-    a.hist_spread = e->d_hist_spread;
+    a.hist_spread = lease.acc();
     a.spread = smmc::kHistSpread;
   }
   // 16 bytes per lane per iteration, 1024-thread workgroups, four per CU: two are resident (32 waves
@@ -330,12 +328,8 @@ int values_stats_enqueue(smmc_engine *e, const float *d_values, uint64_t n, floa
   // histogram: 1 per CU 0.102 / 0.758 ms, 2 per CU 0.083 / 0.699, 4 per CU 0.080 / 0.676
   const uint64_t want = (n / 4 + 1023) / 1024;
   uint32_t per_cu = 4;
-  if (const char *env = std::getenv("SMMC_STATS_BLOCKS_PER_CU")) {  // tuning knob
-    const long v = std::strtol(env, nullptr, 10);
-    if (v >= 1 && v <= 16) per_cu = static_cast<uint32_t>(v);
-  }
+  env_long("SMMC_STATS_BLOCKS_PER_CU", 1, 16, &per_cu);  // tuning knob
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(want, 1), std::min(e->compute_units * per_cu, e->max_grid)));
-  e->hist_dirty = n_bins != 0;  // until the finalize that clears the accumulator is in the queue
   if (n) {
     int rc = timed ? timing_begin(e) : SMMC_OK;
     if (rc) return rc;
@@ -347,9 +341,9 @@ int values_stats_enqueue(smmc_engine *e, const float *d_values, uint64_t n, floa
     rc = timed ? timing_end(e) : SMMC_OK;
     if (rc) return rc;
   }
-  SMMC_HIP(smmc::launch_finalize(e->d_partials, n ? grid : 0u, static_cast<smmc_stats *>(d_stats), n_bins, e->stream,
+  SMMC_HIP(smmc::launch_finalize(e->d_partials.p, n ? grid : 0u, static_cast<smmc_stats *>(d_stats), n_bins, e->stream,
                                  a.hist_spread, a.spread));
-  e->hist_dirty = false;
+  lease.finalize_queued();
   return SMMC_OK;
 }
 
@@ -367,16 +361,10 @@ int enqueue_ref_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, fl
                            void *d_stats, float *d_traj = nullptr) {
   const uint64_t n = s->n_paths;
   float *fin = d_final;
+  // the three arrays below are grown behind a drained stream: the kernels of the call before may still read them
   if (!fin && n) {
-    if (e->ref_final_cap < n) {
-      SMMC_HIP(hipStreamSynchronize(e->stream));
-      if (e->d_ref_final) SMMC_HIP(hipFree(e->d_ref_final));
-      e->d_ref_final = nullptr;
-      e->ref_final_cap = 0;
-      SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_ref_final), sizeof(float) * n));
-      e->ref_final_cap = n;
-    }
-    fin = e->d_ref_final;
+    SMMC_HIP(e->d_ref_final.reserve(sizeof(float) * n, &e->stream));
+    fin = e->d_ref_final.p;
   }
   const uint32_t T = e->table_len;
   const uint32_t P = s->n_periods;
@@ -384,34 +372,19 @@ int enqueue_ref_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, fl
   const uint32_t full_grid = e->compute_units * e->ref_generic_per_cu;
   if (n) {
     const uint64_t seg = std::min<uint64_t>(n, kRefLaunchPaths);
-    if (windowed && e->ref_redo_cap < seg) {
-      SMMC_HIP(hipStreamSynchronize(e->stream));
-      if (e->d_ref_redo) SMMC_HIP(hipFree(e->d_ref_redo));
-      e->d_ref_redo = nullptr;
-      e->ref_redo_cap = 0;
-      SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_ref_redo), sizeof(uint32_t) * (seg + 4)));
-      e->ref_redo_cap = seg;
-    }
-    const uint32_t ws_grid = windowed ? kRefRedoGrid : full_grid;
-    if (e->ref_ws_grid < ws_grid) {
-      SMMC_HIP(hipStreamSynchronize(e->stream));
-      if (e->d_ref_ws) SMMC_HIP(hipFree(e->d_ref_ws));
-      e->d_ref_ws = nullptr;
-      e->ref_ws_grid = 0;
-      SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_ref_ws), smmc::ref_workspace_bytes(ws_grid)));
-      e->ref_ws_grid = ws_grid;
-    }
+    if (windowed) SMMC_HIP(e->d_ref_redo.reserve(sizeof(uint32_t) * (seg + 4), &e->stream));
+    SMMC_HIP(e->d_ref_ws.reserve(smmc::ref_workspace_bytes(windowed ? kRefRedoGrid : full_grid), &e->stream));
     if (smmc::ref_windowed_lds_bytes(T, d_traj != nullptr) + 2048 > e->max_lds)
       return fail(SMMC_ERR_INVALID, "the table needs %zu bytes of LDS, device allows %zu",
                   smmc::ref_windowed_lds_bytes(T, d_traj != nullptr), e->max_lds);
     smmc::RefArgs a;
     std::memset(&a, 0, sizeof a);
-    a.table_a = e->d_table;
+    a.table_a = e->d_table.p;
     a.table_len = T;
     a.reject_below = static_cast<uint32_t>((0x100000000ull - T) % T);  // uniform_int_dist.h:258: -range % range
     a.n_periods = P;
     a.initial_capital = s->initial_capital;
-    a.workspace = e->d_ref_ws;
+    a.workspace = e->d_ref_ws.p;
     int div = divide_kind(e, s, true, &a.chk_lo, &a.chk_hi);
     int rc = timing_begin(e);
     if (rc) return rc;
@@ -430,16 +403,15 @@ int enqueue_ref_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, fl
       if (d_traj) {
         const uint64_t n_super = (count + 2047) / 2048, want = 6ull * e->compute_units;
         while (a.traj_rows > 1 && n_super * (8u / a.traj_rows) < want) a.traj_rows /= 2;
-        if (const char *env = std::getenv("SMMC_REF_TRAJ_ROWS")) {  // tuning knob
-          const long v = std::strtol(env, nullptr, 10);
-          if (v == 8 || v == 4 || v == 2 || v == 1) a.traj_rows = static_cast<uint32_t>(v);
-        }
+        uint32_t rows = a.traj_rows;
+        env_long("SMMC_REF_TRAJ_ROWS", 1, 8, &rows);  // tuning knob: 8, 4, 2 or 1
+        if ((rows & (rows - 1)) == 0) a.traj_rows = rows;
       }
       const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((count + smmc::kBlock - 1) / smmc::kBlock, e->max_grid));
       if (windowed) {
-        a.redo_count = e->d_ref_redo;
-        a.redo_list = e->d_ref_redo + 4;
-        SMMC_HIP_TIMED(e, hipMemsetAsync(e->d_ref_redo, 0, sizeof(uint32_t), e->stream));
+        a.redo_count = e->d_ref_redo.p;
+        a.redo_list = e->d_ref_redo.p + 4;
+        SMMC_HIP_TIMED(e, hipMemsetAsync(e->d_ref_redo.p, 0, sizeof(uint32_t), e->stream));
         SMMC_HIP_TIMED(e, smmc::launch_ref_windowed(a, div, grid, e->stream));
         SMMC_HIP_TIMED(e, smmc::launch_ref_generic(a, true, kRefRedoGrid, e->stream));
       } else {
@@ -473,16 +445,16 @@ int enqueue_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, float 
   a.d_chunk_var = d_chunk_var;
   const uint64_t n_chunks = (s->n_paths + smmc::kBlock - 1) / smmc::kBlock;
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(n_chunks, e->max_grid));
+  smmc::ZeroLease lease;
   if (d_stats) {  // no memset: finalize_kernel writes the whole record and leaves the accumulator zero again
-    a.partials = e->d_partials;
+    a.partials = e->d_partials.p;
     if (s->n_bins) {
-      const int rc = hist_acc_ready(e);
+      const int rc = smmc::engine_acc_lease(e, &lease);
       if (rc) return rc;
-      a.d_hist = e->d_hist_spread;  // copy 0
-      e->hist_dirty = true;
+      a.d_hist = lease.acc();  // copy 0
     }
   }
-  a.clock_probe = e->timing ? e->d_clock : nullptr;
+  a.clock_probe = e->timing ? e->d_clock.p : nullptr;
   if (grid > 0) {
     const size_t lds = smmc::paths_lds_bytes(a.table_len, d_stats ? s->n_bins : 0u, a.stream);
     if (lds + 2048 > e->max_lds)
@@ -492,9 +464,102 @@ int enqueue_simulation(smmc_engine *e, const smmc_sim *s, float *d_final, float 
     if (rc) return rc;
   }
   if (d_stats) {
-    SMMC_HIP(smmc::launch_finalize(e->d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, e->stream,
-                                   s->n_bins ? e->d_hist_spread : nullptr, s->n_bins ? 1u : 0u));
-    e->hist_dirty = false;
+    SMMC_HIP(smmc::launch_finalize(e->d_partials.p, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, e->stream,
+                                   lease.acc(), s->n_bins ? 1u : 0u));
+    lease.finalize_queued();
+  }
+  return SMMC_OK;
+}
+
+// The launch plan of smmc_engine_simulate_keepdata: decided on the host from numbers it already has -- the engine's
+// geometry, the table length, the request and the tuning knobs (results depend on none of them) -- before any device work.
+struct KeepdataPlan {
+  bool comb;               // the comb form takes rows [0, n_comb), the tile form the rest
+  uint64_t n_comb, n_wave_chunks;
+  int comb_waves, per_step;
+  uint32_t k_rows, comb_grid;
+  int tile, tile_waves;
+  uint32_t tile_grid;
+};
+int plan_keepdata(const smmc_engine *e, const smmc_sim *sim, KeepdataPlan *p) {
+  // Two kernels (smmc_kernels.hip).  The comb form takes whole 2048-row super-chunks when the row
+  // length is odd by construction (n_periods a multiple of the draws per Philox block) and there is
+  // enough of it to fill the chip; the tile form takes the rest (< 2048 rows), or everything.
+  // SMMC_KEEPDATA_KERNEL=tile|comb forces one (results never depend on it).
+  const size_t lds_cu = 160u * 1024u;
+  const uint32_t tl = sim->mode == SMMC_MODE_TABLE ? e->table_len : 0u;
+  const int strm = (sim->flags & SMMC_FLAG_STREAM_V2) ? 2 : 3;
+  const uint32_t draws = smmc::keepdata_draws(tl);
+  const uint64_t row_len = static_cast<uint64_t>(sim->n_periods) + 1;
+  const uint64_t n_super = sim->n_paths / 2048u;
+  const bool comb_fits = sim->n_periods >= 64u && sim->n_periods % draws == 0u && row_len <= (1u << 20) && n_super >= 1;
+  // waves per workgroup of the comb form: what fits the CU's LDS beside the tables, one workgroup per
+  // CU; table mode (tiles of 40 columns: 14 would fit) runs 12, three per SIMD: 3 % faster than 14
+  p->comb_waves = 0;
+  if (comb_fits) {
+    const size_t fixed = smmc::keepdata_comb_lds_bytes(tl, 0, strm);
+    const size_t per_wave = smmc::keepdata_comb_lds_bytes(tl, 1, strm) - fixed;
+    p->comb_waves = fixed < lds_cu ? static_cast<int>(std::min<size_t>((lds_cu - fixed) / per_wave, 16)) : 0;
+    if (sim->mode == SMMC_MODE_TABLE && p->comb_waves > 12) p->comb_waves = 12;
+    env_long("SMMC_KEEPDATA_COMB_WAVES", 1, p->comb_waves, &p->comb_waves);  // tuning knob
+  }
+  // the comb form needs enough chunks (64 rows each) to keep its waves level: below ~4 per wave
+  // (1e6 rows) the tile kernel's finer grain wins (0.20 vs 0.26 ms at 6e5 rows of 361 values; at
+  // 1.5e6 rows of 1001 values the comb form is ahead, 1.41 vs 1.58 ms in Gaussian mode)
+  p->comb = comb_fits && p->comb_waves >= 1 && n_super * 32u >= 4ull * e->compute_units * static_cast<uint64_t>(p->comb_waves);
+  if (const char *env = std::getenv("SMMC_KEEPDATA_KERNEL")) {
+    if (!std::strcmp(env, "tile")) p->comb = false;
+    if (!std::strcmp(env, "comb")) p->comb = comb_fits && p->comb_waves >= 1;
+  }
+  p->n_comb = p->comb ? n_super * 2048u : 0u;
+  // rows per stream.  More rows cost fewer extra columns (4.3 % at K = 1, 2.1 % at K = 2 for P = 360)
+  // but make the chunks a wave takes coarser.  Measured (tools/kd_ab.py, profiles/r02/keepdata_ab_stream_v3.txt):
+  // Gaussian 4e6 x 361: K = 1 1.141 ms, K = 2 1.150, K = 4 1.159; 1.5e6 x 1001: 1.293 / 1.324 / 1.344;
+  // table mode 1.095 / 1.103 and 1.212 / 1.236.  (With the costlier draws of stream v2 K = 2 won the
+  // first shape by 1.3 %.)
+  p->k_rows = 1;
+  p->n_wave_chunks = 0;
+  p->comb_grid = 0;
+  p->per_step = 1;
+  if (p->comb) {
+    uint32_t k = 1;
+    env_long("SMMC_KEEPDATA_K", 1, 32, &k);  // tuning knob: 1, 2, 4, 8, 16 or 32
+    if ((k & (k - 1)) == 0) p->k_rows = k;
+    p->n_wave_chunks = n_super * (32u / p->k_rows);
+    const uint32_t per_cu = e->keepdata_blocks_per_cu ? e->keepdata_blocks_per_cu : 1u;
+    p->comb_grid = static_cast<uint32_t>(std::min<uint64_t>((p->n_wave_chunks + p->comb_waves - 1) / p->comb_waves,
+                                                            static_cast<uint64_t>(e->compute_units) * per_cu));
+    // Philox blocks drawn together per step (instruction-level parallelism at < 4 waves per SIMD)
+    p->per_step = (sim->n_periods / draws) % 2u == 0u ? 2 : 1;
+    if (const char *env = std::getenv("SMMC_KEEPDATA_COMB_ILP")) {  // tuning knob
+      if (!std::strcmp(env, "1")) p->per_step = 1;
+    }
+  }
+  // Tile form (the rows the comb form does not take): tuning knobs, results do not depend on them:
+  // columns per LDS tile (16 | 32), waves per workgroup, workgroups per CU.  Defaults measured with
+  // tools/kd_ab.py: 32 columns (16 writes half lines); table mode 4 waves, three workgroups per CU (8 or
+  // 12 waves 1-5 % slower, 3 / 5 / 6 waves -- SIMDs unevenly filled -- 5-25 % slower); Gaussian mode,
+  // where the Box-Muller tables take 18.9 KB of every workgroup's LDS, one 12-wave workgroup per CU
+  // (2-15 % faster than two of 4); grid = what is resident (a wave strides over its 64-path chunks).
+  p->tile = 32;
+  p->tile_waves = 0;
+  p->tile_grid = 0;
+  if (p->n_comb < sim->n_paths) {
+    int tile = 32;
+    env_long("SMMC_KEEPDATA_TILE", 16, 32, &tile);
+    if (tile == 16 || tile == 32) p->tile = tile;
+    const size_t fixed = smmc::keepdata_lds_bytes(tl, p->tile, 0, strm);
+    const size_t per_wave = smmc::keepdata_lds_bytes(tl, p->tile, 1, strm) - fixed;
+    const int fit = fixed < lds_cu ? static_cast<int>(std::min<size_t>((lds_cu - fixed) / per_wave, 12)) : 0;
+    if (fit < 1) return fail(SMMC_ERR_INVALID, "keepdata: the table leaves no LDS for a tile");
+    p->tile_waves = sim->mode == SMMC_MODE_TABLE ? std::min(fit, 4) : (fit >= 12 ? 12 : fit >= 8 ? 8 : std::min(fit, 4));
+    env_long("SMMC_KEEPDATA_WAVES", 1, fit, &p->tile_waves);
+    const size_t lds = smmc::keepdata_lds_bytes(tl, p->tile, p->tile_waves, strm);
+    const uint64_t n_wave_chunks = (sim->n_paths - p->n_comb + 63) / 64;
+    const uint32_t resident = static_cast<uint32_t>(std::max<size_t>(lds_cu / lds, 1));
+    const uint32_t per_cu = e->keepdata_blocks_per_cu ? e->keepdata_blocks_per_cu : resident;
+    p->tile_grid = static_cast<uint32_t>(std::min<uint64_t>((n_wave_chunks + p->tile_waves - 1) / p->tile_waves,
+                                                            static_cast<uint64_t>(e->compute_units) * per_cu));
   }
   return SMMC_OK;
 }
@@ -562,15 +627,9 @@ int smmc_engine_create(int device, void *stream, smmc_engine **out) {
   e->device = device;
   e->compute_units = static_cast<uint32_t>(prop.multiProcessorCount);
   uint32_t blocks_per_cu = kBlocksPerCU;
-  if (const char *env = std::getenv("SMMC_BLOCKS_PER_CU")) {  // tuning knob, results do not depend on it
-    const long v = std::strtol(env, nullptr, 10);
-    if (v >= 1 && v <= 4096) blocks_per_cu = static_cast<uint32_t>(v);
-  }
+  env_long("SMMC_BLOCKS_PER_CU", 1, 4096, &blocks_per_cu);  // tuning knob, results do not depend on it
   e->max_grid = e->compute_units * blocks_per_cu;
-  if (const char *env = std::getenv("SMMC_KEEPDATA_BLOCKS_PER_CU")) {
-    const long v = std::strtol(env, nullptr, 10);
-    if (v >= 1 && v <= 4096) e->keepdata_blocks_per_cu = static_cast<uint32_t>(v);
-  }
+  env_long("SMMC_KEEPDATA_BLOCKS_PER_CU", 1, 4096, &e->keepdata_blocks_per_cu);
   if (const char *env = std::getenv("SMMC_HOST_CHUNK_PATHS")) {  // tuning/test knob, results do not depend on it
     const long long v = std::strtoll(env, nullptr, 10);
     if (v >= 1024) e->host_chunk_paths = static_cast<uint64_t>(v) / 1024 * 1024;
@@ -580,10 +639,7 @@ int smmc_engine_create(int device, void *stream, smmc_engine **out) {
   if (const char *env = std::getenv("SMMC_REF_KERNEL")) {  // test knob, results do not depend on it
     e->ref_kernel = !std::strcmp(env, "windowed") ? 1 : !std::strcmp(env, "generic") ? 2 : 0;
   }
-  if (const char *env = std::getenv("SMMC_REF_GENERIC_BLOCKS_PER_CU")) {  // tuning knob
-    const long v = std::strtol(env, nullptr, 10);
-    if (v >= 1 && v <= 16) e->ref_generic_per_cu = static_cast<uint32_t>(v);
-  }
+  env_long("SMMC_REF_GENERIC_BLOCKS_PER_CU", 1, 16, &e->ref_generic_per_cu);  // tuning knob
   // dynamic LDS a launch may ask for: the kernels opt in above the 64 KiB default (CDNA4: 160 KiB per CU)
   e->max_lds = std::max<size_t>(prop.sharedMemPerBlock, 128u * 1024u);
   // The first stream of a process costs ~20 ms (its hardware queue), the first host-to-device copy ~17 ms,
@@ -615,25 +671,21 @@ int smmc_engine_create(int device, void *stream, smmc_engine **out) {
   };
   auto make_side = [&]() {  // what simulate_to_host and reduce_mean_host would otherwise create on first use
     err_side = hipSetDevice(device);
-    if (err_side == hipSuccess) err_side = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && err_side == hipSuccess; ++i) {
-      err_side = hipEventCreateWithFlags(&e->ev_compute[i], hipEventDisableTiming);
-      if (err_side == hipSuccess) err_side = hipEventCreateWithFlags(&e->ev_copy[i], hipEventDisableTiming);
-    }
+    if (err_side == hipSuccess) err_side = side_ready(e);
     phase.mark("side stream and events");
   };
   auto make_tables = [&]() {
     err_tables = hipSetDevice(device);
     if (err_tables == hipSuccess)
-      err_tables = hipMalloc(reinterpret_cast<void **>(&e->d_partials), sizeof(smmc::BlockPartial) * e->max_grid);
+      err_tables = e->d_partials.reserve(sizeof(smmc::BlockPartial) * e->max_grid, nullptr);
     // the Gaussian kernels read counter stream v3's tables at absolute LDS addresses from 0
     if (err_tables == hipSuccess) err_tables = smmc::static_lds_bytes(&static_lds);
     phase.mark("kernel attributes (code object loaded)");
     // Box-Muller tables, as the kernels stage them: radius cubics then (cos, sin) pairs, counter stream
     // v2's set first, then v3's
     if (err_tables == hipSuccess)
-      err_tables = hipMalloc(reinterpret_cast<void **>(&e->d_bm_tables), smmc::bm_tables_bytes(2) + smmc::bm_tables_bytes(3));
-    char *dst = reinterpret_cast<char *>(e->d_bm_tables);
+      err_tables = e->d_bm_tables.reserve(smmc::bm_tables_bytes(2) + smmc::bm_tables_bytes(3), nullptr);
+    char *dst = reinterpret_cast<char *>(e->d_bm_tables.p);
     const void *parts[4] = {smmc_bm_radius, smmc_bm_trig, smmc_bm3_radius, smmc_bm3_trig};
     const size_t sizes[4] = {sizeof(smmc_bm_radius), sizeof(smmc_bm_trig), sizeof(smmc_bm3_radius), sizeof(smmc_bm3_trig)};
     for (int i = 0; i < 4 && err_tables == hipSuccess; ++i) {
@@ -674,27 +726,10 @@ void smmc_engine_destroy(smmc_engine *e) {
   for (int i = 0; i < 2; ++i) {
     if (e->ev_compute[i]) (void)hipEventDestroy(e->ev_compute[i]);
     if (e->ev_copy[i]) (void)hipEventDestroy(e->ev_copy[i]);
-    if (e->d_stage[i]) (void)hipFree(e->d_stage[i]);
-    if (e->d_stage_cs[i]) (void)hipFree(e->d_stage_cs[i]);
   }
-  if (e->d_stage_stats) (void)hipFree(e->d_stage_stats);
-  if (e->d_table) (void)hipFree(e->d_table);
-  if (e->d_bm_tables) (void)hipFree(e->d_bm_tables);
-  if (e->d_select) (void)hipFree(e->d_select);
-  if (e->d_radix_hist) (void)hipFree(e->d_radix_hist);
-  if (e->h_select) (void)hipHostFree(e->h_select);
-  if (e->d_select_out) (void)hipFree(e->d_select_out);
-  if (e->d_scratch_stats) (void)hipFree(e->d_scratch_stats);
-  if (e->d_work_counter) (void)hipFree(e->d_work_counter);
-  if (e->d_hist_spread) (void)hipFree(e->d_hist_spread);
-  if (e->d_ck_partials) (void)hipFree(e->d_ck_partials);
-  if (e->d_ref_final) (void)hipFree(e->d_ref_final);
-  if (e->d_ref_redo) (void)hipFree(e->d_ref_redo);
-  if (e->d_ref_ws) (void)hipFree(e->d_ref_ws);
-  if (e->d_partials) (void)hipFree(e->d_partials);
-  if (e->d_clock) (void)hipFree(e->d_clock);
-  if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  const hipStream_t owned = e->own_stream ? e->stream : nullptr;
+  delete e;  // every DeviceBuffer member: the device is current (guard), the owned stream still exists
+  if (owned) (void)hipStreamDestroy(owned);
 }
 
 int smmc_engine_set_table(smmc_engine *e, const float *returns_percent, uint32_t n) {
@@ -716,12 +751,11 @@ int smmc_engine_set_table(smmc_engine *e, const float *returns_percent, uint32_t
   if (e->table_len != n) {
     // the previous table may still be read by enqueued kernels
     SMMC_HIP(hipStreamSynchronize(e->stream));
-    if (e->d_table) SMMC_HIP(hipFree(e->d_table));
-    e->d_table = nullptr;
+    SMMC_HIP(e->d_table.release());  // a table of another length is a new allocation, also a shorter one
     e->table_len = 0;
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_table), sizeof(float) * n));
+    SMMC_HIP(e->d_table.reserve(sizeof(float) * n, nullptr));
   }
-  SMMC_HIP(hipMemcpyAsync(e->d_table, a.data(), sizeof(float) * n, hipMemcpyHostToDevice, e->stream));
+  SMMC_HIP(hipMemcpyAsync(e->d_table.p, a.data(), sizeof(float) * n, hipMemcpyHostToDevice, e->stream));
   SMMC_HIP(hipStreamSynchronize(e->stream));  // `a` is a local
   e->table_len = n;
   e->table_min_a = lo;
@@ -757,127 +791,36 @@ int smmc_engine_simulate_keepdata(smmc_engine *e, const smmc_sim *sim, float *d_
     return enqueue_ref_simulation(e, sim, d_final, nullptr, nullptr, nullptr, d_traj);
   float unused_lo, unused_hi;
   const bool exact_div = divide_kind(e, sim, false, &unused_lo, &unused_hi) != SMMC_DIV_FAST;
-
-  // Two kernels (smmc_kernels.hip).  The comb form takes whole 2048-row super-chunks when the row
-  // length is odd by construction (n_periods a multiple of the draws per Philox block) and there is
-  // enough of it to fill the chip; the tile form takes the rest (< 2048 rows), or everything.
-  // SMMC_KEEPDATA_KERNEL=tile|comb forces one (results never depend on it).
-  const uint32_t draws = smmc::keepdata_draws(sim->mode == SMMC_MODE_TABLE ? e->table_len : 0u);
-  const uint64_t row_len = static_cast<uint64_t>(sim->n_periods) + 1;
-  uint64_t n_super = sim->n_paths / 2048u;
-  const bool comb_fits = sim->n_periods >= 64u && sim->n_periods % draws == 0u && row_len <= (1u << 20) && n_super >= 1;
-  // waves per workgroup of the comb form: what fits the CU's LDS beside the tables, one workgroup per
-  // CU; table mode (tiles of 40 columns: 14 would fit) runs 12, three per SIMD: 3 % faster than 14
-  int comb_waves = 0;
-  if (comb_fits) {
-    const size_t lds_cu = 160u * 1024u;
-    const uint32_t tl = sim->mode == SMMC_MODE_TABLE ? e->table_len : 0u;
-    const int strm = (sim->flags & SMMC_FLAG_STREAM_V2) ? 2 : 3;
-    const size_t fixed = smmc::keepdata_comb_lds_bytes(tl, 0, strm);
-    const size_t per_wave = smmc::keepdata_comb_lds_bytes(tl, 1, strm) - fixed;
-    comb_waves = fixed < lds_cu ? static_cast<int>(std::min<size_t>((lds_cu - fixed) / per_wave, 16)) : 0;
-    if (sim->mode == SMMC_MODE_TABLE && comb_waves > 12) comb_waves = 12;
-    if (const char *env = std::getenv("SMMC_KEEPDATA_COMB_WAVES")) {  // tuning knob
-      const long v = std::strtol(env, nullptr, 10);
-      if (v >= 1 && v <= comb_waves) comb_waves = static_cast<int>(v);
-    }
-  }
-  // the comb form needs enough chunks (64 rows each) to keep its waves level: below ~4 per wave
-  // (1e6 rows) the tile kernel's finer grain wins (0.20 vs 0.26 ms at 6e5 rows of 361 values; at
-  // 1.5e6 rows of 1001 values the comb form is ahead, 1.41 vs 1.58 ms in Gaussian mode)
-  bool comb = comb_fits && comb_waves >= 1 &&
-              n_super * 32u >= 4ull * e->compute_units * static_cast<uint64_t>(comb_waves);
-  if (const char *env = std::getenv("SMMC_KEEPDATA_KERNEL")) {
-    if (!std::strcmp(env, "tile")) comb = false;
-    if (!std::strcmp(env, "comb")) comb = comb_fits && comb_waves >= 1;
-  }
-  const uint64_t n_comb = comb ? n_super * 2048u : 0u;
   // Everything that can fail is decided BEFORE the first launch and before the timing pair opens
   // (a failing tile set-up used to leave the comb part written and a start event without its stop).
-  // Tile form (the rows the comb form does not take): tuning knobs, results do not depend on them:
-  // columns per LDS tile (16 | 32), waves per workgroup, workgroups per CU.  Defaults measured with
-  // tools/kd_ab.py: 32 columns (16 writes half lines); table mode 4 waves, three workgroups per CU (8 or
-  // 12 waves 1-5 % slower, 3 / 5 / 6 waves -- SIMDs unevenly filled -- 5-25 % slower); Gaussian mode,
-  // where the Box-Muller tables take 18.9 KB of every workgroup's LDS, one 12-wave workgroup per CU
-  // (2-15 % faster than two of 4); grid = what is resident (a wave strides over its 64-path chunks).
-  int tile = 32, tile_waves = 0;
-  uint32_t tile_grid = 0;
-  if (n_comb < sim->n_paths) {
-    const uint32_t tl = sim->mode == SMMC_MODE_TABLE ? e->table_len : 0u;
-    const int strm = (sim->flags & SMMC_FLAG_STREAM_V2) ? 2 : 3;
-    if (const char *env = std::getenv("SMMC_KEEPDATA_TILE")) {
-      const long v = std::strtol(env, nullptr, 10);
-      if (v == 16 || v == 32) tile = static_cast<int>(v);
-    }
-    const size_t lds_cu = 160u * 1024u;
-    const size_t fixed = smmc::keepdata_lds_bytes(tl, tile, 0, strm);
-    const size_t per_wave = smmc::keepdata_lds_bytes(tl, tile, 1, strm) - fixed;
-    const int fit = fixed < lds_cu ? static_cast<int>(std::min<size_t>((lds_cu - fixed) / per_wave, 12)) : 0;
-    if (fit < 1) return fail(SMMC_ERR_INVALID, "keepdata: the table leaves no LDS for a tile");
-    tile_waves = sim->mode == SMMC_MODE_TABLE ? std::min(fit, 4) : (fit >= 12 ? 12 : fit >= 8 ? 8 : std::min(fit, 4));
-    if (const char *env = std::getenv("SMMC_KEEPDATA_WAVES")) {
-      const long v = std::strtol(env, nullptr, 10);
-      if (v >= 1 && v <= fit) tile_waves = static_cast<int>(v);
-    }
-    const size_t lds = smmc::keepdata_lds_bytes(tl, tile, tile_waves, strm);
-    const uint64_t n_wave_chunks = (sim->n_paths - n_comb + 63) / 64;
-    const uint32_t resident = static_cast<uint32_t>(std::max<size_t>(lds_cu / lds, 1));
-    const uint32_t per_cu = e->keepdata_blocks_per_cu ? e->keepdata_blocks_per_cu : resident;
-    tile_grid = static_cast<uint32_t>(
-        std::min<uint64_t>((n_wave_chunks + tile_waves - 1) / tile_waves, static_cast<uint64_t>(e->compute_units) * per_cu));
-  }
-  if (comb && !e->d_work_counter)
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_work_counter), sizeof(unsigned long long)));
+  KeepdataPlan p;
+  rc = plan_keepdata(e, sim, &p);
+  if (rc) return rc;
+  if (p.comb) SMMC_HIP(e->d_work_counter.reserve(sizeof(unsigned long long), nullptr));  // allocated once
   rc = timing_begin(e);
   if (rc) return rc;
-  // from here on a failure closes the timing pair before it returns
-  auto bail = [&](hipError_t err, const char *what) {
-    (void)timing_end(e);
-    return fail(SMMC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(err));
-  };
-  if (comb) {
+  // from here on a failure closes the timing pair before it returns (SMMC_HIP_TIMED)
+  const uint64_t row_len = static_cast<uint64_t>(sim->n_periods) + 1;
+  if (p.comb) {
     smmc::KernelArgs a = make_args(e, sim);
     a.d_traj = d_traj;
     a.d_final = nullptr;
-    a.n_paths = n_comb;
-    const int waves = comb_waves;
-    // rows per stream.  More rows cost fewer extra columns (4.3 % at K = 1, 2.1 % at K = 2 for P = 360)
-    // but make the chunks a wave takes coarser.  Measured (tools/kd_ab.py, profiles/r02/keepdata_ab_stream_v3.txt):
-    // Gaussian 4e6 x 361: K = 1 1.141 ms, K = 2 1.150, K = 4 1.159; 1.5e6 x 1001: 1.293 / 1.324 / 1.344;
-    // table mode 1.095 / 1.103 and 1.212 / 1.236.  (With the costlier draws of stream v2 K = 2 won the
-    // first shape by 1.3 %.)
-    uint32_t k_rows = 1;
-    if (const char *env = std::getenv("SMMC_KEEPDATA_K")) {  // tuning knob: 1, 2, 4, 8, 16 or 32
-      const long v = std::strtol(env, nullptr, 10);
-      if (v >= 1 && v <= 32 && (v & (v - 1)) == 0) k_rows = static_cast<uint32_t>(v);
-    }
-    const uint64_t n_wave_chunks = n_super * (32u / k_rows);
-    const uint32_t per_cu = e->keepdata_blocks_per_cu ? e->keepdata_blocks_per_cu : 1u;
-    const uint32_t cgrid = static_cast<uint32_t>(
-        std::min<uint64_t>((n_wave_chunks + waves - 1) / waves, static_cast<uint64_t>(e->compute_units) * per_cu));
-    // Philox blocks drawn together per step (instruction-level parallelism at < 4 waves per SIMD)
-    int per_step = (sim->n_periods / draws) % 2u == 0u ? 2 : 1;
-    if (const char *env = std::getenv("SMMC_KEEPDATA_COMB_ILP")) {  // tuning knob
-      if (!std::strcmp(env, "1")) per_step = 1;
-    }
-    const hipError_t err = smmc::launch_keepdata_comb(a, exact_div, per_step, k_rows, n_wave_chunks, sim->n_paths, waves, cgrid,
-                                                      e->d_work_counter, e->stream);
-    if (err != hipSuccess) return bail(err, "launch_keepdata_comb");
+    a.n_paths = p.n_comb;
+    SMMC_HIP_TIMED(e, smmc::launch_keepdata_comb(a, exact_div, p.per_step, p.k_rows, p.n_wave_chunks, sim->n_paths, p.comb_waves,
+                                                 p.comb_grid, e->d_work_counter.p, e->stream));
   }
-  if (n_comb < sim->n_paths) {
+  if (p.n_comb < sim->n_paths) {
     smmc_sim rest = *sim;
-    rest.first_path = sim->first_path + n_comb;
-    rest.n_paths = sim->n_paths - n_comb;
+    rest.first_path = sim->first_path + p.n_comb;
+    rest.n_paths = sim->n_paths - p.n_comb;
     smmc::KernelArgs a = make_args(e, &rest);
-    a.d_traj = d_traj + n_comb * row_len;
-    a.d_final = (d_final && !comb) ? d_final : nullptr;
-    const hipError_t err = smmc::launch_keepdata(a, exact_div, tile, tile_waves, tile_grid, e->stream);
-    if (err != hipSuccess) return bail(err, "launch_keepdata");
+    a.d_traj = d_traj + p.n_comb * row_len;
+    a.d_final = (d_final && !p.comb) ? d_final : nullptr;
+    SMMC_HIP_TIMED(e, smmc::launch_keepdata(a, exact_div, p.tile, p.tile_waves, p.tile_grid, e->stream));
   }
-  if (comb && d_final) {  // the comb form leaves the final values to a gather of the last column
+  if (p.comb && d_final) {  // the comb form leaves the final values to a gather of the last column
     const uint32_t fgrid = static_cast<uint32_t>(std::min<uint64_t>((sim->n_paths + smmc::kBlock - 1) / smmc::kBlock, e->max_grid));
-    const hipError_t err = smmc::launch_final_column(d_traj, sim->n_paths, static_cast<uint32_t>(row_len), d_final, fgrid, e->stream);
-    if (err != hipSuccess) return bail(err, "launch_final_column");
+    SMMC_HIP_TIMED(e, smmc::launch_final_column(d_traj, sim->n_paths, static_cast<uint32_t>(row_len), d_final, fgrid, e->stream));
   }
   return timing_end(e);
 }
@@ -932,22 +875,15 @@ int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const 
     return fail(SMMC_ERR_INVALID, "table + checkpoint histograms need %zu bytes of LDS, device allows %zu", lds, e->max_lds);
   DeviceGuard guard(e->device);
   if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-  const size_t want = static_cast<size_t>(grid) * n_checkpoints;
-  if (e->ck_partials_cap < want) {
-    SMMC_HIP(hipStreamSynchronize(e->stream));  // an earlier launch may still read the old array
-    if (e->d_ck_partials) SMMC_HIP(hipFree(e->d_ck_partials));
-    e->d_ck_partials = nullptr;
-    e->ck_partials_cap = 0;
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_ck_partials), sizeof(smmc::BlockPartial) * want));
-    e->ck_partials_cap = want;
-  }
+  // drained: an earlier launch may still read the old array
+  SMMC_HIP(e->d_ck_partials.reserve(sizeof(smmc::BlockPartial) * grid * n_checkpoints, &e->stream));
   a.d_final = d_final;
-  a.partials = e->d_ck_partials;
+  a.partials = e->d_ck_partials.p;
+  smmc::ZeroLease lease;
   if (sim->n_bins) {
-    rc = hist_acc_ready(e);
+    rc = smmc::engine_acc_lease(e, &lease);
     if (rc) return rc;
-    a.d_hist = e->d_hist_spread;  // [checkpoint][bucket], zero now and zero again after the finalize
-    e->hist_dirty = true;
+    a.d_hist = lease.acc();  // [checkpoint][bucket], zero now and zero again after the finalize
   }
   if (grid) {
     float unused_lo, unused_hi;
@@ -956,9 +892,9 @@ int smmc_engine_simulate_checkpoints(smmc_engine *e, const smmc_sim *sim, const 
                                  [&] { return smmc::launch_checkpoints(a, periods, n_checkpoints, exact_div, grid, e->stream); });
     if (rc) return rc;
   }
-  SMMC_HIP(smmc::launch_finalize_checkpoints(e->d_ck_partials, grid, n_checkpoints, d_records, sim->n_bins,
-                                             sim->n_bins ? e->d_hist_spread : nullptr, e->stream));
-  e->hist_dirty = false;
+  SMMC_HIP(smmc::launch_finalize_checkpoints(e->d_ck_partials.p, grid, n_checkpoints, d_records, sim->n_bins,
+                                             lease.acc(), e->stream));
+  lease.finalize_queued();
   return SMMC_OK;
 }
 
@@ -987,15 +923,10 @@ int smmc_engine_sync(smmc_engine *e) {
 namespace {
 
 // The two device staging buffers of the host pipeline, at least `chunk` floats each.  Device must be current.
+// Not drained, nor are the other staging buffers: both pipelines return behind a synchronisation of the streams
+// that used them.
 int reserve_staging(smmc_engine *e, uint64_t chunk) {
-  if (e->stage_paths >= chunk) return SMMC_OK;
-  for (int i = 0; i < 2; ++i) {
-    if (e->d_stage[i]) SMMC_HIP(hipFree(e->d_stage[i]));
-    e->d_stage[i] = nullptr;
-  }
-  e->stage_paths = 0;
-  for (int i = 0; i < 2; ++i) SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_stage[i]), sizeof(float) * chunk));
-  e->stage_paths = chunk;
+  for (int i = 0; i < 2; ++i) SMMC_HIP(e->d_stage[i].reserve(sizeof(float) * chunk, nullptr));
   return SMMC_OK;
 }
 
@@ -1143,32 +1074,13 @@ int smmc::host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host
   const size_t rec = smmc_stats_bytes(sim->n_bins);
   const uint64_t cs_per_chunk = (chunk + smmc::kBlock - 1) / smmc::kBlock;
 
-  if (!e->copy_stream) SMMC_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    if (!e->ev_compute[i]) SMMC_HIP(hipEventCreateWithFlags(&e->ev_compute[i], hipEventDisableTiming));
-    if (!e->ev_copy[i]) SMMC_HIP(hipEventCreateWithFlags(&e->ev_copy[i], hipEventDisableTiming));
-  }
+  SMMC_HIP(side_ready(e));
   if (host_final) {
     rc = reserve_staging(e, chunk);
     if (rc) return rc;
   }
-  if (want_cs && e->stage_cs < cs_per_chunk) {
-    for (int i = 0; i < 2; ++i) {
-      if (e->d_stage_cs[i]) SMMC_HIP(hipFree(e->d_stage_cs[i]));
-      e->d_stage_cs[i] = nullptr;
-    }
-    e->stage_cs = 0;
-    for (int i = 0; i < 2; ++i)
-      SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_stage_cs[i]), sizeof(float) * 2 * cs_per_chunk));
-    e->stage_cs = cs_per_chunk;
-  }
-  if (want_stats && e->stage_stats_bytes < rec * std::max<uint64_t>(n_chunks, 1)) {
-    if (e->d_stage_stats) SMMC_HIP(hipFree(e->d_stage_stats));
-    e->d_stage_stats = nullptr;
-    e->stage_stats_bytes = 0;
-    SMMC_HIP(hipMalloc(&e->d_stage_stats, rec * std::max<uint64_t>(n_chunks, 1)));
-    e->stage_stats_bytes = rec * std::max<uint64_t>(n_chunks, 1);
-  }
+  for (int i = 0; i < 2 && want_cs; ++i) SMMC_HIP(e->d_stage_cs[i].reserve(sizeof(float) * 2 * cs_per_chunk, nullptr));
+  if (want_stats) SMMC_HIP(e->d_stage_stats.reserve(rec * std::max<uint64_t>(n_chunks, 1), nullptr));
   phase.mark("side stream, events, staging buffers");
   auto report = [&](uint64_t done) {
     if (progress) __atomic_store_n(const_cast<int64_t *>(progress), static_cast<int64_t>(done), __ATOMIC_RELEASE);
@@ -1230,17 +1142,17 @@ int smmc::host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host
       if (pin_chunks) pin_chunk[(c - 2) % 3].release();
     }
     if (pin_chunks && c >= 1 && c + 1 < n_chunks) pin_chunk_c(c + 1);  // chunks c - 1, c, c + 1 registered while copy c is enqueued
-    void *d_rec = want_stats ? static_cast<char *>(e->d_stage_stats) + rec * c : nullptr;
-    float *d_cm = want_cs ? e->d_stage_cs[b] : nullptr;
-    float *d_cv = want_cs ? e->d_stage_cs[b] + cs_per_chunk : nullptr;
-    rc = enqueue(e, &part, host_final ? e->d_stage[b] : nullptr, d_cm, d_cv, d_rec, ctx);
+    void *d_rec = want_stats ? static_cast<char *>(e->d_stage_stats.p) + rec * c : nullptr;
+    float *d_cm = want_cs ? e->d_stage_cs[b].p : nullptr;
+    float *d_cv = want_cs ? d_cm + cs_per_chunk : nullptr;
+    rc = enqueue(e, &part, host_final ? e->d_stage[b].p : nullptr, d_cm, d_cv, d_rec, ctx);
     if (rc) return rc;
     if (copies) {
       SMMC_HIP(hipEventRecord(e->ev_compute[b], e->stream));
       SMMC_HIP(hipStreamWaitEvent(e->copy_stream, e->ev_compute[b], 0));
       if (host_final) {
         char *dst = reinterpret_cast<char *>(host_final + c * chunk);
-        const char *src = reinterpret_cast<const char *>(e->d_stage[b]);
+        const char *src = reinterpret_cast<const char *>(e->d_stage[b].p);
         const size_t bytes = sizeof(float) * part.n_paths;
         size_t head = bytes;
         if (pin_chunks && c + 1 < n_chunks) {  // the last bytes lie in the page chunk c + 1 owns
@@ -1285,7 +1197,7 @@ int smmc::host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host
     h->max = -std::numeric_limits<float>::infinity();
     h->n_bins = sim->n_bins;
     if (n_chunks) {
-      SMMC_HIP(hipMemcpy(all.data(), e->d_stage_stats, rec * n_chunks, hipMemcpyDeviceToHost));
+      SMMC_HIP(hipMemcpy(all.data(), e->d_stage_stats.p, rec * n_chunks, hipMemcpyDeviceToHost));
       for (uint64_t c = 0; c < n_chunks; ++c) {
         rc = smmc_stats_merge(acc.data(), all.data() + rec * c);
         if (rc) return rc;
@@ -1311,23 +1223,20 @@ int smmc_engine_simulate_keepdata_to_host(smmc_engine *e, const smmc_sim *sim, f
   uint64_t slice = std::max<uint64_t>((1ull << 28) / row, 1);
   slice = std::max<uint64_t>(slice / smmc::kBlock * smmc::kBlock, smmc::kBlock);
   slice = std::min<uint64_t>(slice, std::max<uint64_t>(sim->n_paths, 1));
-  float *d_traj = nullptr, *d_fin = nullptr;
-  SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&d_traj), sizeof(float) * slice * row));
-  hipError_t err = hipMalloc(reinterpret_cast<void **>(&d_fin), sizeof(float) * slice);
+  smmc::DeviceBuffer<float> d_traj, d_fin;  // the call's own: freed on every way out
+  SMMC_HIP(d_traj.reserve(sizeof(float) * slice * row, nullptr));
+  hipError_t err = d_fin.reserve(sizeof(float) * slice, nullptr);
   for (uint64_t first = 0; err == hipSuccess && first < sim->n_paths; first += slice) {
     smmc_sim part = *sim;
     part.first_path = sim->first_path + first;
     part.n_paths = std::min<uint64_t>(slice, sim->n_paths - first);
-    rc = smmc_engine_simulate_keepdata(e, &part, d_traj, d_fin);
-    if (rc) break;
-    err = hipMemcpyAsync(host_traj + first * row, d_traj, sizeof(float) * part.n_paths * row, hipMemcpyDeviceToHost, e->stream);
+    rc = smmc_engine_simulate_keepdata(e, &part, d_traj.p, d_fin.p);
+    if (rc) return rc;
+    err = hipMemcpyAsync(host_traj + first * row, d_traj.p, sizeof(float) * part.n_paths * row, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess && host_final)
-      err = hipMemcpyAsync(host_final + first, d_fin, sizeof(float) * part.n_paths, hipMemcpyDeviceToHost, e->stream);
+      err = hipMemcpyAsync(host_final + first, d_fin.p, sizeof(float) * part.n_paths, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   }
-  (void)hipFree(d_traj);
-  if (d_fin) (void)hipFree(d_fin);
-  if (rc) return rc;
   if (err != hipSuccess) return fail(SMMC_ERR_HIP, "keepdata_to_host failed: %s", hipGetErrorString(err));
   return SMMC_OK;
 }
@@ -1358,42 +1267,34 @@ int smmc_engine_order_statistics(smmc_engine *e, const float *d_values, uint64_t
   DeviceGuard guard(e->device);
   if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
   const size_t hist_bytes = sizeof(unsigned long long) * smmc::kMaxRanks * 2048;
-  if (!e->d_select) SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_select), sizeof(smmc::SelectState)));
-  if (!e->d_radix_hist) {
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_radix_hist), hist_bytes));
-    e->radix_dirty = true;
-  }
-  if (!e->d_select_out) SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_select_out), sizeof(float) * smmc::kMaxRanks));
-  if (!e->h_select) SMMC_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->h_select), sizeof(smmc::SelectState), hipHostMallocDefault));
-  if (e->radix_dirty) {
-    SMMC_HIP(hipMemsetAsync(e->d_radix_hist, 0, hist_bytes, e->stream));
-    e->radix_dirty = false;
-  }
+  // the workspace, allocated once; the histogram is leased until the last pick of the call is in the queue: an error
+  // return in between leaves counts behind
+  SMMC_HIP(e->d_select.reserve(sizeof(smmc::SelectState), nullptr));
+  SMMC_HIP(e->d_select_out.reserve(sizeof(float) * smmc::kMaxRanks, nullptr));
+  SMMC_HIP(e->h_select.reserve(sizeof(smmc::SelectState), nullptr));
+  smmc::ZeroLease lease;
+  SMMC_HIP(lease.take(e->radix_hist, hist_bytes, e->stream));
   // the state goes up from the engine's page-locked copy: every call ends with a synchronisation of the stream, so the
   // copy of the call before has long been read
-  std::memset(e->h_select, 0, sizeof(smmc::SelectState));
-  for (uint32_t q = 0; q < n_ranks; ++q) e->h_select->rank[q] = ranks[q];
-  SMMC_HIP(hipMemcpyAsync(e->d_select, e->h_select, sizeof(smmc::SelectState), hipMemcpyHostToDevice, e->stream));
+  std::memset(e->h_select.p, 0, sizeof(smmc::SelectState));
+  for (uint32_t q = 0; q < n_ranks; ++q) e->h_select.p->rank[q] = ranks[q];
+  SMMC_HIP(hipMemcpyAsync(e->d_select.p, e->h_select.p, sizeof(smmc::SelectState), hipMemcpyHostToDevice, e->stream));
   // 1024-thread workgroups, four per CU of which two are resident (the LDS histograms allow no more);
   // the queued ones even out the CUs: 1e9 values 0.730 -> 0.699 ms per pass (2 -> 4 per CU)
   const uint64_t want = (n / 8 + 1023) / 1024;
   uint32_t radix_per_cu = 4;
-  if (const char *env = std::getenv("SMMC_RADIX_BLOCKS_PER_CU")) {  // tuning knob
-    const long v = std::strtol(env, nullptr, 10);
-    if (v >= 1 && v <= 16) radix_per_cu = static_cast<uint32_t>(v);
-  }
+  env_long("SMMC_RADIX_BLOCKS_PER_CU", 1, 16, &radix_per_cu);  // tuning knob
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(want, 1), e->compute_units * radix_per_cu));
-  e->radix_dirty = true;  // until the last pick of the call is in the queue: an error return in between leaves counts behind
   for (int pass = 0; pass < 3; ++pass) {
     int rc = timing_begin(e);
     if (rc) return rc;
-    SMMC_HIP_TIMED(e, smmc::launch_radix_hist(d_values, n, pass, n_ranks, e->d_select, e->d_radix_hist, grid, e->stream));
+    SMMC_HIP_TIMED(e, smmc::launch_radix_hist(d_values, n, pass, n_ranks, e->d_select.p, lease.acc(), grid, e->stream));
     rc = timing_end(e);
     if (rc) return rc;
-    SMMC_HIP(smmc::launch_radix_pick(pass, n_ranks, e->d_select, e->d_radix_hist, e->d_select_out, e->stream));
+    SMMC_HIP(smmc::launch_radix_pick(pass, n_ranks, e->d_select.p, lease.acc(), e->d_select_out.p, e->stream));
   }
-  e->radix_dirty = false;
-  SMMC_HIP(hipMemcpyAsync(host_out, e->d_select_out, sizeof(float) * n_ranks, hipMemcpyDeviceToHost, e->stream));
+  lease.finalize_queued();
+  SMMC_HIP(hipMemcpyAsync(host_out, e->d_select_out.p, sizeof(float) * n_ranks, hipMemcpyDeviceToHost, e->stream));
   SMMC_HIP(hipStreamSynchronize(e->stream));
   return SMMC_OK;
 }
@@ -1418,34 +1319,24 @@ int smmc_engine_reduce_mean_host(smmc_engine *e, const float *host_values, uint6
     const int rc = reserve_staging(e, chunk);
     if (rc) return rc;
   }
-  if (!e->copy_stream) SMMC_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    if (!e->ev_compute[i]) SMMC_HIP(hipEventCreateWithFlags(&e->ev_compute[i], hipEventDisableTiming));
-    if (!e->ev_copy[i]) SMMC_HIP(hipEventCreateWithFlags(&e->ev_copy[i], hipEventDisableTiming));
-  }
+  SMMC_HIP(side_ready(e));
   const uint64_t n_chunks = (n + chunk - 1) / chunk;
   const size_t rec = smmc_stats_bytes(0);
-  if (e->stage_stats_bytes < rec * n_chunks) {
-    if (e->d_stage_stats) SMMC_HIP(hipFree(e->d_stage_stats));
-    e->d_stage_stats = nullptr;
-    e->stage_stats_bytes = 0;
-    SMMC_HIP(hipMalloc(&e->d_stage_stats, rec * n_chunks));
-    e->stage_stats_bytes = rec * n_chunks;
-  }
+  SMMC_HIP(e->d_stage_stats.reserve(rec * n_chunks, nullptr));  // not drained: see reserve_staging
   // H2D of chunk c (copy stream) overlaps the reduction of chunk c - 1 (engine stream)
   for (uint64_t c = 0; c < n_chunks; ++c) {
     const int b = static_cast<int>(c & 1);
     const uint64_t count = std::min<uint64_t>(chunk, n - c * chunk);
     if (c >= 2) SMMC_HIP(hipStreamWaitEvent(e->copy_stream, e->ev_compute[b], 0));
-    SMMC_HIP(hipMemcpyAsync(e->d_stage[b], host_values + c * chunk, sizeof(float) * count, hipMemcpyHostToDevice, e->copy_stream));
+    SMMC_HIP(hipMemcpyAsync(e->d_stage[b].p, host_values + c * chunk, sizeof(float) * count, hipMemcpyHostToDevice, e->copy_stream));
     SMMC_HIP(hipEventRecord(e->ev_copy[b], e->copy_stream));
     SMMC_HIP(hipStreamWaitEvent(e->stream, e->ev_copy[b], 0));
-    int rc = smmc_engine_values_stats(e, e->d_stage[b], count, 0.f, 0, 0.f, 1.f, static_cast<char *>(e->d_stage_stats) + rec * c);
+    int rc = smmc_engine_values_stats(e, e->d_stage[b].p, count, 0.f, 0, 0.f, 1.f, static_cast<char *>(e->d_stage_stats.p) + rec * c);
     if (rc) return rc;
     SMMC_HIP(hipEventRecord(e->ev_compute[b], e->stream));
   }
   std::vector<smmc_stats> recs(n_chunks);
-  SMMC_HIP(hipMemcpyAsync(recs.data(), e->d_stage_stats, rec * n_chunks, hipMemcpyDeviceToHost, e->stream));
+  SMMC_HIP(hipMemcpyAsync(recs.data(), e->d_stage_stats.p, rec * n_chunks, hipMemcpyDeviceToHost, e->stream));
   SMMC_HIP(hipStreamSynchronize(e->stream));
   double total = 0.0;
   for (uint64_t c = 0; c < n_chunks; ++c) total += recs[c].sum;  // chunk order
@@ -1462,16 +1353,17 @@ int smmc_engine_host_values_summary(smmc_engine *e, const float *host_values, ui
   if (n_bins > SMMC_MAX_BINS) return fail(SMMC_ERR_INVALID, "n_bins %u exceeds SMMC_MAX_BINS %d", n_bins, SMMC_MAX_BINS);
   DeviceGuard guard(e->device);
   if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-  float *d = nullptr;
-  SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(float) * n));
+  smmc::DeviceBuffer<float> values;  // the call's copy: freed on every way out, behind the synchronisation below
+  SMMC_HIP(values.reserve(sizeof(float) * n, nullptr));
+  float *const d = values.p;
   int rc = SMMC_OK;
   hipError_t err = hipMemcpyAsync(d, host_values, sizeof(float) * n, hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess && !e->d_scratch_stats) err = hipMalloc(&e->d_scratch_stats, smmc_stats_bytes(SMMC_MAX_BINS));
+  if (err == hipSuccess) err = e->d_scratch_stats.reserve(smmc_stats_bytes(SMMC_MAX_BINS), nullptr);  // allocated once
   if (err == hipSuccess && (stats || hist)) {
-    rc = smmc_engine_values_stats(e, d, n, below_threshold, n_bins, hist_lo, hist_hi, e->d_scratch_stats);
+    rc = smmc_engine_values_stats(e, d, n, below_threshold, n_bins, hist_lo, hist_hi, e->d_scratch_stats.p);
     if (rc == SMMC_OK) {
       std::vector<char> rec(smmc_stats_bytes(n_bins));
-      err = hipMemcpyAsync(rec.data(), e->d_scratch_stats, rec.size(), hipMemcpyDeviceToHost, e->stream);
+      err = hipMemcpyAsync(rec.data(), e->d_scratch_stats.p, rec.size(), hipMemcpyDeviceToHost, e->stream);
       if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
       if (err == hipSuccess) {
         if (stats) std::memcpy(stats, rec.data(), sizeof(smmc_stats));
@@ -1481,7 +1373,6 @@ int smmc_engine_host_values_summary(smmc_engine *e, const float *host_values, ui
   }
   if (err == hipSuccess && rc == SMMC_OK && quartiles) rc = smmc_engine_quartiles(e, d, n, quartiles);
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
   if (rc) return rc;
   if (err != hipSuccess) return fail(SMMC_ERR_HIP, "host_values_summary failed: %s", hipGetErrorString(err));
   return SMMC_OK;
@@ -1558,11 +1449,11 @@ int smmc_engine_set_progress(smmc_engine *e, smmc_progress_fn fn, void *user) {
 
 int smmc_engine_timing(smmc_engine *e, int enable) {
   if (!e) return fail(SMMC_ERR_INVALID, "engine is NULL");
-  if (enable && !e->d_clock) {
+  if (enable && !e->d_clock.p) {
     DeviceGuard guard(e->device);
     if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&e->d_clock), 2 * sizeof(unsigned long long)));
-    SMMC_HIP(hipMemsetAsync(e->d_clock, 0, 2 * sizeof(unsigned long long), e->stream));
+    SMMC_HIP(e->d_clock.reserve(2 * sizeof(unsigned long long), nullptr));  // allocated once
+    SMMC_HIP(hipMemsetAsync(e->d_clock.p, 0, 2 * sizeof(unsigned long long), e->stream));
   }
   e->timing = enable != 0;
   return SMMC_OK;
@@ -1571,12 +1462,12 @@ int smmc_engine_timing(smmc_engine *e, int enable) {
 int smmc_engine_kernel_clock(smmc_engine *e, double *ghz) {
   if (!e || !ghz) return fail(SMMC_ERR_INVALID, "NULL argument");
   *ghz = 0.0;
-  if (!e->d_clock) return SMMC_OK;  // timing was never enabled
+  if (!e->d_clock.p) return SMMC_OK;  // timing was never enabled
   DeviceGuard guard(e->device);
   if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
   unsigned long long h[2] = {0, 0};
-  SMMC_HIP(hipMemcpyAsync(h, e->d_clock, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  SMMC_HIP(hipMemsetAsync(e->d_clock, 0, sizeof h, e->stream));
+  SMMC_HIP(hipMemcpyAsync(h, e->d_clock.p, sizeof h, hipMemcpyDeviceToHost, e->stream));
+  SMMC_HIP(hipMemsetAsync(e->d_clock.p, 0, sizeof h, e->stream));
   SMMC_HIP(hipStreamSynchronize(e->stream));
   if (h[1]) *ghz = static_cast<double>(h[0]) / static_cast<double>(h[1]) * 0.1;  // s_memrealtime ticks at 100 MHz
   return SMMC_OK;
@@ -1669,18 +1560,14 @@ bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_
 }
 KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s) { return make_args(e, s); }
 EngineView engine_view(const smmc_engine *e) {
-  return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials,
-                    e->timing ? e->d_clock : nullptr};
+  return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials.p,
+                    e->timing ? e->d_clock.p : nullptr};
 }
 EngineExt *engine_ext(smmc_engine *e) { return &e->ext; }
-int engine_acc_begin(smmc_engine *e, unsigned long long **acc) {
-  const int rc = hist_acc_ready(e);
-  if (rc) return rc;
-  *acc = e->d_hist_spread;
-  e->hist_dirty = true;
+int engine_acc_lease(smmc_engine *e, ZeroLease *lease) {
+  SMMC_HIP(lease->take(e->hist_acc, sizeof(unsigned long long) * kHistSpread * SMMC_MAX_BINS, e->stream));
   return SMMC_OK;
 }
-void engine_acc_clean(smmc_engine *e) { e->hist_dirty = false; }
 int host_require_v3(const smmc_sim *s, const char *feature) {
   if (s->flags & (SMMC_FLAG_STREAM_REF | SMMC_FLAG_STREAM_V2))
     return fail(SMMC_ERR_INVALID, "%s counter stream v3 only (not SMMC_FLAG_STREAM_%s)", feature,
@@ -1712,8 +1599,9 @@ int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *piec
   if (n_pieces > kMaxHostPieces) return fail(SMMC_ERR_INVALID, "%s: %d output pieces, at most %d", what, n_pieces, kMaxHostPieces);
   size_t total = 0;
   for (int i = 0; i < n_pieces; ++i) total += pieces[i].host ? pieces[i].bytes : 0;
-  char *d = nullptr;
-  if (total) SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
+  DeviceBuffer<char> mem;  // freed on every way out, behind the synchronisation below
+  SMMC_HIP(mem.reserve(total, nullptr));
+  char *const d = mem.p;
   void *dev[kMaxHostPieces];
   size_t at = 0;
   for (int i = 0; i < n_pieces; ++i) {
@@ -1725,7 +1613,6 @@ int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *piec
   hipError_t err = hipStreamSynchronize(e->stream);  // also after a failure: nothing of the call may outlive its buffer
   for (int i = 0; i < n_pieces; ++i)
     if (rc == SMMC_OK && err == hipSuccess && dev[i]) err = hipMemcpy(pieces[i].host, dev[i], pieces[i].bytes, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
   if (rc) return rc;
   if (err != hipSuccess) return fail(SMMC_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
   return SMMC_OK;

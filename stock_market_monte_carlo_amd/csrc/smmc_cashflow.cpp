@@ -2,7 +2,7 @@
 // contribution schedules with depletion statistics.
 //
 // A translation unit of its own: smmc_capi.cpp owns struct smmc_engine and never calls into this file; what is
-// needed of an engine comes through smmc_internal.h (engine_view, engine_acc_begin, ...), and what this file keeps
+// needed of an engine comes through smmc_internal.h and smmc_host.h (engine_view, engine_acc_lease, ...), and what this file keeps
 // per engine -- the staged schedule -- hangs in the engine's extension slot (engine_ext), released by
 // smmc_engine_destroy.  The launch is a wave walk, and its host side is the shared one: host_require_v3,
 // host_wave_walk_grid, host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in
@@ -14,6 +14,7 @@
 #include <cstring>
 #include <new>
 
+#include "smmc_host.h"
 #include "smmc_internal.h"
 
 namespace {
@@ -36,8 +37,8 @@ static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>
 // call before it on the engine stream.
 constexpr int kSlots = 4;
 struct CashflowState {
-  float *h_slots = nullptr;  // page-locked, kSlots x 2 x kStrideMax
-  float *d_schedule = nullptr;  // 2 x kStrideMax
+  smmc::PinnedBuffer<float> h_slots;     // page-locked, kSlots x 2 x kStrideMax
+  smmc::DeviceBuffer<float> d_schedule;  // 2 x kStrideMax
   hipEvent_t uploaded[kSlots] = {nullptr, nullptr, nullptr, nullptr};
   bool in_flight[kSlots] = {false, false, false, false};
   int next = 0;
@@ -48,9 +49,7 @@ void release_state(void *p) {
   if (!st) return;
   for (hipEvent_t ev : st->uploaded)
     if (ev) (void)hipEventDestroy(ev);
-  if (st->h_slots) (void)hipHostFree(st->h_slots);
-  if (st->d_schedule) (void)hipFree(st->d_schedule);
-  delete st;
+  delete st;  // the two buffers with it
 }
 
 // Device must be current.
@@ -62,12 +61,12 @@ int state_of(smmc_engine *e, CashflowState **out) {
     ext->state = st;
     ext->release = release_state;
     const size_t bytes = sizeof(float) * 2u * kStrideMax;
-    SMMC_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->h_slots), bytes * kSlots, hipHostMallocDefault));
-    SMMC_HIP(hipMalloc(reinterpret_cast<void **>(&st->d_schedule), bytes));
+    SMMC_HIP(st->h_slots.reserve(bytes * kSlots, nullptr));  // both allocated once
+    SMMC_HIP(st->d_schedule.reserve(bytes, nullptr));
     for (hipEvent_t &ev : st->uploaded) SMMC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
   *out = static_cast<CashflowState *>(ext->state);
-  if (!(*out)->h_slots || !(*out)->d_schedule || !(*out)->uploaded[kSlots - 1])
+  if (!(*out)->h_slots.p || !(*out)->d_schedule.p || !(*out)->uploaded[kSlots - 1])
     return host_fail(SMMC_ERR_HIP, "the engine's cash-flow staging buffers could not be allocated earlier");
   return SMMC_OK;
 }
@@ -190,25 +189,25 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
     if (st->in_flight[slot]) SMMC_HIP(hipEventSynchronize(st->uploaded[slot]));
     st->in_flight[slot] = false;
     const uint32_t stride = (sim->n_periods + 7u) & ~7u;
-    float *h = st->h_slots + static_cast<size_t>(slot) * 2u * kStrideMax;
+    float *h = st->h_slots.p + static_cast<size_t>(slot) * 2u * kStrideMax;
     for (uint32_t t = 0; t < stride; ++t) {
       h[t] = t < sim->n_periods ? amount_at(cf, t) : 0.0f;
       h[stride + t] = t < sim->n_periods ? fraction_at(cf, t) : 0.0f;
     }
-    SMMC_HIP(hipMemcpyAsync(st->d_schedule, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
+    SMMC_HIP(hipMemcpyAsync(st->d_schedule.p, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
     SMMC_HIP(hipEventRecord(st->uploaded[slot], view.stream));
     st->in_flight[slot] = true;
     st->next = (slot + 1) % kSlots;
-    c.schedule = st->d_schedule;
+    c.schedule = st->d_schedule.p;
     c.stride = stride;
   }
   a.d_final = d_final;
-  unsigned long long *acc = nullptr;
-  const bool use_acc = (d_stats && sim->n_bins) || d_depleted_at;
-  if (use_acc) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_begin(e, &acc);
+  smmc::ZeroLease lease;
+  if ((d_stats && sim->n_bins) || d_depleted_at) {  // zero now, and zero again after the finalize launches below
+    rc = smmc::engine_acc_lease(e, &lease);
     if (rc) return rc;
   }
+  unsigned long long *const acc = lease.acc();
   if (d_stats) {
     a.partials = view.d_partials;
     a.d_hist = sim->n_bins ? acc : nullptr;
@@ -225,7 +224,7 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   if (d_depleted_at)
     SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
                                                reinterpret_cast<unsigned long long *>(d_depleted_at), view.stream));
-  if (use_acc) smmc::engine_acc_clean(e);
+  lease.finalize_queued();
   return SMMC_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "smmc_host.h"
 #include "smmc_internal.h"
 
 namespace {
@@ -125,12 +126,12 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
   xa.d_first_below = out->first_below;
   xa.d_first_reach = out->first_reach;
   a.d_final = out->final;
-  unsigned long long *acc = nullptr;
-  const bool use_acc = ((out->stats || out->drawdown_stats) && sim->n_bins) || out->first_below_at || out->first_reach_at;
-  if (use_acc) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_begin(e, &acc);
+  smmc::ZeroLease lease;
+  if (((out->stats || out->drawdown_stats) && sim->n_bins) || out->first_below_at || out->first_reach_at) {
+    rc = smmc::engine_acc_lease(e, &lease);  // zero now, and zero again after the finalize launches below
     if (rc) return rc;
   }
+  unsigned long long *const acc = lease.acc();
   if (out->stats) {
     a.partials = view.d_partials;
     a.d_hist = sim->n_bins ? acc : nullptr;
@@ -159,7 +160,7 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
   if (out->first_reach_at)
     SMMC_HIP(smmc::launch_finalize_depleted(acc + kAccReachAt, sim->n_periods + 1u,
                                                reinterpret_cast<unsigned long long *>(out->first_reach_at), view.stream));
-  if (use_acc) smmc::engine_acc_clean(e);
+  lease.finalize_queued();
   return SMMC_OK;
 }
 

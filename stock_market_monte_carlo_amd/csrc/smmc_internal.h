@@ -33,7 +33,7 @@ struct KernelArgs {
   float *d_chunk_mean;   // nullable
   float *d_chunk_var;    // nullable
   BlockPartial *partials;        // nullable => no statistics
-  unsigned long long *d_hist;    // nullable; n_bins counters, pre-zeroed, in the packed record
+  unsigned long long *d_hist;    // nullable; n_bins counters, zero before the launch: the engine's accumulator, folded by finalize
   uint32_t n_bins;
   float hist_lo, hist_hi;
   double hist_inv;       // (double)n_bins / ((double)hi - (double)lo), computed on the host
@@ -122,7 +122,7 @@ hipError_t launch_radix_pick(int pass, uint32_t n_ranks, SelectState *st, unsign
 hipError_t launch_paths(const KernelArgs &a, int div, uint32_t grid, size_t lds_bytes,
                         hipStream_t stream);
 // hist_acc: `spread` copies of n_bins bucket counts accumulated by the launch before; folded into the record and zeroed
-// again (the engine keeps the array zero between launches: smmc_capi.cpp, hist_acc_ready)
+// again (the engine keeps the array zero between launches: smmc_host.h, ZeroLease)
 hipError_t launch_finalize(const BlockPartial *partials, uint32_t n_partials, smmc_stats *d_stats,
                            uint32_t n_bins, hipStream_t stream, unsigned long long *hist_acc, uint32_t spread);
 hipError_t launch_keepdata(const KernelArgs &a, bool exact_div, int tile, int waves, uint32_t grid,
@@ -267,10 +267,7 @@ bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_
 KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
 EngineView engine_view(const smmc_engine *e);
 EngineExt *engine_ext(smmc_engine *e);
-// The engine's zeroed accumulator (kHistSpread x SMMC_MAX_BINS counters; a launch that adds into it must have its
-// finalize put it back to zero): *acc is ready, and marked dirty until engine_acc_clean says the finalize is queued.
-int engine_acc_begin(smmc_engine *e, unsigned long long **acc);
-void engine_acc_clean(smmc_engine *e);
+// (the engine's zeroed accumulator is leased through smmc_host.h: ZeroLease, engine_acc_lease)
 // smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
 // smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around

@@ -254,6 +254,56 @@ int main() {
       smmc_engine_destroy(e);
     }
   }
+  // 5c. stale buckets after a failure, with a bucket-less call in between: the fold of a bucketed call fails to enqueue
+  //     (counts are left in the accumulator), then a call WITHOUT buckets succeeds -- it never takes the accumulator, so
+  //     it must not take the mark off either -- and the next bucketed call still has to clear the array first
+  {
+    smmc_engine *e = nullptr;
+    EXPECT(smmc_engine_create(0, nullptr, &e) == SMMC_OK);
+    if (e) {
+      EXPECT(smmc_engine_set_table(e, table.data(), uint32_t(table.size())) == SMMC_OK);
+      const uint64_t n = 70001;
+      smmc_sim s = make_sim(SMMC_MODE_TABLE, 78, 9, n, 360, 64);
+      std::vector<float> out(n);
+      std::vector<uint64_t> hist(64), want_hist;
+      smmc_stats st, want, none;
+      expected_record(s, &want, want_hist);
+      fake_launch_fail_finalize(1);
+      EXPECT(smmc_engine_simulate_to_host(e, &s, out.data(), nullptr, nullptr, nullptr, &st, hist.data()) != SMMC_OK);
+      fake_launch_fail_finalize(0);
+      EXPECT(smmc_engine_values_stats(e, nullptr, 0, 0.f, 0, 0.f, 1.f, &none) == SMMC_OK && none.count == 0);  // "device" memory is the host's
+      EXPECT(smmc_engine_simulate_to_host(e, &s, out.data(), nullptr, nullptr, nullptr, &st, hist.data()) == SMMC_OK);
+      EXPECT(hist == want_hist && st.count == n && st.below == want.below);
+      smmc_engine_destroy(e);
+    }
+  }
+  // 5d. a staging buffer that has to grow while the device is out of memory: an error, not a crash; the same call
+  //     succeeds once memory is back; a call of the same shape allocates nothing more; and smmc_engine_destroy gives
+  //     back every allocation the engine made
+  {
+    const size_t live_before = fake_hip_live_allocations();
+    smmc_engine *e = nullptr;
+    EXPECT(smmc_engine_create(0, nullptr, &e) == SMMC_OK);
+    if (e) {
+      EXPECT(smmc_engine_set_table(e, table.data(), uint32_t(table.size())) == SMMC_OK);
+      smmc_sim small = make_sim(SMMC_MODE_TABLE, 79, 0, 3000, 36, 16), s = make_sim(SMMC_MODE_TABLE, 79, 0, 50000, 36, 16);
+      std::vector<float> out(s.n_paths), cm(s.n_paths / 256 + 1), cv(s.n_paths / 256 + 1);
+      std::vector<uint64_t> hist(16), want_hist;
+      smmc_stats st, want;
+      expected_record(s, &want, want_hist);
+      EXPECT(smmc_engine_simulate_to_host(e, &small, out.data(), cm.data(), cv.data(), nullptr, &st, hist.data()) == SMMC_OK);
+      fake_hip_fail_mallocs_on(0);
+      EXPECT(smmc_engine_simulate_to_host(e, &s, out.data(), cm.data(), cv.data(), nullptr, &st, hist.data()) == SMMC_ERR_HIP);
+      fake_hip_fail_mallocs_on(-1);
+      EXPECT(smmc_engine_simulate_to_host(e, &s, out.data(), cm.data(), cv.data(), nullptr, &st, hist.data()) == SMMC_OK);
+      EXPECT(values_in_place(out, s) && hist == want_hist && st.count == s.n_paths && st.below == want.below);
+      const size_t live_steady = fake_hip_live_allocations();
+      EXPECT(smmc_engine_simulate_to_host(e, &s, out.data(), cm.data(), cv.data(), nullptr, &st, hist.data()) == SMMC_OK);
+      EXPECT(fake_hip_live_allocations() == live_steady && hist == want_hist);
+      smmc_engine_destroy(e);
+    }
+    EXPECT(fake_hip_live_allocations() == live_before);
+  }
 
   // 6. the RCCL merge with G distinct devices (FAKE_RCCL=1: tests/cpp/fake_rccl.cpp is the librccl.so.1 on the library
   //    path -- host memory, completes inside ncclGroupEnd, refuses ranks that disagree).  What real RCCL would show as a

@@ -126,15 +126,23 @@ def test_struct_sizes_agree_with_the_c_compiler(tmp_path):
 
 
 def test_every_environment_knob_of_the_library_is_documented():
-    """Every SMMC_* variable the product reads (getenv in csrc/) has a row in INTEGRATION.md's table."""
+    """Every SMMC_* variable the product reads (getenv, or the range-checked env_long, in csrc/ -- the name a string
+    literal at the call) has a row in INTEGRATION.md's table; and they are exactly the ones below: a knob that is
+    added, dropped or read in a way this search does not see fails here."""
     import re
+    known = {"SMMC_BLOCKS_PER_CU", "SMMC_BLOCKS_READ", "SMMC_DEVICE_MAP", "SMMC_GROUP_MERGE", "SMMC_HOST_CHUNK_PATHS", "SMMC_JSON",
+             "SMMC_KEEPDATA_BLOCKS_PER_CU", "SMMC_KEEPDATA_COMB_ILP", "SMMC_KEEPDATA_COMB_WAVES", "SMMC_KEEPDATA_K",
+             "SMMC_KEEPDATA_KERNEL", "SMMC_KEEPDATA_TILE", "SMMC_KEEPDATA_WAVES", "SMMC_MODE", "SMMC_PIN_HOST",
+             "SMMC_RADIX_BLOCKS_PER_CU", "SMMC_RADIX_MATCH", "SMMC_REF_GENERIC_BLOCKS_PER_CU", "SMMC_REF_KERNEL",
+             "SMMC_REF_TRAJ_ROWS", "SMMC_SEED", "SMMC_STATS_BLOCKS_PER_CU", "SMMC_STATS_HIST_COPIES", "SMMC_STREAM", "SMMC_TABLE",
+             "SMMC_VERBOSE"}
     names = set()
     csrc = os.path.join(ROOT, "stock_market_monte_carlo_amd", "csrc")
     for dirpath, _, files in os.walk(csrc):
         for fn in files:
             if fn.endswith((".cpp", ".hip", ".h")):
-                names |= set(re.findall(r'getenv\("(SMMC_[A-Z0-9_]+)"\)', open(os.path.join(dirpath, fn)).read()))
-    assert len(names) >= 15
+                names |= set(re.findall(r'(?:getenv|env_long)\("(SMMC_[A-Z0-9_]+)"[,)]', open(os.path.join(dirpath, fn)).read()))
+    assert names == known, sorted(names ^ known)
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     missing = sorted(n for n in names if n not in doc)
     assert not missing, missing
