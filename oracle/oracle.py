@@ -86,6 +86,7 @@ def lib():
                                      C.c_void_p, C.c_int]
         L.orc_counter_path_returns.argtypes = [C.POINTER(Params), C.c_uint64, C.c_void_p]
         L.orc_counter_path_indices.argtypes = [C.POINTER(Params), C.c_uint64, C.c_void_p]
+        L.orc_counter_indices.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int]
         L.orc_draws_per_block.restype = C.c_uint32
         L.orc_draws_per_block.argtypes = [C.c_int32, C.c_uint32]
         L.orc_chunk_mean_var.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -282,6 +283,13 @@ def counter_path_returns(params, path):
 def counter_path_indices(params, path):
     out = np.empty(params.n_periods, dtype=np.uint32)
     lib().orc_counter_path_indices(C.byref(params), C.c_uint64(path), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def counter_indices(params, n_threads=0):
+    """counter_path_indices of every path of params: [n_paths, n_periods]."""
+    out = np.empty((int(params.n_paths), int(params.n_periods)), dtype=np.uint32)
+    lib().orc_counter_indices(C.byref(params), out.ctypes.data_as(C.c_void_p), n_threads)
     return out
 
 

@@ -67,6 +67,7 @@ int main(void) {
   const uint32_t periods[] = {0, 1, 3, 4, 5, 7, 8, 9, 15, 16, 17, 360};
   uint64_t *hist = malloc(sizeof(uint64_t) * 4096);
   float *traj = malloc(sizeof(float) * 300 * 361);
+  uint32_t *all_idx = malloc(sizeof(uint32_t) * 300 * 360);
   for (int mode = 0; mode < 2; mode++)
     for (unsigned tl = 0; tl < 3; tl++)
       for (unsigned pi = 0; pi < 12; pi++) {
@@ -100,6 +101,8 @@ int main(void) {
         if (mode == 0) {
           orc_counter_path_indices(&p, p.first_path + 5, ii);
           for (uint32_t k = 0; k < p.n_periods; k++) EXPECT(ii[k] < p.table_len && rr[k] == table[ii[k]]);
+          orc_counter_indices(&p, all_idx, 2);
+          EXPECT(memcmp(all_idx + (size_t)5 * p.n_periods, ii, sizeof(uint32_t) * p.n_periods) == 0);
         }
         EXPECT(orc_counter_mc(&p, 0, 0, &st, 0, 1) == 0);  /* every output optional */
         p.n_paths = 0;
@@ -143,7 +146,7 @@ int main(void) {
   EXPECT(orc_div100_mismatches(0x3f800000u, 0x3f800000u + 100000u, &first_bad) == 0);
   EXPECT(orc_div100_mismatches(0u, 4096u, &first_bad) > 0);  /* denormal inputs: outside the proven range */
 
-  free(table); free(fin); free(hist); free(traj);
+  free(table); free(fin); free(hist); free(traj); free(all_idx);
   printf(fails ? "oracle_driver: %d FAILURES\n" : "oracle_driver: ok\n", fails);
   return fails != 0;
 }

@@ -450,6 +450,18 @@ ORC_API void orc_counter_path_indices(const orc_params *p, uint64_t path, uint32
   }
 }
 
+/* orc_counter_path_indices for paths first_path .. first_path + n_paths - 1: indices is path-major,
+ * n_paths x n_periods.  Parallelised over paths when OpenMP is on. */
+ORC_API void orc_counter_indices(const orc_params *p, uint32_t *indices, int n_threads) {
+  int64_t n = (int64_t)p->n_paths;
+#ifdef _OPENMP
+  if (n_threads <= 0) n_threads = omp_get_num_procs();
+#pragma omp parallel for schedule(static) num_threads(n_threads)
+#endif
+  for (int64_t i = 0; i < n; i++)
+    orc_counter_path_indices(p, p->first_path + (uint64_t)i, indices + (size_t)i * p->n_periods);
+}
+
 static float counter_one_path(const orc_params *p, uint64_t path, float *trajectory) {
   const uint32_t D = orc_draws_per_block(p->mode, p->table_len);
   float total = p->initial_capital;

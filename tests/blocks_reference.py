@@ -55,10 +55,41 @@ def finals(oracle, table, seed, first_path, n_paths, n_periods, block_len, capit
     return out
 
 
+def starts_bulk(oracle, table, seed, first_path, n_paths, n_blocks):
+    """[n_paths, n_blocks] block starts of paths first_path ..: starts() of every path in one oracle call."""
+    p = oracle.make_params(oracle.MODE_TABLE, n_blocks, n_paths, seed, first_path=first_path, table=table)
+    return oracle.counter_indices(p).astype(np.int64)
+
+
+def finals_bulk(oracle, table, seed, first_path, n_paths, n_periods, block_len, capital=CAPITAL):
+    """finals() for many paths: starts_bulk and the oracle's update_fund as three numpy binary32 operations per
+    period (100.0f + r, the product, the divide; numpy never fuses).  The first and last paths are compared with finals()."""
+    table = np.asarray(table, dtype=f32)
+    T = int(table.size)
+    s = starts_bulk(oracle, table, seed, first_path, n_paths, -(-n_periods // block_len))
+    v = np.full(n_paths, capital, f32)
+    with np.errstate(all="ignore"):
+        for t in range(n_periods):
+            r = table[(s[:, t // block_len] + t % block_len) % T]
+            v = (v * (f32(100.0) + r)) / f32(100.0)
+    assert v.dtype == f32
+    head, tail = min(n_paths, 8), max(n_paths - 8, 0)
+    assert np.array_equal(v[:head].view(np.uint32), finals(oracle, table, seed, first_path, head, n_periods, block_len, capital).view(np.uint32))
+    assert np.array_equal(v[tail:].view(np.uint32),
+                          finals(oracle, table, seed, first_path + tail, n_paths - tail, n_periods, block_len, capital).view(np.uint32))
+    return v
+
+
 def result(oracle, table, n_paths, n_periods, block_len, seed=SEED, first_path=FIRST_PATH, capital=CAPITAL, n_bins=BINS,
            lo=LO, hi=HI, below=BELOW):
     """dict(final, stats, hist, chunk_mean, chunk_var) of one request."""
     final = finals(oracle, table, seed, first_path, n_paths, n_periods, block_len, capital)
+    return record_of(oracle, final, n_bins, lo, hi, below)
+
+
+def record_of(oracle, final, n_bins=BINS, lo=LO, hi=HI, below=BELOW):
+    """result()'s dict for final values already computed (a prefix of a longer run's: paths do not depend on n_paths)."""
+    n_paths = int(final.size)
     st, hist = oracle.values_stats(final, below, n_bins, lo, hi)
     if n_paths:
         cm, cv = oracle.chunk_mean_var(final)

@@ -4,6 +4,7 @@ CPU oracle's per-path returns: the reference of tests/test_cashflow_cpu.py and t
 Every operation is one binary32 rounding (numpy float32 arithmetic never fuses).  The oracle's returns r reproduce
 the engine's multiplier as 100.0f + r, and total * a / 100 exactly, for a in [50, 200]: the bundled table
 (-15.1 .. +14.3 %), the tests' 3001-entry table (+-25 %) and the default Gaussian stay inside that."""
+import ctypes
 import functools
 
 import numpy as np
@@ -24,7 +25,12 @@ def big_table():
 def returns(oracle, mode, table, n_paths, n_periods, first_path=FIRST_PATH, seed=SEED):
     """[n_paths, n_periods] percent returns of paths first_path .. (counter stream v3)."""
     p = oracle.make_params(mode, n_periods, n_paths, seed, first_path=first_path, initial_capital=CAPITAL, table=table)
-    return np.stack([oracle.counter_path_returns(p, first_path + i) for i in range(n_paths)])
+    R = np.empty((n_paths, n_periods), dtype=f32)
+    # oracle.counter_path_returns row by row, written in place: a launch that walks its chunks twice has 1e5 paths
+    fill, ref, row, step = oracle.lib().orc_counter_path_returns, ctypes.byref(p), R.ctypes.data, 4 * n_periods
+    for i in range(n_paths):
+        fill(ref, first_path + i, row + i * step)
+    return R
 
 
 def simulate(R, amount=0.0, fraction=0.0, floor=0.0, capital=CAPITAL):
