@@ -501,6 +501,20 @@ int smmc_engine_kernel_clock(smmc_engine *e, double *ghz);
  * IEEE x / 100.0f.  Synchronous. */
 int smmc_engine_selftest(smmc_engine *e, uint32_t bits_lo, uint32_t bits_hi, uint64_t *div_mismatches);
 
+/* Device self-test of the draws: what the kernels make of GIVEN random words.  Item i is the four 32-bit words at
+ * words[4 i ..] (host memory), in the place of one Philox block's output; out (host memory) receives per item the
+ * *draws_per_item multipliers a = 100 + return that a path would compound with: 8 in table mode with a table of up
+ * to 2048 entries, else 4.  Mode, SMMC_FLAG_STREAM_V2, gauss_mean, gauss_std and the engine's table are taken from
+ * `sim` exactly as smmc_engine_simulate takes them (seed, paths, periods and the statistics fields are not used),
+ * and the words go through the same device functions and the same staged tables as in every simulation kernel, so
+ * that a test can reach every bin of the Gaussian radius table, every sector of its angle table and every digit
+ * boundary of a table draw on purpose.  form 0 draws one item at a time, form 1 two together (the order of the
+ * kernels that interleave two Philox blocks); the values are the same.  SMMC_FLAG_STREAM_REF is refused (its
+ * draw is not made of Philox words).  n = 0 sets *draws_per_item (nullable) and touches nothing else; n <= 2^28.
+ * Copies in and out itself on the engine's stream.  Synchronous. */
+int smmc_engine_selftest_draws(smmc_engine *e, const smmc_sim *sim, const uint32_t *words, uint64_t n, int form,
+                               float *out, uint32_t *draws_per_item);
+
 /* Which divide-by-100 a launch of `sim` uses (the result never depends on it): SMMC_DIV_FAST, the
  * reciprocal-multiply form, when the returns table (or mean +- 7 std), the capital and the number of
  * periods prove that no path can leave its domain; SMMC_DIV_CHECKED (final-value launches only)

@@ -87,6 +87,8 @@ def lib():
         L.orc_counter_path_returns.argtypes = [C.POINTER(Params), C.c_uint64, C.c_void_p]
         L.orc_counter_path_indices.argtypes = [C.POINTER(Params), C.c_uint64, C.c_void_p]
         L.orc_counter_indices.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int]
+        L.orc_multipliers_of_words.argtypes = [C.POINTER(Params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.orc_philox4x32_10_bulk.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.orc_draws_per_block.restype = C.c_uint32
         L.orc_draws_per_block.argtypes = [C.c_int32, C.c_uint32]
         L.orc_chunk_mean_var.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -136,6 +138,30 @@ def philox4x32_10(ctr, key):
     lib().orc_philox4x32_10(c.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p),
                             out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def philox4x32_10_bulk(ctrs, key):
+    """philox4x32_10 of every row of ctrs (n, 4): (n, 4) uint32."""
+    c = np.ascontiguousarray(ctrs, dtype=np.uint32)
+    assert c.ndim == 2 and c.shape[1] == 4
+    k = np.asarray(key, dtype=np.uint32)
+    out = np.empty_like(c)
+    lib().orc_philox4x32_10_bulk(c.ctypes.data_as(C.c_void_p), C.c_uint64(c.shape[0]), k.ctypes.data_as(C.c_void_p),
+                                 out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def multipliers_of_words(params, words, want_indices=False):
+    """What the path loop makes of given Philox words: words (n, 4) uint32 -> multipliers float32 (n, draws per
+    block); with want_indices (table mode) also the table indices drawn, uint32 of the same shape."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    assert w.ndim == 2 and w.shape[1] == 4
+    d = int(lib().orc_draws_per_block(params.mode, params.table_len))
+    out = np.empty((w.shape[0], d), dtype=np.float32)
+    idx = np.zeros((w.shape[0], d), dtype=np.uint32) if want_indices else None
+    lib().orc_multipliers_of_words(C.byref(params), w.ctypes.data_as(C.c_void_p), C.c_uint64(w.shape[0]),
+                                   out.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if want_indices else None)
+    return (out, idx) if want_indices else out
 
 
 def box_muller_scaled(ua, ub, scale, shift):

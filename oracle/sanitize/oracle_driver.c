@@ -104,6 +104,26 @@ int main(void) {
           orc_counter_indices(&p, all_idx, 2);
           EXPECT(memcmp(all_idx + (size_t)5 * p.n_periods, ii, sizeof(uint32_t) * p.n_periods) == 0);
         }
+        {
+          /* given words: the corners of the word range in every position, both streams, every table length */
+          uint32_t w[8 * 4], wi[8 * 8];
+          float wm[8 * 8];
+          for (unsigned k = 0; k < 8; k++)
+            for (unsigned j = 0; j < 4; j++) w[4 * k + j] = corners[(k + 3 * j) % 8];
+          const uint32_t D = orc_draws_per_block(p.mode, p.table_len);
+          orc_multipliers_of_words(&p, w, 8, wm, wi);
+          for (uint32_t k = 0; k < 8 * D; k++) {
+            EXPECT(isfinite(wm[k]));
+            if (mode == 0) EXPECT(wi[k] < p.table_len && wm[k] == 100.0f + table[wi[k]]);
+          }
+          orc_multipliers_of_words(&p, w, 8, wm, 0);
+          orc_multipliers_of_words(&p, w, 0, wm, wi);
+          uint32_t pw[8];
+          const uint32_t two[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0, 0};
+          orc_philox4x32_10_bulk(two, 2, key, pw);
+          EXPECT(pw[0] == 0x408f276du && pw[3] == 0x6d5451fdu);
+          orc_philox4x32_10_bulk(two, 0, key, pw);
+        }
         EXPECT(orc_counter_mc(&p, 0, 0, &st, 0, 1) == 0);  /* every output optional */
         p.n_paths = 0;
         EXPECT(orc_counter_mc(&p, fin, hist, &st, 0, 1) == 0 && st.count == 0);

@@ -381,27 +381,15 @@ static void digits4(uint32_t h, uint32_t l, uint32_t T, uint32_t idx[4]) {
   idx[3] = (uint32_t)(((uint64_t)h * T) >> 32);
 }
 
-/* The draws of Philox block `blk` of one path: orc_draws_per_block() of them.  out[] are the period
+/* The draws that the four words u of one Philox block give: orc_draws_per_block() of them.  out[] are the period
  * returns in percent, mult[] the multipliers a = 100 + return the compounding step uses (period p
  * uses draw p % D of block p / D).  Table mode and Gaussian v2: the return is drawn (table entry;
  * fma(std, z, mean)) and a = 100.0f + return.  Gaussian v3: the MULTIPLIER is drawn,
  * a = fma(r std, cos theta, 100.0f + mean), and the return is defined as a - 100.0f (exact for
  * a in [50, 200], where update_fund(total, return) then reproduces total * a / 100 bit for bit). */
-static void path_returns_block(const orc_params *p, uint64_t path, uint32_t blk, float out[8],
-                               uint32_t idx_out[8], float mult[8]) {
-  /* counter: stream v3 counts blocks in the FIRST word, (block, path_lo, path_hi, mode) -- on the device
-   * the first two Philox rounds then cost two instructions instead of four --, stream v2 in the third */
-  uint32_t ctr[4] = {(uint32_t)path, (uint32_t)(path >> 32), blk, (uint32_t)p->mode};
-  if (p->stream != 2) {
-    ctr[0] = blk;
-    ctr[1] = (uint32_t)path;
-    ctr[2] = (uint32_t)(path >> 32);
-  }
-  uint32_t key[2] = {(uint32_t)p->seed, (uint32_t)(p->seed >> 32)};
-  uint32_t u[4];
+static void draws_of_words(const orc_params *p, const uint32_t u[4], float out[8], uint32_t idx_out[8], float mult[8]) {
   float a[8];
   uint32_t n = orc_draws_per_block(p->mode, p->table_len);
-  orc_philox4x32_10(ctr, key, u);
   if (p->mode == ORC_MODE_TABLE) {
     uint32_t idx[8];
     if (n == 8) {
@@ -427,6 +415,44 @@ static void path_returns_block(const orc_params *p, uint64_t path, uint32_t blk,
   }
   if (mult)
     for (uint32_t j = 0; j < n; j++) mult[j] = a[j];
+}
+
+/* Philox block `blk` of one path, then draws_of_words. */
+static void path_returns_block(const orc_params *p, uint64_t path, uint32_t blk, float out[8],
+                               uint32_t idx_out[8], float mult[8]) {
+  /* counter: stream v3 counts blocks in the FIRST word, (block, path_lo, path_hi, mode) -- on the device
+   * the first two Philox rounds then cost two instructions instead of four --, stream v2 in the third */
+  uint32_t ctr[4] = {(uint32_t)path, (uint32_t)(path >> 32), blk, (uint32_t)p->mode};
+  if (p->stream != 2) {
+    ctr[0] = blk;
+    ctr[1] = (uint32_t)path;
+    ctr[2] = (uint32_t)(path >> 32);
+  }
+  uint32_t key[2] = {(uint32_t)p->seed, (uint32_t)(p->seed >> 32)};
+  uint32_t u[4];
+  orc_philox4x32_10(ctr, key, u);
+  draws_of_words(p, u, out, idx_out, mult);
+}
+
+/* The multipliers of n items of four GIVEN words each (words: n x 4), what the path loop makes of a Philox block's
+ * output: out is n x orc_draws_per_block().  The very function the path loop calls (draws_of_words); the device's
+ * counterpart is smmc_engine_selftest_draws.  indices (nullable, table mode): the table indices drawn, same shape. */
+ORC_API void orc_multipliers_of_words(const orc_params *p, const uint32_t *words, uint64_t n, float *out, uint32_t *indices) {
+  const uint32_t D = orc_draws_per_block(p->mode, p->table_len);
+  for (uint64_t i = 0; i < n; i++) {
+    float r[8], a[8];
+    uint32_t idx[8];
+    draws_of_words(p, words + 4 * i, r, idx, a);
+    for (uint32_t j = 0; j < D; j++) {
+      out[i * D + j] = a[j];
+      if (indices && p->mode == ORC_MODE_TABLE) indices[i * D + j] = idx[j];
+    }
+  }
+}
+
+/* n Philox blocks at once: ctrs n x 4 -> out n x 4 (tests that need the words of many blocks). */
+ORC_API void orc_philox4x32_10_bulk(const uint32_t *ctrs, uint64_t n, const uint32_t key[2], uint32_t *out) {
+  for (uint64_t i = 0; i < n; i++) orc_philox4x32_10(ctrs + 4 * i, key, out + 4 * i);
 }
 
 /* Writes the n_periods returns of global path `path` (percent). */

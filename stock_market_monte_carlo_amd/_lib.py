@@ -178,6 +178,8 @@ SYMBOLS = [
     ("smmc_engine_kernel_clock", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("smmc_engine_selftest", C.c_int,
      [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("smmc_engine_selftest_draws", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("smmc_engine_geometry", C.c_int,
      [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("smmc_engine_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.c_int]),

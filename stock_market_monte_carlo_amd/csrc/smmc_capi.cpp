@@ -25,8 +25,9 @@
 
 // The host-side test builds link this file against stand-ins for the kernel translation units that predate the
 // checkpoint kernel: where it is missing, smmc_engine_simulate_checkpoints reports that after its argument checks
-// (an error, never another path to a result).
+// (an error, never another path to a result).  The same holds for the draw self-test's kernel.
 namespace smmc {
+extern __attribute__((weak)) decltype(launch_draw_words) launch_draw_words;
 extern __attribute__((weak)) decltype(launch_checkpoints) launch_checkpoints;
 extern __attribute__((weak)) decltype(launch_finalize_checkpoints) launch_finalize_checkpoints;
 extern __attribute__((weak)) decltype(checkpoints_lds_bytes) checkpoints_lds_bytes;
@@ -1503,6 +1504,37 @@ int smmc_engine_selftest(smmc_engine *e, uint32_t bits_lo, uint32_t bits_hi, uin
   (void)hipFree(d);
   if (err != hipSuccess) return fail(SMMC_ERR_HIP, "self-test failed: %s", hipGetErrorString(err));
   if (div_mismatches) *div_mismatches = h;
+  return SMMC_OK;
+}
+
+int smmc_engine_selftest_draws(smmc_engine *e, const smmc_sim *sim, const uint32_t *words, uint64_t n, int form, float *out,
+                               uint32_t *draws_per_item) {
+  const int rc = check_sim(e, sim);
+  if (rc) return rc;
+  if (sim->flags & SMMC_FLAG_STREAM_REF)
+    return fail(SMMC_ERR_INVALID, "the draw self-test covers the counter streams (not SMMC_FLAG_STREAM_REF)");
+  if (form != 0 && form != 1) return fail(SMMC_ERR_INVALID, "form is %d: 0 (one item at a time) or 1 (two together)", form);
+  if (n > (1ull << 28)) return fail(SMMC_ERR_INVALID, "n %llu exceeds 2^28 items", static_cast<unsigned long long>(n));
+  if (n && (!words || !out)) return fail(SMMC_ERR_INVALID, "NULL words or out with n > 0");
+  const smmc::KernelArgs a = make_args(e, sim);
+  const uint32_t draws = smmc::keepdata_draws(a.table_len);
+  if (draws_per_item) *draws_per_item = draws;
+  if (!n) return SMMC_OK;
+  if (!smmc::launch_draw_words) return fail(SMMC_ERR_HIP, "this build carries no draw self-test kernel");
+  DeviceGuard guard(e->device);
+  if (!guard.ok) return fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+  const size_t words_bytes = static_cast<size_t>(n) * 4u * sizeof(uint32_t), out_bytes = static_cast<size_t>(n) * draws * sizeof(float);
+  smmc::DeviceBuffer<uint32_t> d_words;  // freed on every way out, behind the synchronisation below
+  smmc::DeviceBuffer<float> d_out;
+  SMMC_HIP(d_words.reserve(words_bytes, nullptr));
+  SMMC_HIP(d_out.reserve(out_bytes, nullptr));
+  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + smmc::kBlock - 1) / smmc::kBlock, e->max_grid));
+  hipError_t err = hipMemcpyAsync(d_words.p, words, words_bytes, hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess) err = smmc::launch_draw_words(a, d_words.p, n, form, d_out.p, grid, e->stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, e->stream);
+  const hipError_t sync = hipStreamSynchronize(e->stream);  // also after a failure: nothing of the call may outlive its buffers
+  if (err == hipSuccess) err = sync;
+  if (err != hipSuccess) return fail(SMMC_ERR_HIP, "draw self-test failed: %s", hipGetErrorString(err));
   return SMMC_OK;
 }
 

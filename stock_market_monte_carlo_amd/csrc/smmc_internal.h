@@ -137,6 +137,11 @@ size_t keepdata_comb_lds_bytes(uint32_t table_len, int waves, int stream);
 uint32_t keepdata_draws(uint32_t table_len);
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
                            hipStream_t stream);
+// draw_words_kernel (smmc_engine_selftest_draws): the multipliers that n >= 1 items of four given words yield in the
+// launch's mode -- d_words n x 4, d_out n x keepdata_draws(a.table_len) -- through the path kernels' own draw
+// functions and staged tables.  form 0: one item at a time; 1: two together (block_multipliers_multi's order).
+hipError_t launch_draw_words(const KernelArgs &a, const uint32_t *d_words, uint64_t n, int form, float *d_out, uint32_t grid,
+                             hipStream_t stream);
 size_t paths_lds_bytes(uint32_t table_len, uint32_t n_bins, int stream);
 // checkpoints_kernel (smmc_engine_simulate_checkpoints; counter stream v3 only).  a.partials: n_checkpoints x grid
 // entries, [checkpoint][workgroup]; a.d_hist: n_checkpoints x a.n_bins counters, zero before the launch.  A workgroup

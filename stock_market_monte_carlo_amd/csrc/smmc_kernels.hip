@@ -350,16 +350,11 @@ __device__ __forceinline__ void digits4(uint32_t h, uint32_t l, uint32_t T, uint
   idx[3] = __umulhi(h, T);
 }
 
-// The per-period multipliers a = 100.0f + r of Philox block `blk` of a path.
-template <int kMode, bool kDense, bool kUniformBlock = false>
-__device__ __forceinline__ void block_multipliers(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
-                                                  uint32_t path_lo, uint32_t path_hi, uint32_t blk,
-                                                  float (&a)[Draws<kMode, kDense>::value]) {
-  uint32_t u[4];
-  if constexpr (counter_v3(kMode))
-    philox4x32_10<kUniformBlock>(blk, path_lo, path_hi, mode_tag(kMode), k.key0, k.key1, dr, u);
-  else
-    philox4x32_10<false>(path_lo, path_hi, blk, mode_tag(kMode), k.key0, k.key1, dr, u);
+// The per-period multipliers a = 100.0f + r that the four Philox words u of one block give: everything a draw does
+// after Philox.  draw_words_kernel (the device self-test of the draws) feeds it chosen words.
+template <int kMode, bool kDense>
+__device__ __forceinline__ void multipliers_of_words(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
+                                                     const uint32_t (&u)[4], float (&a)[Draws<kMode, kDense>::value]) {
   if constexpr (is_table(kMode) && kDense) {
     uint32_t ia[4], ib[4];
     digits4(u[0], u[1], k.table_len, ia);
@@ -386,22 +381,25 @@ __device__ __forceinline__ void block_multipliers(const KernelArgs &k, const Dra
   }
 }
 
-// The multipliers of the N consecutive Philox blocks blk .. blk + N - 1 of a path, drawn TOGETHER:
-// interleaved Philox rounds, then all table gathers issued before the first is used.  The values are
-// those of N calls of block_multipliers.
-template <int kMode, bool kDense, int N, bool kUniformBlock = false>
-__device__ __forceinline__ void block_multipliers_multi(const KernelArgs &k, const DrawRegs &dr, const float *lds_table, uint32_t path_lo,
-                                                        uint32_t path_hi, uint32_t blk,
-                                                        float (&a)[N][Draws<kMode, kDense>::value]) {
-  uint32_t u[N][4];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    u[i][0] = counter_v3(kMode) ? blk + i : path_lo;
-    u[i][1] = counter_v3(kMode) ? path_lo : path_hi;
-    u[i][2] = counter_v3(kMode) ? path_hi : blk + i;
-    u[i][3] = mode_tag(kMode);
-  }
-  philox4x32_10_multi<N, kUniformBlock && counter_v3(kMode)>(u, k.key0, k.key1, dr);
+// The per-period multipliers a = 100.0f + r of Philox block `blk` of a path.
+template <int kMode, bool kDense, bool kUniformBlock = false>
+__device__ __forceinline__ void block_multipliers(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
+                                                  uint32_t path_lo, uint32_t path_hi, uint32_t blk,
+                                                  float (&a)[Draws<kMode, kDense>::value]) {
+  uint32_t u[4];
+  if constexpr (counter_v3(kMode))
+    philox4x32_10<kUniformBlock>(blk, path_lo, path_hi, mode_tag(kMode), k.key0, k.key1, dr, u);
+  else
+    philox4x32_10<false>(path_lo, path_hi, blk, mode_tag(kMode), k.key0, k.key1, dr, u);
+  multipliers_of_words<kMode, kDense>(k, dr, lds_table, u, a);
+}
+
+// multipliers_of_words for the words of N blocks, drawn TOGETHER: all table gathers issued before the first is
+// used.  The values are those of N calls of multipliers_of_words.
+template <int kMode, bool kDense, int N>
+__device__ __forceinline__ void multipliers_of_words_multi(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
+                                                           const uint32_t (&u)[N][4],
+                                                           float (&a)[N][Draws<kMode, kDense>::value]) {
   if constexpr (is_table(kMode) && kDense) {
     uint32_t idx[N][8];
 #pragma unroll
@@ -452,6 +450,24 @@ __device__ __forceinline__ void block_multipliers_multi(const KernelArgs &k, con
       bm3_finish(p[i][1], dr.shift100, a[i][2], a[i][3]);
     }
   }
+}
+
+// The multipliers of the N consecutive Philox blocks blk .. blk + N - 1 of a path, drawn TOGETHER:
+// interleaved Philox rounds, then multipliers_of_words_multi.  The values are those of N calls of block_multipliers.
+template <int kMode, bool kDense, int N, bool kUniformBlock = false>
+__device__ __forceinline__ void block_multipliers_multi(const KernelArgs &k, const DrawRegs &dr, const float *lds_table, uint32_t path_lo,
+                                                        uint32_t path_hi, uint32_t blk,
+                                                        float (&a)[N][Draws<kMode, kDense>::value]) {
+  uint32_t u[N][4];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    u[i][0] = counter_v3(kMode) ? blk + i : path_lo;
+    u[i][1] = counter_v3(kMode) ? path_lo : path_hi;
+    u[i][2] = counter_v3(kMode) ? path_hi : blk + i;
+    u[i][3] = mode_tag(kMode);
+  }
+  philox4x32_10_multi<N, kUniformBlock && counter_v3(kMode)>(u, k.key0, k.key1, dr);
+  multipliers_of_words_multi<kMode, kDense, N>(k, dr, lds_table, u, a);
 }
 
 template <int kMode, int kDiv, bool kDense>
@@ -1934,6 +1950,53 @@ __global__ __launch_bounds__(kBlock) void selftest_kernel(uint32_t lo, uint32_t 
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, bad);
 }
 
+// Device self-test of the draws: item i takes its four "Philox" words from words[4 i ..] and writes the
+// Draws<kMode, kDense>::value multipliers they give to out -- the tables staged and the registers made exactly
+// as the path kernels do (stage_tables at LDS offset 0, make_draw_regs), so that every radius bin, sector and
+// digit can be reached with chosen words instead of waiting for a seed that hits it.  form 0: one item per
+// trip through multipliers_of_words; form 1: items 2 i, 2 i + 1 through multipliers_of_words_multi<.., 2> (a
+// ragged last item is drawn with a copy of itself and stored once).
+template <int kMode, bool kDense>
+__global__ __launch_bounds__(kBlock) void draw_words_kernel(const KernelArgs k, const uint32_t *words, uint64_t n, int form,
+                                                            float *out) {
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *lds_table = reinterpret_cast<float *>(lds_raw);
+  stage_tables<kMode>(k, lds_table, kBlock);
+  __syncthreads();
+  const DrawRegs dr = make_draw_regs(k);
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (form == 0) {
+    for (uint64_t i = first; i < n; i += stride) {
+      uint32_t u[4];
+      float a[kDraws];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) u[j] = words[i * 4 + j];
+      multipliers_of_words<kMode, kDense>(k, dr, lds_table, u, a);
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j) out[i * kDraws + j] = a[j];
+    }
+  } else {
+    for (uint64_t i = first; 2 * i < n; i += stride) {
+      const uint64_t item[2] = {2 * i, 2 * i + 1 < n ? 2 * i + 1 : 2 * i};
+      uint32_t u[2][4];
+      float a[2][kDraws];
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) u[b][j] = words[item[b] * 4 + j];
+      multipliers_of_words_multi<kMode, kDense, 2>(k, dr, lds_table, u, a);
+#pragma unroll
+      for (int j = 0; j < kDraws; ++j) out[item[0] * kDraws + j] = a[0][j];
+      if (item[1] != item[0]) {
+#pragma unroll
+        for (int j = 0; j < kDraws; ++j) out[item[1] * kDraws + j] = a[1][j];
+      }
+    }
+  }
+}
+
 // ---- cash flows: a withdrawal or contribution after every period's return -------------------------
 //
 // smmc_engine_simulate_cashflow ("Cash flows"): the draws of paths_kernel, and after each period's
@@ -2261,6 +2324,7 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, true>),
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, false, false>),
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, true, false>),
+      reinterpret_cast<const void *>(draw_words_kernel<SMMC_MODE_GAUSSIAN, false>),
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -2303,6 +2367,31 @@ static hipError_t launch_paths_mode(const KernelArgs &a, int div, uint32_t grid,
 }
 
 bool table_is_dense(uint32_t table_len) { return table_len <= kDenseMaxTable; }
+
+template <int kMode, bool kDense>
+static hipError_t launch_draw_words_variant(const KernelArgs &a, const uint32_t *d_words, uint64_t n, int form, float *d_out,
+                                            uint32_t grid, hipStream_t stream) {
+  const size_t lds = draw_table_words(a.table_len, a.stream) * 4u;  // the tables alone, at LDS offset 0
+  hipError_t err = allow_lds(draw_words_kernel<kMode, kDense>, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((draw_words_kernel<kMode, kDense>), dim3(grid), dim3(kBlock), lds, stream, a, d_words, n, form, d_out);
+  return hipGetLastError();
+}
+
+// draw_words_kernel on n items (n >= 1): d_words n x 4, d_out n x keepdata_draws(a.table_len).  The mode ladder is
+// launch_paths's, so `dense` is decided by the same rule.
+hipError_t launch_draw_words(const KernelArgs &a, const uint32_t *d_words, uint64_t n, int form, float *d_out, uint32_t grid,
+                             hipStream_t stream) {
+  if (!n || !grid || (form != 0 && form != 1)) return hipErrorInvalidValue;
+  if (a.mode != SMMC_MODE_TABLE)
+    return a.stream == 2 ? launch_draw_words_variant<kModeGaussianV2, false>(a, d_words, n, form, d_out, grid, stream)
+                         : launch_draw_words_variant<SMMC_MODE_GAUSSIAN, false>(a, d_words, n, form, d_out, grid, stream);
+  if (a.stream == 2)
+    return table_is_dense(a.table_len) ? launch_draw_words_variant<kModeTableV2, true>(a, d_words, n, form, d_out, grid, stream)
+                                       : launch_draw_words_variant<kModeTableV2, false>(a, d_words, n, form, d_out, grid, stream);
+  return table_is_dense(a.table_len) ? launch_draw_words_variant<SMMC_MODE_TABLE, true>(a, d_words, n, form, d_out, grid, stream)
+                                     : launch_draw_words_variant<SMMC_MODE_TABLE, false>(a, d_words, n, form, d_out, grid, stream);
+}
 
 hipError_t launch_paths(const KernelArgs &a, int div, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
   if (a.mode != SMMC_MODE_TABLE)

@@ -276,6 +276,24 @@ class Engine:
         _lib.check(self._L.smmc_engine_selftest(self._h, bits_lo, bits_hi, C.byref(a)))
         return a.value
 
+    def selftest_draws(self, sim, words, form=0):
+        """The multipliers the device draws from GIVEN words in sim's mode and stream (smmc_engine_selftest_draws):
+        words is (n, 4) uint32, one item per row in the place of a Philox block's output; returns float32
+        (n, draws), draws = 8 for a table of up to 2048 entries, else 4.  form 0 draws one item at a time, form 1
+        two together as the kernels that interleave two blocks do.  Waits for the result."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if w.ndim != 2 or w.shape[1] != 4:
+            raise ValueError("words must have shape (n, 4)")
+        n, draws = int(w.shape[0]), C.c_uint32()
+        self._enter()
+        # the count first (n = 0 touches no buffer), then the call itself into an array of that width
+        _lib.check(self._L.smmc_engine_selftest_draws(self._h, C.byref(sim), None, 0, int(form), None, C.byref(draws)))
+        out = np.empty((n, draws.value), dtype=np.float32)
+        if n:
+            _lib.check(self._L.smmc_engine_selftest_draws(self._h, C.byref(sim), w.ctypes.data_as(C.c_void_p), n, int(form),
+                                                          out.ctypes.data_as(C.c_void_p), C.byref(draws)))
+        return out
+
     def sync(self):
         """Waits for everything the engine has enqueued.  A "torch" engine first re-binds to the caller's
         current stream (work enqueued on the stream of an earlier call stays ordered before it; a stream
