@@ -390,6 +390,86 @@ int smmc_engine_simulate_blocks_to_host(smmc_engine *e, const smmc_sim *sim, con
  * the IEEE divide. */
 int smmc_engine_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_blocks *blocks);
 
+/* ---- portfolios: jointly drawn assets, weights, periodic rebalancing ---------------------------- */
+
+/* K = n_assets return series per path, drawn JOINTLY, held with weights w_k and rebalanced to them every R =
+ * rebalance_every periods (R = 0: never, buy and hold).  Counter stream v3 only.  Two independent runs cannot be
+ * combined into this: table mode needs the same historical month for every asset, Gaussian mode a given correlation,
+ * and with rebalancing the value of a path is no function of the assets' separate products.
+ *
+ * Holdings, every operation one binary32 rounding:
+ *   at the start       h_k = fl(initial_capital * w_k)
+ *   period t = 1 .. P  h_k = fl(fl(h_k * a_k(t)) / 100.0f) for every asset: smmc_update_fund from its second rounding on
+ *   the value          V_t = ((h_0 + h_1) + h_2) + h_3, binary32 additions left to right over the K assets (K = 1:
+ *                      V_t = h_0); V_0 is the same sum of the initial holdings
+ *   rebalance          if R > 0 and t mod R == 0, the holdings of the following periods are h_k = fl(V_t * w_k)
+ *   the final value    V_P, formed BEFORE any rebalance at P; so are the final holdings
+ * V_p does not depend on n_periods.  With K = 1 and w_0 = 1 every R gives the plain path.
+ *
+ * Table mode: joint rows.  smmc_engine_set_asset_table gives the engine a table of n_rows x n_assets returns in percent,
+ * row-major, stored as a = 100.0f + r (as smmc_engine_set_table stores its table; the two tables are independent and
+ * a portfolio does not need the single-series one).  Period t of a path uses row i_t for EVERY asset, and i_t is
+ * exactly the index SMMC_MODE_TABLE draws for that path at period t - 1 (0-based) with T = n_rows: the same key, the
+ * same counter (t' / D, id lo, id hi, 0), the same digits; D = 8 for n_rows <= 2048, else 4.  With K = 1 and w_0 = 1
+ * the final values are bit-identical to smmc_engine_simulate's on the same column.
+ *
+ * Gaussian mode: correlated normals.  Asset j's STANDARD normals z_j for the periods 4b .. 4b + 3 are counter stream
+ * v3's Box-Muller draws of the Philox block (b, id lo, id hi, 1 + 2 j) with the launch's key, taken with scale 1.0f and
+ * shift 0.0f: asset 0 reads the very words of the plain Gaussian stream; odd fourth words belong to Gaussian assets,
+ * even ones stay reserved for the table.  With s_k = fl(100.0f + means[k]) and the lower-triangular factor L (percent),
+ *   a_k = fma(L[k][k], z_k, fma(L[k][k-1], z_{k-1}, ... fma(L[k][0], z_0, s_k))),
+ * the terms taken from j = 0 upwards, each step ONE fused multiply-add.  sim->gauss_mean and sim->gauss_std are not
+ * read.  K = 1 gives the LAW of the plain Gaussian mode with gauss_std = L[0][0] but not its bits: the plain mode
+ * folds the standard deviation into the coefficients of the radius cubic, here it multiplies the finished normal.
+ *
+ * A path depends only on (seed, global path id, table or means and L, weights, R); the launch shape and the sharding
+ * are invisible. */
+#define SMMC_MAX_ASSETS 4
+typedef struct smmc_portfolio {
+  uint32_t struct_size;     /* = sizeof(smmc_portfolio) */
+  uint32_t n_assets;        /* K, 1 .. SMMC_MAX_ASSETS */
+  uint32_t rebalance_every; /* R; 0 = never (buy and hold) */
+  uint32_t reserved;        /* 0 */
+  float weights[SMMC_MAX_ASSETS];                  /* w_k >= 0, summing to 1 within 1e-6; entries k >= K must be 0 */
+  float means[SMMC_MAX_ASSETS];                    /* Gaussian mode: percent per period; else 0 */
+  float factor[SMMC_MAX_ASSETS * SMMC_MAX_ASSETS]; /* Gaussian mode: lower-triangular L, percent, L[k][j] at
+                                                      [k * SMMC_MAX_ASSETS + j], diagonal >= 0; everything else 0 */
+} smmc_portfolio;
+
+typedef struct smmc_portfolio_outputs {
+  uint32_t struct_size, reserved; /* = sizeof(smmc_portfolio_outputs), 0 */
+  float *d_final;    /* n_paths, nullable */
+  float *d_holdings; /* asset-major K x n_paths final holdings (before any rebalance at P), nullable */
+  void *d_stats;     /* packed record of the final values, smmc_stats_bytes(n_bins), nullable */
+} smmc_portfolio_outputs;
+
+/* The joint table of table-mode portfolios: n_rows x n_assets returns in percent, row-major; n_assets in 1 ..
+ * SMMC_MAX_ASSETS, n_rows * n_assets <= SMMC_MAX_TABLE.  Copied before the call returns; replaces an earlier one. */
+int smmc_engine_set_asset_table(smmc_engine *e, const float *returns_percent, uint32_t n_rows, uint32_t n_assets);
+/* One portfolio simulation, enqueued on the engine stream; out holds DEVICE pointers (4-byte aligned, d_stats 8-byte),
+ * any may be NULL.  n_periods == 0 yields V_0; n_paths == 0 launches nothing and yields the empty record.
+ * SMMC_ERR_INVALID with a text: NULL or wrongly sized structures; SMMC_FLAG_STREAM_V2 or SMMC_FLAG_STREAM_REF;
+ * n_assets == 0 or > SMMC_MAX_ASSETS; reserved != 0; a weight that is negative, NaN or infinite, or non-zero at
+ * k >= n_assets; |sum of the weights (in double) - 1| > 1e-6; table mode without an asset table or with one of another
+ * column count, or with a non-zero entry in means or factor; Gaussian mode with a non-finite mean or factor entry, a
+ * non-zero entry above the diagonal or beyond K, or a negative diagonal; asset table, histogram and partials beyond the
+ * device's LDS; 2^32 or more paths per workgroup (shard the request); the other argument errors of
+ * smmc_engine_simulate.  Divide by 100: smmc_engine_portfolio_divide_kind; the result does not depend on it. */
+int smmc_engine_simulate_portfolio(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                   const smmc_portfolio_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_portfolio_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                           const smmc_portfolio_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT (never SMMC_DIV_CHECKED: the holdings are summed at every rebalance, so a value must
+ * be right whenever it is looked at -- keepdata's rule), or an error of the call's argument checks.  FAST when every
+ * product h_k * a_k provably stays inside [2^-89, 2^127) or is exactly 0: per asset a_k lies between its column's
+ * extremes (table mode) or inside s_k -+ Zmax * sum_j |L[k][j]| (Gaussian mode, the draw bound of
+ * smmc_engine_divide_kind); a value lies between V_0 times the worst and the best asset's multiplier / 100 to the
+ * power t; a positive holding is at least the smallest positive initial holding, or the smallest positive weight times
+ * the lowest possible value, shrunk by the worst multiplier since ("Portfolios").  A holding of exactly 0
+ * stays 0 in both forms.  SMMC_FLAG_EXACT_DIV forces the IEEE divide. */
+int smmc_engine_portfolio_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

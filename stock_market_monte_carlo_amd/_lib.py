@@ -31,6 +31,7 @@ MAX_CHECKPOINTS = 64
 MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
 MAX_CASHFLOW_PERIODS = 4096  # largest n_periods of a simulate_cashflow call
 MAX_EXCURSION_PERIODS = 4096  # largest n_periods of a simulate_excursions call
+MAX_ASSETS = 4  # most assets of a simulate_portfolio call
 
 
 class Sim(C.Structure):
@@ -103,6 +104,30 @@ class Blocks(C.Structure):
 
 BLOCKS_CIRCULAR = 0
 
+
+class Portfolio(C.Structure):
+    """smmc_portfolio"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_assets", C.c_uint32),
+        ("rebalance_every", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("weights", C.c_float * MAX_ASSETS),
+        ("means", C.c_float * MAX_ASSETS),
+        ("factor", C.c_float * (MAX_ASSETS * MAX_ASSETS)),
+    ]
+
+
+class PortfolioOutputs(C.Structure):
+    """smmc_portfolio_outputs"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("final", C.c_void_p),
+        ("holdings", C.c_void_p),
+        ("stats", C.c_void_p),
+    ]
+
 # the pointer fields of smmc_excursion_outputs, in the order of the structure
 EXCURSION_OUTPUTS = ("final", "peak", "low", "drawdown", "drawdown_period", "underwater", "first_below", "first_reach",
                      "stats", "drawdown_stats", "first_below_at", "first_reach_at")
@@ -156,6 +181,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
       C.c_void_p]),
     ("smmc_engine_blocks_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks)]),
+    ("smmc_engine_set_asset_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("smmc_engine_simulate_portfolio", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioOutputs)]),
+    ("smmc_engine_simulate_portfolio_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioOutputs)]),
+    ("smmc_engine_portfolio_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -143,7 +143,7 @@ struct smmc_engine {
   // launches and neither it nor the record is memset per call.  Taken through a ZeroLease (engine_acc_lease).
   smmc::ZeroedArray hist_acc;
   smmc::DeviceBuffer<smmc::BlockPartial> d_ck_partials;  // checkpoints_kernel: [checkpoint][workgroup], grown on demand
-  smmc::EngineExt ext = {nullptr, nullptr};     // state of another translation unit (smmc_internal.h: engine_ext)
+  smmc::EngineExt ext[smmc::kEngineExtSlots] = {};  // state of other translation units, by owner (smmc_internal.h: engine_ext)
 
   // SMMC_FLAG_STREAM_REF (smmc_ref_kernels.hip)
   smmc::DeviceBuffer<float> d_ref_final;    // final values of a launch that asked for none (statistics are formed from them)
@@ -721,7 +721,8 @@ void smmc_engine_destroy(smmc_engine *e) {
     (void)hipStreamSynchronize(e->copy_stream);
     (void)hipStreamDestroy(e->copy_stream);
   }
-  if (e->ext.release) e->ext.release(e->ext.state);
+  for (smmc::EngineExt &x : e->ext)
+    if (x.release) x.release(x.state);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->ev_order) (void)hipEventDestroy(e->ev_order);
   for (int i = 0; i < 2; ++i) {
@@ -1595,7 +1596,16 @@ EngineView engine_view(const smmc_engine *e) {
   return EngineView{e->device, e->stream, e->compute_units, e->max_grid, e->max_lds, e->d_partials.p,
                     e->timing ? e->d_clock.p : nullptr};
 }
-EngineExt *engine_ext(smmc_engine *e) { return &e->ext; }
+EngineExt *engine_ext(smmc_engine *e, const void *owner) {
+  for (EngineExt &x : e->ext)
+    if (x.owner == owner) return &x;
+  for (EngineExt &x : e->ext)
+    if (!x.owner) {
+      x.owner = owner;
+      return &x;
+    }
+  return nullptr;
+}
 int engine_acc_lease(smmc_engine *e, ZeroLease *lease) {
   SMMC_HIP(lease->take(e->hist_acc, sizeof(unsigned long long) * kHistSpread * SMMC_MAX_BINS, e->stream));
   return SMMC_OK;

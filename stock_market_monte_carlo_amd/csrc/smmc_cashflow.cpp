@@ -3,7 +3,7 @@
 //
 // A translation unit of its own: smmc_capi.cpp owns struct smmc_engine and never calls into this file; what is
 // needed of an engine comes through smmc_internal.h and smmc_host.h (engine_view, engine_acc_lease, ...), and what this file keeps
-// per engine -- the staged schedule -- hangs in the engine's extension slot (engine_ext), released by
+// per engine -- the staged schedule -- hangs in this unit's extension slot of the engine (engine_ext), released by
 // smmc_engine_destroy.  The launch is a wave walk, and its host side is the shared one: host_require_v3,
 // host_wave_walk_grid, host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in
 // smmc_capi.cpp).  The reference has no counterpart: its README lists withdrawal strategies as open.
@@ -52,9 +52,12 @@ void release_state(void *p) {
   delete st;  // the two buffers with it
 }
 
+const char kOwner = 0;  // its address names this unit's slot among the engine's (engine_ext)
+
 // Device must be current.
 int state_of(smmc_engine *e, CashflowState **out) {
-  smmc::EngineExt *ext = smmc::engine_ext(e);
+  smmc::EngineExt *ext = smmc::engine_ext(e, &kOwner);
+  if (!ext) return host_fail(SMMC_ERR_INVALID, "the engine has no extension slot left for the cash-flow schedule");
   if (!ext->state) {
     CashflowState *st = new (std::nothrow) CashflowState();
     if (!st) return host_fail(SMMC_ERR_NOMEM, "out of host memory");

@@ -195,6 +195,22 @@ size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods
 // `grid` workgroups of kBlock threads, one partial each.
 hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int div, uint32_t grid, hipStream_t stream);
 size_t blocks_lds_bytes(uint32_t table_len, uint32_t n_bins, bool wide);
+// portfolio_kernel (smmc_engine_simulate_portfolio, csrc/smmc_portfolio.cpp; counter stream v3 only): K jointly drawn
+// assets per path, held with weights and rebalanced every `rebalance_every` periods ("Portfolios").
+// Table mode: a.table_a is the asset table, a.table_len rows of portfolio_row_words(K) words (a = 100.0f + r, padding
+// 0).  Gaussian mode: a.gauss_std = 1.0f and a.gauss_shift100 = 0.0f (the staged draw yields standard normals).
+struct PortfolioArgs {
+  uint32_t n_assets, rebalance_every;
+  float weights[SMMC_MAX_ASSETS];
+  float shift100[SMMC_MAX_ASSETS];                   // s_k = 100.0f + means[k]
+  float factor[SMMC_MAX_ASSETS * SMMC_MAX_ASSETS];  // L, row-major
+  float *d_holdings;                                 // nullable: n_assets x n_paths, asset-major
+};
+constexpr uint32_t portfolio_row_words(uint32_t n_assets) { return n_assets == 3u ? 4u : n_assets; }  // 1, 2 or 4
+// a.partials: `grid` entries or null; a.d_hist: a.n_bins counters, zero before the launch.  A workgroup walks chunks of
+// wave_walk_group_paths(mode) consecutive paths.
+hipError_t launch_portfolio(const KernelArgs &a, const PortfolioArgs &p, bool exact_div, uint32_t grid, hipStream_t stream);
+size_t portfolio_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_bins);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
@@ -225,7 +241,11 @@ struct EngineView {  // what a launch needs to know of an engine
   BlockPartial *d_partials;  // max_grid entries
   unsigned long long *clock_probe;  // KernelArgs::clock_probe of a launch now: null unless smmc_engine_timing is on
 };
-struct EngineExt {  // one slot of state owned by another translation unit: smmc_engine_destroy calls release(state)
+// One slot of state owned by another translation unit, keyed by `owner` (the address of an object of that unit):
+// smmc_engine_destroy calls release(state) for every slot taken.
+constexpr int kEngineExtSlots = 4;
+struct EngineExt {
+  const void *owner;  // null: free
   void *state;
   void (*release)(void *state);
 };
@@ -271,7 +291,8 @@ int host_check_sim(const smmc_engine *e, const smmc_sim *s);
 bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
 KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
 EngineView engine_view(const smmc_engine *e);
-EngineExt *engine_ext(smmc_engine *e);
+// The slot of `owner`, claimed at the first ask; null when every slot belongs to somebody else.
+EngineExt *engine_ext(smmc_engine *e, const void *owner);
 // (the engine's zeroed accumulator is leased through smmc_host.h: ZeroLease, engine_acc_lease)
 // smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);

@@ -1133,10 +1133,11 @@ void blocks_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t bloc
 // aligned, the waves' BlockPartial records.  The counters count paths of ONE workgroup: the host refuses a launch in
 // which a workgroup would get 2^32 or more (host_wave_walk_grid, smmc_capi.cpp).
 //
-// Periods (walk_periods).  k.n_periods / kDraws whole Philox blocks, then the path's partial block, whose draws
-// past the last period are dropped; `prefetch(blk)` runs before a block's Philox rounds, `step(j, a, t)` after
-// them for draw j, multiplier a, period t (1-based; j is a constant after unrolling).  checkpoints_kernel has a
-// block loop of its own (a fast and a slow form per block) and takes the other pieces.
+// Periods (walk_blocks, walk_periods).  k.n_periods / kDraws whole Philox blocks, then the path's partial block, whose
+// draws past the last period are dropped; `prefetch(blk)` runs before a block's Philox rounds, `step(j, a, t)` after
+// them for draw j, multiplier a, period t (1-based; j is a constant after unrolling).  portfolio_kernel draws K
+// multipliers per period and walks the same blocks with a draw of its own; checkpoints_kernel has a block loop of its
+// own (a fast and a slow form per block) and takes the other pieces.
 //
 // Records.  wave_record reduces the wave's 64 values to the wave-uniform sums, extremes and counts of one record
 // and makes the LDS bucket adds; where the totals go is the kernel's (checkpoint_record, wave_record_add).  At the
@@ -1185,26 +1186,36 @@ __device__ __forceinline__ void wave_chunks(const KernelArgs &k, const WalkLds &
   }
 }
 
+// The block walk under walk_periods and the portfolio's period loop: n_periods / kDraws whole Philox blocks, then the
+// partial block.  draw(blk) makes the block's kDraws draws; step(j, t) consumes draw j at period t (1-based).
+template <int kDraws, typename Draw, typename Step>
+__device__ __forceinline__ void walk_blocks(uint32_t n_periods, Draw draw, Step step) {
+  const uint32_t full = n_periods / kDraws, rem = n_periods - full * kDraws;
+  for (uint32_t blk = 0; blk < full; ++blk) {
+    draw(blk);
+#pragma unroll
+    for (int j = 0; j < kDraws; ++j) step(j, blk * kDraws + j + 1u);
+  }
+  if (rem) {  // wave-uniform: the path's last, partial block
+    draw(full);
+#pragma unroll
+    for (int j = 0; j < kDraws - 1; ++j)
+      if (static_cast<uint32_t>(j) < rem) step(j, full * kDraws + j + 1u);
+  }
+}
+
 template <int kMode, bool kDense, typename Prefetch, typename Step>
 __device__ __forceinline__ void walk_periods(const KernelArgs &k, const DrawRegs &dr, const float *lds_table, uint32_t path_lo,
                                              uint32_t path_hi, Prefetch prefetch, Step step) {
   constexpr int kDraws = Draws<kMode, kDense>::value;
-  const uint32_t full = k.n_periods / kDraws, rem = k.n_periods - full * kDraws;
-  for (uint32_t blk = 0; blk < full; ++blk) {
-    prefetch(blk);
-    float a[kDraws];
-    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
-#pragma unroll
-    for (int j = 0; j < kDraws; ++j) step(j, a[j], blk * kDraws + j + 1u);
-  }
-  if (rem) {  // wave-uniform: the path's last, partial block
-    prefetch(full);
-    float a[kDraws];
-    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
-#pragma unroll
-    for (int j = 0; j < kDraws - 1; ++j)
-      if (static_cast<uint32_t>(j) < rem) step(j, a[j], full * kDraws + j + 1u);
-  }
+  float a[kDraws];
+  walk_blocks<kDraws>(
+      k.n_periods,
+      [&](uint32_t blk) {
+        prefetch(blk);
+        block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+      },
+      [&](int j, uint32_t t) { step(j, a[j], t); });
 }
 
 template <int kShift>
@@ -1284,6 +1295,49 @@ __device__ __forceinline__ void flush_counters(const uint32_t *counters, uint32_
     if (c) atomicAdd(&out[b], static_cast<unsigned long long>(c));
   }
 }
+
+// A lane's running record of the final values of its paths, as paths_kernel forms it: the accumulators stay per lane
+// from chunk to chunk (a wave record per chunk would add the doubles in another order) and are reduced over the wave
+// once, at the end of the walk.  cashflow_kernel and portfolio_kernel.
+struct LaneRecord {
+  double sum = 0.0, sumsq = 0.0;
+  uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
+  float vmin = __builtin_inff(), vmax = -__builtin_inff();
+  // an active lane's value v; want_hist: one LDS add into the k.n_bins buckets at lds_hist
+  __device__ __forceinline__ void add(const KernelArgs &k, float v, bool want_hist, uint32_t *lds_hist) {
+    const double dv = static_cast<double>(v);
+    sum += dv;
+    sumsq += dv * dv;
+    n_count += 1;
+    n_below += (v < k.below_threshold) ? 1u : 0u;
+    vmin = fminf(vmin, v);
+    vmax = fmaxf(vmax, v);
+    if (want_hist) {
+      if (v < k.hist_lo) {
+        n_under += 1;
+      } else if (v < k.hist_hi) {
+        int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
+        b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
+        atomicAdd(&lds_hist[b], 1u);
+      } else {
+        n_over += 1;
+      }
+    }
+  }
+  // the wave's partial into s.wave_part[s.wave]; every lane of the wave calls
+  __device__ __forceinline__ void store(const WalkLds &s) const {
+    BlockPartial p;
+    p.sum = wave_sum(sum);
+    p.sumsq = wave_sum(sumsq);
+    p.count = wave_sum(static_cast<unsigned long long>(n_count));
+    p.below = wave_sum(static_cast<unsigned long long>(n_below));
+    p.underflow = wave_sum(static_cast<unsigned long long>(n_under));
+    p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
+    p.min = wave_min(vmin);
+    p.max = wave_max(vmax);
+    if (s.lane == 0) s.wave_part[s.wave] = p;
+  }
+};
 
 // ---- checkpoints: the value distribution at chosen periods ---------------------------------------
 //
@@ -2056,9 +2110,7 @@ void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
   const bool want_stats = k.partials != nullptr;  // all uniform
   const bool want_hist = want_stats && k.n_bins != 0;
   const bool want_dep = c.d_depleted != nullptr;
-  double sum = 0.0, sumsq = 0.0;
-  uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
-  float vmin = __builtin_inff(), vmax = -__builtin_inff();
+  LaneRecord rec;
   const DrawRegs dr = make_draw_regs(k);
   const const_float_ptr amounts = (const_float_ptr)(c.schedule);
   const const_float_ptr fractions = amounts + c.stride;
@@ -2084,40 +2136,10 @@ void cashflow_kernel(const KernelArgs k, const CashflowArgs c) {
       if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
       if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
     }
-    if (want_stats && active) {  // the final value's statistics, as paths_kernel forms them
-      const double dv = static_cast<double>(v);
-      sum += dv;
-      sumsq += dv * dv;
-      n_count += 1;
-      n_below += (v < k.below_threshold) ? 1u : 0u;
-      vmin = fminf(vmin, v);
-      vmax = fmaxf(vmax, v);
-      if (want_hist) {
-        if (v < k.hist_lo) {
-          n_under += 1;
-        } else if (v < k.hist_hi) {
-          int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
-          b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
-          atomicAdd(&lds_hist[b], 1u);
-        } else {
-          n_over += 1;
-        }
-      }
-    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
   });
 
-  if (want_stats) {
-    BlockPartial p;
-    p.sum = wave_sum(sum);
-    p.sumsq = wave_sum(sumsq);
-    p.count = wave_sum(static_cast<unsigned long long>(n_count));
-    p.below = wave_sum(static_cast<unsigned long long>(n_below));
-    p.underflow = wave_sum(static_cast<unsigned long long>(n_under));
-    p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
-    p.min = wave_min(vmin);
-    p.max = wave_max(vmax);
-    if (s.lane == 0) s.wave_part[s.wave] = p;
-  }
+  if (want_stats) rec.store(s);
   __syncthreads();  // the waves' partials are written and their LDS adds complete
   if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
   if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
@@ -2272,6 +2294,143 @@ void excursions_kernel(const KernelArgs k, const ExcursionArgs x) {
   }
 }
 
+// ---- portfolios: jointly drawn assets, weights, periodic rebalancing ------------------------------
+//
+// smmc_engine_simulate_portfolio (csrc/smmc_portfolio.cpp; include/smmc.h and DESIGN.md, "Portfolios", state the
+// contract).  A lane carries K holdings; a period draws K multipliers jointly, compounds each holding with
+// compound<>() and, every R periods, sets the holdings to the weights' shares of their sum.  R and the period index
+// are wave-uniform: the rebalance is a uniform branch behind a scalar countdown (no modulo in the loop).  A wave walk:
+// work split, LDS carving, the block walk (walk_blocks) and the epilogue pieces are the skeleton's; the record of the
+// final values is formed as cashflow_kernel forms it (LaneRecord).  Bound like its siblings: VALU issue.
+//
+// Table mode.  The asset table sits at LDS address 0, one row per month padded to 1, 2 or 4 words
+// (portfolio_row_words), so a row is ONE ds_read_b32 / b64 / b128 at index << 2 | 3 | 4; the row indices are
+// block_starts' with table_len = n_rows -- the indices SMMC_MODE_TABLE draws -- and one Philox block serves D periods of
+// all assets.
+// Gaussian mode.  K Philox blocks per four periods, (blk, id lo, id hi, 1 + 2 j): they differ in a compile-time word
+// only, so the scalarised first rounds of philox4x32_10<true> apply to each, and philox4x32_10_multi interleaves the K
+// chains.  The v3 tables are staged once with gauss_std = 1.0f, the draw's additive term is 0.0f (the host sets both):
+// multipliers_of_words_multi then yields STANDARD normals, and the multiplier is the contract's chain of fused
+// multiply-adds over L's row, j = 0 upwards from s_k.  The additions of V_t are __fadd_rn, the weight products
+// __fmul_rn: nothing may be re-associated or contracted.
+template <int K>
+__device__ __forceinline__ void load_asset_row(uint32_t row, float (&a)[K]) {
+  static_assert(K >= 1 && K <= SMMC_MAX_ASSETS, "1 .. 4 assets");
+  if constexpr (K == 1) {
+    a[0] = lds_load_at<float>(row << 2);
+  } else if constexpr (K == 2) {
+    const f32x2_t r = lds_load_at<f32x2_t>(row << 3);
+    a[0] = r.x;
+    a[1] = r.y;
+  } else {
+    const f32x4_t r = lds_load_at<f32x4_t>(row << 4);
+    a[0] = r.x;
+    a[1] = r.y;
+    a[2] = r.z;
+    if constexpr (K == 4) a[3] = r.w;
+  }
+}
+
+// The multipliers a[j][k] of asset k at draw j of Philox block `blk` (wave-uniform) of a path.
+template <int kMode, bool kDense, int K>
+__device__ __forceinline__ void portfolio_multipliers(const KernelArgs &k, const PortfolioArgs &p, const DrawRegs &dr,
+                                                      const float *lds_table, uint32_t path_lo, uint32_t path_hi, uint32_t blk,
+                                                      float (&a)[Draws<kMode, kDense>::value][K]) {
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  if constexpr (is_table(kMode)) {
+    uint32_t row[kDraws];
+    block_starts<kDense>(k, dr, path_lo, path_hi, blk, row);
+#pragma unroll
+    for (int j = 0; j < kDraws; ++j) load_asset_row<K>(row[j], a[j]);
+  } else {
+    uint32_t u[K][4];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      u[i][0] = blk;
+      u[i][1] = path_lo;
+      u[i][2] = path_hi;
+      u[i][3] = 1u + 2u * static_cast<uint32_t>(i);
+    }
+    philox4x32_10_multi<K, true>(u, k.key0, k.key1, dr);
+    float z[K][kDraws];  // standard normals: the tables are staged at scale 1, dr.shift100 is 0
+    multipliers_of_words_multi<SMMC_MODE_GAUSSIAN, false, K>(k, dr, lds_table, u, z);
+#pragma unroll
+    for (int j = 0; j < kDraws; ++j)
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        float acc = p.shift100[i];
+#pragma unroll
+        for (int m = 0; m <= i; ++m) acc = __builtin_fmaf(p.factor[i * SMMC_MAX_ASSETS + m], z[m][j], acc);
+        a[j][i] = acc;
+      }
+  }
+}
+
+template <int K>
+__device__ __forceinline__ float portfolio_value(const float (&h)[K]) {  // ((h_0 + h_1) + h_2) + h_3
+  float v = h[0];
+#pragma unroll
+  for (int i = 1; i < K; ++i) v = __fadd_rn(v, h[i]);
+  return v;
+}
+
+template <int kMode, bool kExactDiv, bool kDense, int K>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void portfolio_kernel(const KernelArgs k, const PortfolioArgs p) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), k.n_bins);
+  uint32_t *lds_hist = s.counters;  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends (n_periods < 2^31)
+    float a[kDraws][K];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) { portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a); },
+        [&](int j, uint32_t t) {
+#pragma unroll
+          for (int x = 0; x < K; ++x) h[x] = compound<kExactDiv>(h[x], a[j][x]);
+          if (--until == 0u) {  // uniform: t mod every == 0
+            until = every;
+            if (t != k.n_periods) {  // the final value and holdings are formed before any rebalance at P
+              const float v = portfolio_value<K>(h);
+#pragma unroll
+              for (int x = 0; x < K; ++x) h[x] = __fmul_rn(v, p.weights[x]);
+            }
+          }
+        });
+    const float v = portfolio_value<K>(h);
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int x = 0; x < K; ++x) p.d_holdings[static_cast<uint64_t>(x) * k.n_paths + i] = h[x];
+      }
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 }  // namespace
 
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
@@ -2301,7 +2460,7 @@ size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream) {
   const int row = keepdata_row_words(tile, draws);
   return (table_words + static_cast<size_t>(waves) * 64 * (row + 1)) * 4u;
 }
-// Static LDS of the kernels that read the v3 tables through absolute LDS addresses: must be 0.
+// Static LDS of the kernels that read their draw tables through absolute LDS addresses: must be 0.
 hipError_t static_lds_bytes(size_t *bytes) {
   *bytes = 0;
   const void *kernels[] = {
@@ -2325,6 +2484,15 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, false, false>),
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, true, false>),
       reinterpret_cast<const void *>(draw_words_kernel<SMMC_MODE_GAUSSIAN, false>),
+#define SMMC_PORTFOLIO_KERNELS(K) /* both modes: the asset table is read through absolute addresses too */                  \
+  reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_GAUSSIAN, false, false, K>),                                     \
+      reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_GAUSSIAN, true, false, K>),                                  \
+      reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_TABLE, false, true, K>),                                     \
+      reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_TABLE, true, true, K>),                                      \
+      reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_TABLE, false, false, K>),                                    \
+      reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_TABLE, true, false, K>)
+      SMMC_PORTFOLIO_KERNELS(1), SMMC_PORTFOLIO_KERNELS(2), SMMC_PORTFOLIO_KERNELS(3), SMMC_PORTFOLIO_KERNELS(4),
+#undef SMMC_PORTFOLIO_KERNELS
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -2648,6 +2816,30 @@ struct ExcursionsFamily {
 hipError_t launch_excursions(const KernelArgs &a, const ExcursionArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
   if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_EXCURSION_PERIODS) return hipErrorInvalidValue;
   return launch_wave_walk<ExcursionsFamily>(a, x, exact_div, grid, excursions_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins), stream);
+}
+
+// ---- portfolios ----
+
+size_t portfolio_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_bins) {
+  // the padded rows in the table's place; counters: the histogram [n_bins]; one partial per wave
+  return wave_walk_lds_bytes(mode, n_rows * portfolio_row_words(n_assets), n_bins, 1u);
+}
+
+struct PortfolioFamily {
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<PortfolioArgs> get(const PortfolioArgs &p) {
+    switch (p.n_assets) {
+      case 1: return portfolio_kernel<kMode, kExactDiv, kDense, 1>;
+      case 2: return portfolio_kernel<kMode, kExactDiv, kDense, 2>;
+      case 3: return portfolio_kernel<kMode, kExactDiv, kDense, 3>;
+      default: return portfolio_kernel<kMode, kExactDiv, kDense, 4>;
+    }
+  }
+};
+hipError_t launch_portfolio(const KernelArgs &a, const PortfolioArgs &p, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream != 3 || p.n_assets < 1 || p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  return launch_wave_walk<PortfolioFamily>(a, p, exact_div, grid, portfolio_lds_bytes(a.mode, a.table_len, p.n_assets, a.n_bins), stream);
 }
 
 }  // namespace smmc

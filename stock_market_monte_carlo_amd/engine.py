@@ -182,6 +182,32 @@ class ExcursionResult:
         return _by_period(self.first_reach_at, "reached_by")
 
 
+@dataclasses.dataclass
+class PortfolioResult:
+    """What Engine.simulate_portfolio returns: the outputs that were asked for, None for the others."""
+    n_paths: int
+    n_assets: int
+    final: object = None     # torch.float32 [n_paths] on the engine's device: V_P
+    holdings: object = None  # torch.float32 [n_assets, n_paths]: the final holdings, before any rebalance at P
+    stats: Stats = None      # record of the final values
+
+
+def cholesky_factor(stds, corr):
+    """The lower-triangular factor L (float32 [K, K], percent) of diag(stds) corr diag(stds), for
+    Engine.simulate_portfolio(factor=...): numpy's float64 Cholesky, cast once.  Raises ValueError for a matrix that
+    is not symmetric positive definite."""
+    sd = np.asarray(stds, dtype=np.float64)
+    c = np.asarray(corr, dtype=np.float64)
+    if sd.ndim != 1 or c.shape != (sd.size, sd.size):
+        raise ValueError("stds must have K entries and corr K x K")
+    if not (np.isfinite(sd).all() and np.isfinite(c).all() and (sd > 0).all() and np.allclose(c, c.T)):
+        raise ValueError("stds must be positive and corr symmetric and finite")
+    try:
+        return np.linalg.cholesky(sd[:, None] * c * sd[None, :]).astype(np.float32)
+    except np.linalg.LinAlgError as err:
+        raise ValueError("the covariance matrix is not positive definite") from err
+
+
 class Engine:
     """One engine per (process, device): table, workspace and stream stay resident."""
 
@@ -649,6 +675,106 @@ class Engine:
         on it)."""
         blocks = self.make_blocks(block_len)
         rc = self._L.smmc_engine_blocks_divide_kind(self._h, C.byref(sim), C.byref(blocks))
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- portfolios: jointly drawn assets, weights, periodic rebalancing (smmc_engine_simulate_portfolio) -----
+    def set_asset_table(self, returns_percent):
+        """The joint table of table-mode portfolios: returns[T, K] in percent, one row per month, one column per asset."""
+        t = np.ascontiguousarray(returns_percent, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("the asset table has shape (rows, assets)")
+        self._enter()
+        _lib.check(self._L.smmc_engine_set_asset_table(self._h, t.ctypes.data_as(C.c_void_p), t.shape[0], t.shape[1]))
+
+    @staticmethod
+    def make_portfolio(weights, rebalance_every=0, means=None, factor=None):
+        """smmc_portfolio of K = len(weights) assets; means [K] and factor [K, K] (lower triangular) in Gaussian mode."""
+        w = np.asarray(weights, dtype=np.float32).ravel()
+        K = int(w.size)
+        if not 1 <= K <= _lib.MAX_ASSETS:
+            raise ValueError(f"1 .. {_lib.MAX_ASSETS} assets")
+        pf = _lib.Portfolio()
+        pf.struct_size = C.sizeof(_lib.Portfolio)
+        pf.n_assets, pf.rebalance_every = K, int(rebalance_every)
+        for k in range(K):
+            pf.weights[k] = float(w[k])
+        if means is not None:
+            m = np.asarray(means, dtype=np.float32).ravel()
+            if m.size != K:
+                raise ValueError("means must hold one entry per asset")
+            for k in range(K):
+                pf.means[k] = float(m[k])
+        if factor is not None:
+            f = np.asarray(factor, dtype=np.float32)
+            if f.shape != (K, K):
+                raise ValueError("factor must be K x K")
+            for k in range(K):
+                for j in range(K):
+                    pf.factor[k * _lib.MAX_ASSETS + j] = float(f[k, j])
+        return pf
+
+    def simulate_portfolio(self, sim, weights, rebalance_every=0, means=None, factor=None, want_final=True,
+                           want_holdings=False, want_stats=False, out=None):
+        """One simulation of a portfolio of K = len(weights) assets drawn jointly -- table mode: the rows of
+        set_asset_table; Gaussian mode: normals with the given means and Cholesky factor (cholesky_factor) -- held with
+        `weights` and rebalanced to them every `rebalance_every` periods (0: never).  Returns a PortfolioResult; final
+        and holdings stay on the device, stats is read back (that waits).  include/smmc.h states the arithmetic."""
+        raw = self.simulate_portfolio_raw(sim, weights, rebalance_every, means, factor, want_final, want_holdings,
+                                          want_stats, out)
+        res = PortfolioResult(int(sim.n_paths), raw["n_assets"], raw["final"], raw["holdings"])
+        if want_stats:
+            self.sync()
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        return res
+
+    def simulate_portfolio_raw(self, sim, weights, rebalance_every=0, means=None, factor=None, want_final=True,
+                               want_holdings=False, want_stats=False, out=None):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, holdings (float32) and
+        stats_raw (uint8, the packed record); None for what was not asked for."""
+        torch = self._torch
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, K = int(sim.n_paths), int(pf.n_assets)
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": out if (want_final and out is not None) else new(want_final, n, torch.float32),
+               "holdings": new(want_holdings, (K, n), torch.float32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8)}
+        if res["final"] is not None:
+            assert res["final"].numel() >= n and res["final"].dtype == torch.float32 and res["final"].is_contiguous()
+        o = _lib.PortfolioOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioOutputs)
+        for name, key in (("final", "final"), ("holdings", "holdings"), ("stats", "stats_raw")):
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio(self._h, C.byref(sim), C.byref(pf), C.byref(o)))
+        self._leave(cur, res["final"], res["holdings"], res["stats_raw"])
+        return res
+
+    def simulate_portfolio_to_host(self, sim, weights, rebalance_every=0, means=None, factor=None, want_final=True,
+                                   want_holdings=False, want_stats=False):
+        """The same through smmc_engine_simulate_portfolio_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, K = int(sim.n_paths), int(pf.n_assets)
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64)}
+        o = _lib.PortfolioOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioOutputs)
+        for name, key in (("final", "final"), ("holdings", "holdings"), ("stats", "stats_raw")):
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(o)))
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def portfolio_divide_kind(self, sim, weights, rebalance_every=0, means=None, factor=None):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_portfolio uses for this request (results never depend on it)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        rc = self._L.smmc_engine_portfolio_divide_kind(self._h, C.byref(sim), C.byref(pf))
         if rc < 0:
             _lib.check(rc)
         return rc
