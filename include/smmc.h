@@ -285,6 +285,52 @@ int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, c
  * (never SMMC_DIV_CHECKED), or an error of that call's argument checks. */
 int smmc_engine_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf);
 
+/* ---- cash-flow sweeps: up to eight constant schedules on the same paths, one launch ---------- */
+
+#define SMMC_MAX_SWEEP 8
+#define SMMC_MAX_SWEEP_COUNTERS 8192 /* n_scenarios * (n_periods + 1 + n_bins) u32 counters in LDS: 32 KiB */
+
+/* "Which withdrawal still survives?" is a curve over schedules.  One launch draws every period's return once and
+ * steps n_scenarios (1 .. SMMC_MAX_SWEEP) schedules on it: the scenarios share their paths (common random
+ * numbers), and the draw -- more than half of a single call's work -- is made once.
+ * scenarios: a HOST array of n_scenarios smmc_cashflow, each a CONSTANT schedule: amount, fraction and floor are
+ * used, amounts and fractions must be NULL.  It may be reused on return.
+ * Outputs: DEVICE pointers, scenario-major, any may be NULL, written, not accumulated into; alignment as
+ * smmc_engine_simulate_cashflow:
+ *   d_final, d_paid, d_ruin_period   [n_scenarios][n_paths]
+ *   d_stats                          n_scenarios packed records, smmc_stats_bytes(sim->n_bins) bytes each
+ *   d_depleted_at                    [n_scenarios][n_periods + 1]
+ * Arithmetic: scenario s is smmc_engine_simulate_cashflow(sim, &scenarios[s]).  final, paid, ruin_period,
+ * depleted_at, the record's integer fields, min, max and bucket counts are those of that call, bit for bit; sum and
+ * sumsq are double sums in a fixed order of the sweep's own (no floating-point atomics: two identical sweeps give
+ * the same bytes) and agree with the single call's to 1e-12 relative.  A path depends on (seed, global path id,
+ * parameters, its scenario) only: not on the other scenarios, n_scenarios, first_path or the launch geometry.
+ * Shards merge by smmc_stats_merge and by adding d_depleted_at, scenario by scenario.
+ * Divide: SMMC_DIV_FAST if and only if smmc_engine_cashflow_divide_kind says FAST for every scenario; otherwise,
+ * or with SMMC_FLAG_EXACT_DIV, the IEEE divide for all of them (smmc_engine_cashflow_sweep_divide_kind says
+ * which).  Results never depend on the variant.
+ * Monotone in the amount: take two scenarios with equal floor, fraction = 0 and amounts a <= b.  On every path the
+ * value under b is <= the value under a after every period, and the period of depletion under b is not later than
+ * under a ("never depleted" counting as latest).  Every binary32 operation of the contract is monotone: for a
+ * multiplier > 0, v -> (v * a_t) / 100 is non-decreasing, g - amount is non-decreasing in g and non-increasing
+ * in the amount, and a depleted path holds 0, which no live path (> floor >= 0) is below.
+ * SMMC_ERR_INVALID with a text: everything smmc_engine_simulate_cashflow refuses, for any scenario; NULL
+ * scenarios; n_scenarios 0 or above SMMC_MAX_SWEEP; a scenario with amounts or fractions; n_scenarios *
+ * (n_periods + 1 + n_bins) above SMMC_MAX_SWEEP_COUNTERS, n_bins counting as 0 when d_stats is NULL; 2^32 paths or
+ * more per workgroup (shard the request); tables and counters beyond the device's LDS. */
+int smmc_engine_simulate_cashflow_sweep(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenarios,
+                                        uint32_t n_scenarios, float *d_final, float *d_paid,
+                                        uint32_t *d_ruin_period, void *d_stats, uint64_t *d_depleted_at);
+/* Synchronous convenience: the same into HOST memory. */
+int smmc_engine_simulate_cashflow_sweep_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenarios,
+                                                uint32_t n_scenarios, float *host_final, float *host_paid,
+                                                uint32_t *host_ruin_period, void *host_stats,
+                                                uint64_t *host_depleted_at);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT: the divide a sweep of (sim, scenarios) uses, or an error of that call's checks
+ * of sim and of the scenarios (the counter cap depends on the outputs and is the simulating calls' alone). */
+int smmc_engine_cashflow_sweep_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenarios,
+                                           uint32_t n_scenarios);
+
 /* ---- excursions: drawdown, running extremes, first passage of levels -------------------------- */
 
 #define SMMC_MAX_EXCURSION_PERIODS 4096 /* two arrays of n_periods + 1 u32 first-passage counters live in LDS */

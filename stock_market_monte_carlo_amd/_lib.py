@@ -30,6 +30,8 @@ MAX_RANKS = 8
 MAX_CHECKPOINTS = 64
 MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
 MAX_CASHFLOW_PERIODS = 4096  # largest n_periods of a simulate_cashflow call
+MAX_SWEEP = 8  # most scenarios of a simulate_cashflow_sweep call
+MAX_SWEEP_COUNTERS = 8192  # largest n_scenarios * (n_periods + 1 + n_bins) of one
 MAX_EXCURSION_PERIODS = 4096  # largest n_periods of a simulate_excursions call
 MAX_ASSETS = 4  # most assets of a simulate_portfolio call
 
@@ -171,6 +173,11 @@ SYMBOLS = [
     ("smmc_engine_simulate_cashflow_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("smmc_engine_cashflow_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow)]),
+    ("smmc_engine_simulate_cashflow_sweep", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_cashflow_sweep_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_cashflow_sweep_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Cashflow), C.c_uint32]),
     ("smmc_engine_simulate_excursions", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Excursions), C.POINTER(ExcursionOutputs)]),
     ("smmc_engine_simulate_excursions_to_host", C.c_int,

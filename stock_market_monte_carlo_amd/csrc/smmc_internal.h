@@ -172,6 +172,25 @@ hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exac
 // d_out[i] = acc[i] for i < n, and leaves acc zero (the engine's accumulator between launches)
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream);
 size_t cashflow_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins);
+// cashflow_sweep_kernel (smmc_engine_simulate_cashflow_sweep, csrc/smmc_sweep.cpp; counter stream v3 only): c.n constant
+// schedules stepped on ONE draw per period ("Cash-flow sweeps").  The kernel is compiled for 2, 4 and 8
+// scenarios: entries n .. sweep_width(n) - 1 are copies of entry n - 1 and leave no output.
+struct SweepArgs {
+  uint32_t n;  // 1 .. SMMC_MAX_SWEEP: the scenarios whose outputs are written
+  float amount[SMMC_MAX_SWEEP], fraction[SMMC_MAX_SWEEP], floor[SMMC_MAX_SWEEP];
+  float *d_paid;                   // nullable: [n][n_paths]
+  uint32_t *d_ruin_period;         // nullable: [n][n_paths]
+  unsigned long long *d_depleted;  // nullable: [n][n_periods + 1] counters, zero before the launch
+};
+constexpr uint32_t sweep_width(uint32_t n) { return n <= 2u ? 2u : n <= 4u ? 4u : 8u; }
+// a.d_final: [n][n_paths]; a.partials: [n][grid] entries or null; a.d_hist: [n][a.n_bins] counters, zero before the launch.
+hipError_t launch_cashflow_sweep(const KernelArgs &a, const SweepArgs &c, bool exact_div, uint32_t grid, hipStream_t stream);
+// Folds partials[scenario][n_partials] and hist_acc[scenario][n_bins] into the n_scenarios packed records at d_records and
+// leaves the counters zero: finalize_checkpoints_kernel under the sweep's name (the depletion counts go through
+// launch_finalize_depleted).
+hipError_t launch_finalize_sweep(const BlockPartial *partials, uint32_t n_partials, uint32_t n_scenarios, void *d_records,
+                                 uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream);
+size_t cashflow_sweep_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins, uint32_t n_scenarios);
 // excursions_kernel (smmc_engine_simulate_excursions, csrc/smmc_excursions.cpp; counter stream v3 only): the paths of
 // paths_kernel with the running extremes, the deepest relative drawdown, the longest time under water and the first
 // passage of two levels kept per lane ("Excursions").

@@ -2294,6 +2294,93 @@ void excursions_kernel(const KernelArgs k, const ExcursionArgs x) {
   }
 }
 
+// ---- cash-flow sweeps: up to eight constant schedules on the same paths ----------------------------
+//
+// smmc_engine_simulate_cashflow_sweep (csrc/smmc_sweep.cpp; include/smmc.h and DESIGN.md, "Cash-flow sweeps", state
+// the contract): scenario sc of a sweep is cashflow_kernel<..., kVarying = false> with (amount, fraction, floor)[sc].
+// The draw of a period depends on (seed, path id, period) alone, so ONE block_multipliers per Philox block serves
+// all scenarios; per draw an unrolled loop makes the kS cashflow_steps, each on its own v, paid, ruin and `alive`
+// (a lane mask in a scalar register pair, as in cashflow_kernel).  The 3 kS parameters are kernel arguments, scalar
+// registers; the loop loads nothing beyond the draw's gathers; control flow stays wave-uniform.
+//
+// kS is 2, 4 or 8: the host pads a request to the next of them with copies of its last scenario, and c.n says how
+// many are real -- a padded scenario is stepped (the loop is unrolled at kS) and nothing of it is ever stored,
+// counted or recorded.
+//
+// Records.  kS per-lane records would take 10 kS registers; instead every chunk's values are reduced over the wave
+// (wave_record) and added to the wave's partial of that scenario in LDS (wave_record_add), as excursions_kernel does
+// for its two records (hence this kernel's place behind it): some 70 VALU per wave, chunk and scenario beside the 13 per lane and period of the step.
+// The order is fixed (a wave's chunks ascending, waves in order, workgroups in finalize's order), but it is not
+// cashflow_kernel's: the two double sums of a scenario differ from the single call's in the last places.
+//
+// LDS (walk_setup): [draw tables][c.n][n_periods + 1] depletion counters][c.n][n_bins] buckets][pad][kS][kW] partials].
+// Epilogue: thread sc folds scenario sc's kW partials into k.partials[sc][workgroup]; both counter arrays go to
+// the accumulator with flush_counters, scenario-major like the outputs.
+template <int kMode, bool kExactDiv, bool kDense, int kS>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void cashflow_sweep_kernel(const KernelArgs k, const SweepArgs c) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  static_assert(kS >= 1 && kS <= SMMC_MAX_SWEEP, "1 .. SMMC_MAX_SWEEP scenarios");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const uint32_t n_at = k.n_periods + 1u;
+  const WalkLds s = walk_setup<kMode>(k, lds_raw, walk_table_words<kMode>(k), c.n * (n_at + k.n_bins));  // wave_part: [kS][kW]
+  uint32_t *lds_dep = s.counters;             // [c.n][n_periods + 1]
+  uint32_t *lds_hist = lds_dep + c.n * n_at;  // [c.n][n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  const uint32_t lane = s.lane;
+  BlockPartial *part = s.wave_part + s.wave;  // scenario sc: part[sc * kW], this wave's own until the barrier
+  if (lane == 0) {
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) partial_identity(part[sc * kW]);
+  }
+  const DrawRegs dr = make_draw_regs(k);
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float v[kS], paid[kS];
+    uint32_t ruin[kS];
+    bool alive[kS];
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) {
+      v[sc] = k.initial_capital;
+      paid[sc] = 0.0f;
+      ruin[sc] = 0u;
+      alive[sc] = true;
+    }
+    walk_periods<kMode, kDense>(
+        k, dr, s.table, path_lo, path_hi, [](uint32_t) {},
+        [&](int, float a, uint32_t t) {
+#pragma unroll
+          for (int sc = 0; sc < kS; ++sc)
+            cashflow_step<kExactDiv>(a, c.amount[sc], c.fraction[sc], c.floor[sc], t, v[sc], paid[sc], ruin[sc], alive[sc]);
+        });
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) {
+      if (static_cast<uint32_t>(sc) >= c.n) continue;  // uniform: a padded scenario leaves nothing
+      const size_t at = static_cast<size_t>(sc) * k.n_paths + i;
+      if (active) {
+        if (k.d_final) k.d_final[at] = v[sc];
+        if (c.d_paid) c.d_paid[at] = paid[sc];
+        if (c.d_ruin_period) c.d_ruin_period[at] = ruin[sc];
+        if (want_dep) atomicAdd(&lds_dep[sc * n_at + ruin[sc]], 1u);  // ruin <= n_periods
+      }
+      if (want_stats)  // uniform: the whole wave
+        wave_record_add(part + sc * kW, v[sc], active, lane, k.below_threshold, k.hist_lo, k.hist_hi, k.hist_inv,
+                        want_hist ? k.n_bins : 0u, lds_hist + sc * k.n_bins);
+    }
+  });
+
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x < c.n)
+    fold_wave_partials<kW>(s.wave_part + threadIdx.x * kW, &k.partials[static_cast<size_t>(threadIdx.x) * gridDim.x + blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, c.n * n_at, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, c.n * k.n_bins, k.d_hist);
+}
+
 // ---- portfolios: jointly drawn assets, weights, periodic rebalancing ------------------------------
 //
 // smmc_engine_simulate_portfolio (csrc/smmc_portfolio.cpp; include/smmc.h and DESIGN.md, "Portfolios", state the
@@ -2484,6 +2571,11 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, false, false>),
       reinterpret_cast<const void *>(excursions_kernel<SMMC_MODE_GAUSSIAN, true, false>),
       reinterpret_cast<const void *>(draw_words_kernel<SMMC_MODE_GAUSSIAN, false>),
+#define SMMC_SWEEP_KERNELS(S)                                                                                               \
+  reinterpret_cast<const void *>(cashflow_sweep_kernel<SMMC_MODE_GAUSSIAN, false, false, S>),                                \
+      reinterpret_cast<const void *>(cashflow_sweep_kernel<SMMC_MODE_GAUSSIAN, true, false, S>)
+      SMMC_SWEEP_KERNELS(2), SMMC_SWEEP_KERNELS(4), SMMC_SWEEP_KERNELS(8),
+#undef SMMC_SWEEP_KERNELS
 #define SMMC_PORTFOLIO_KERNELS(K) /* both modes: the asset table is read through absolute addresses too */                  \
   reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_GAUSSIAN, false, false, K>),                                     \
       reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_GAUSSIAN, true, false, K>),                                  \
@@ -2763,6 +2855,42 @@ hipError_t launch_cashflow(const KernelArgs &a, const CashflowArgs &c, bool exac
 
 hipError_t launch_finalize_depleted(unsigned long long *acc, uint32_t n, unsigned long long *d_out, hipStream_t stream) {
   hipLaunchKernelGGL(finalize_depleted_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, acc, n, d_out);
+  return hipGetLastError();
+}
+
+// ---- cash-flow sweeps ----
+
+size_t cashflow_sweep_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods, uint32_t n_bins, uint32_t n_scenarios) {
+  // counters: per scenario depletion [n_periods + 1] and histogram [n_bins]; sweep_width(n_scenarios) partials per wave
+  return wave_walk_lds_bytes(mode, table_len, static_cast<size_t>(n_scenarios) * (static_cast<size_t>(n_periods) + 1u + n_bins),
+                             sweep_width(n_scenarios));
+}
+
+struct SweepFamily {
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<SweepArgs> get(const SweepArgs &c) {
+    switch (sweep_width(c.n)) {
+      case 2: return cashflow_sweep_kernel<kMode, kExactDiv, kDense, 2>;
+      case 4: return cashflow_sweep_kernel<kMode, kExactDiv, kDense, 4>;
+      default: return cashflow_sweep_kernel<kMode, kExactDiv, kDense, 8>;
+    }
+  }
+};
+// a.d_final, c.d_paid, c.d_ruin_period: [c.n][a.n_paths]; a.partials: [c.n][grid]; a.d_hist: [c.n][a.n_bins] and
+// c.d_depleted: [c.n][a.n_periods + 1] counters, zero before the launch.  The entries of c from c.n up to
+// sweep_width(c.n) must be copies of entry c.n - 1.
+hipError_t launch_cashflow_sweep(const KernelArgs &a, const SweepArgs &c, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream == 2 || a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (c.n < 1 || c.n > SMMC_MAX_SWEEP) return hipErrorInvalidValue;
+  if (static_cast<uint64_t>(c.n) * (static_cast<uint64_t>(a.n_periods) + 1u + a.n_bins) > SMMC_MAX_SWEEP_COUNTERS) return hipErrorInvalidValue;
+  return launch_wave_walk<SweepFamily>(a, c, exact_div, grid, cashflow_sweep_lds_bytes(a.mode, a.table_len, a.n_periods, a.n_bins, c.n),
+                                       stream);
+}
+
+hipError_t launch_finalize_sweep(const BlockPartial *partials, uint32_t n_partials, uint32_t n_scenarios, void *d_records,
+                                 uint32_t n_bins, unsigned long long *hist_acc, hipStream_t stream) {
+  hipLaunchKernelGGL(finalize_checkpoints_kernel, dim3(n_scenarios), dim3(kCheckpointFinalizeBlock), 0, stream, partials, n_partials,
+                     static_cast<unsigned char *>(d_records), n_bins, hist_acc);
   return hipGetLastError();
 }
 

@@ -141,6 +141,52 @@ class CashflowResult:
         return 1.0 - gone / n
 
 
+@dataclasses.dataclass
+class SweepResult:
+    """What Engine.simulate_cashflow_sweep returns: S scenarios on the same paths, scenario-major; None for what was
+    not asked for."""
+    n_paths: int
+    n_periods: int
+    amounts: np.ndarray             # float32 [S]: the scenarios as they were run
+    fractions: np.ndarray
+    floors: np.ndarray
+    final: object = None            # torch.float32 [S, n_paths] on the engine's device: 0 for a depleted path
+    paid: object = None             # torch.float32 [S, n_paths]
+    ruin_period: object = None      # torch.int32 [S, n_paths] holding uint32 values: period of depletion, 0 = never
+    stats: list = None              # S records of the final values
+    depleted_at: np.ndarray = None  # uint64 [S, n_periods + 1]: [s, 0] never depleted, [s, t] depleted at period t
+
+    def _counts(self, what):
+        if self.depleted_at is None:
+            raise ValueError(f"{what}() needs depleted_at (want_depleted_at=True)")
+        d = np.asarray(self.depleted_at, dtype=np.float64)
+        if d.ndim != 2:
+            raise ValueError("depleted_at must have shape [scenarios, n_periods + 1]")
+        return d
+
+    def survival(self):
+        """[S, n_periods + 1]: row s is CashflowResult.survival() of scenario s."""
+        d = self._counts("survival")
+        return np.stack([CashflowResult(self.n_paths, self.n_periods, depleted_at=row).survival() for row in d]) if d.size else d
+
+    def depleted_share(self):
+        """[S]: the share of paths depleted at any period."""
+        d = self._counts("depleted_share")
+        n = d.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, (n - d[:, 0]) / n, np.nan)
+
+    def highest_surviving(self, confidence):
+        """The index of the scenario with the largest amount whose share of paths alive after the last period is at
+        least `confidence` (0 .. 1); None if no scenario of the swept grid reaches it (ties: the first such scenario)."""
+        alive = self.survival()[:, -1]
+        best = None
+        for s in np.flatnonzero(alive >= float(confidence)):
+            if best is None or self.amounts[s] > self.amounts[best]:
+                best = int(s)
+        return best
+
+
 def _by_period(counts, what):
     """Cumulative share of paths whose first passage lies at or before each period, from a [n_periods + 1] count
     array ([0]: never, [t]: first at period t)."""
@@ -515,6 +561,98 @@ class Engine:
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rc = self._L.smmc_engine_cashflow_divide_kind(self._h, C.byref(sim), C.byref(cf))
         del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- cash-flow sweeps: up to MAX_SWEEP constant schedules on the same paths (smmc_engine_simulate_cashflow_sweep) ----
+    @staticmethod
+    def make_sweep(amounts, fractions=0.0, floors=0.0):
+        """(array of smmc_cashflow, amounts, fractions, floors as float32 [S]): scalars broadcast over the scenarios."""
+        try:
+            am, fr, fl = np.broadcast_arrays(np.atleast_1d(np.asarray(amounts, dtype=np.float32)),
+                                             np.asarray(fractions, dtype=np.float32), np.asarray(floors, dtype=np.float32))
+        except ValueError:
+            raise ValueError("amounts, fractions and floors must be scalars or sequences of one length") from None
+        if am.ndim != 1:
+            raise ValueError("amounts, fractions and floors must be scalars or one-dimensional")
+        cfs = (_lib.Cashflow * max(am.size, 1))()
+        for s in range(am.size):
+            cfs[s].struct_size = C.sizeof(_lib.Cashflow)
+            cfs[s].amount, cfs[s].fraction, cfs[s].floor = float(am[s]), float(fr[s]), float(fl[s])
+        return cfs, am.copy(), fr.copy(), fl.copy()
+
+    def simulate_cashflow_sweep(self, sim, amounts, fractions=0.0, floors=0.0, want_final=False, want_paid=False,
+                                want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Up to MAX_SWEEP constant cash-flow schedules on the SAME paths in one launch: scenario s takes amounts[s] +
+        fractions[s] * value out after every period and is depleted at floors[s], exactly as simulate_cashflow with
+        those three (scalars broadcast).  Returns a SweepResult; per-path outputs ([S, n_paths]) stay on the device,
+        stats and depleted_at are read back (that waits).  include/smmc.h states the contract."""
+        raw = self.simulate_cashflow_sweep_raw(sim, amounts, fractions, floors, want_final, want_paid, want_ruin_period,
+                                               want_stats, want_depleted_at)
+        _, am, fr, fl = self.make_sweep(amounts, fractions, floors)
+        res = SweepResult(int(sim.n_paths), int(sim.n_periods), am, fr, fl, raw["final"], raw["paid"], raw["ruin_period"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            host, rec = raw["stats_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
+            res.stats = []
+            for s in range(am.size):
+                st = stats_from_bytes(host[s * rec:(s + 1) * rec])
+                st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+                res.stats.append(st)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_cashflow_sweep_raw(self, sim, amounts, fractions=0.0, floors=0.0, want_final=False, want_paid=False,
+                                    want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Enqueues the sweep and returns its device tensors without waiting: a dict with final, paid (float32
+        [S, n_paths]), ruin_period (int32 holding uint32 values), stats_raw (uint8 [S, smmc_stats_bytes(n_bins)]) and
+        depleted_at (int64 holding uint64 counts, [S, n_periods + 1]); None for what was not asked for."""
+        torch = self._torch
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
+        S = int(am.size)
+        new = lambda want, count, dtype: torch.empty((S, count), dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        out = {"final": new(want_final, n, torch.float32), "paid": new(want_paid, n, torch.float32),
+               "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_cashflow_sweep(
+            self._h, C.byref(sim), cfs, S, ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
+            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
+        self._leave(cur, *out.values())
+        return out
+
+    def simulate_cashflow_sweep_to_host(self, sim, amounts, fractions=0.0, floors=0.0, want_final=False, want_paid=False,
+                                        want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_cashflow_sweep_to_host: a dict of numpy arrays, scenario-major
+        (stats_raw: the S packed records as bytes)."""
+        n, p = int(sim.n_paths), int(sim.n_periods)
+        cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
+        S = int(am.size)
+        new = lambda want, count, dtype: np.zeros((S, count), dtype=dtype) if want else None  # noqa: E731
+        out = {"final": new(want_final, n, np.float32), "paid": new(want_paid, n, np.float32),
+               "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_cashflow_sweep_to_host(
+            self._h, C.byref(sim), cfs, S, ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
+            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
+        if want_stats:
+            out["stats_raw"] = out["stats_raw"].tobytes()
+        return out
+
+    def cashflow_sweep_divide_kind(self, sim, amounts, fractions=0.0, floors=0.0):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_cashflow_sweep uses for this request: FAST only if every
+        scenario's own rule says so (results never depend on it)."""
+        cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
+        rc = self._L.smmc_engine_cashflow_sweep_divide_kind(self._h, C.byref(sim), cfs, int(am.size))
         if rc < 0:
             _lib.check(rc)
         return rc
