@@ -516,6 +516,81 @@ int smmc_engine_simulate_portfolio_to_host(smmc_engine *e, const smmc_sim *sim, 
  * stays 0 in both forms.  SMMC_FLAG_EXACT_DIV forces the IEEE divide. */
 int smmc_engine_portfolio_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf);
 
+/* ---- portfolio cash flows: a schedule on a rebalanced portfolio, with depletion statistics ------ */
+
+/* "60/40, rebalanced yearly, 4 % out every year, contributions before that": the portfolio of smmc_portfolio (meaning,
+ * checks and draws exactly as in smmc_engine_simulate_portfolio, the asset table of smmc_engine_set_asset_table
+ * included) with the cash flow of smmc_cashflow (meaning and checks exactly as in smmc_engine_simulate_cashflow; amounts
+ * and fractions may be arrays; 1 <= n_periods <= SMMC_MAX_CASHFLOW_PERIODS) taken out of its value after every period's
+ * return.  Counter stream v3 only.  The two parent calls cannot be combined into this from outside: with a cash flow
+ * and a rebalance a path's value is no function of two separate runs.
+ *
+ * Per path, every operation ONE binary32 rounding, nothing fused, every comparison false for NaN; a_k(t) are the
+ * portfolio contract's multipliers, R = rebalance_every, P = n_periods:
+ *   start            h_k = fl(capital * w_k);  paid = 0;  ruin = 0;  alive
+ *   t = 1 .. P       h_k = fl(fl(h_k * a_k(t)) / 100.0f)            every asset, as the portfolio step
+ *                    g   = ((h_0 + h_1) + h_2) + h_3                left to right over K
+ *                    w   = fl(amount[t-1] + fl(g * fraction[t-1]))
+ *                    vn  = fl(g - w)
+ *     live, vn > floor:     paid = fl(paid + w);  v = vn
+ *                           if R > 0 and t mod R == 0 and t != P:   h_k = fl(vn * w_k)          rebalance what is left
+ *                           else:                                   h_k = fl(h_k - fl(w * w_k)) the flow settles at the
+ *                                                                                               target weights
+ *     live, !(vn > floor):  depleted at t: every h_k = 0, v = 0, paid = fl(paid + fmaxf(g, 0)), ruin = t
+ *     depleted:             nothing changes (a lane mask keeps it so, not the arithmetic); its draws are still consumed
+ *   final value = v after period P;  final holdings = h_k after period P (no rebalance at P)
+ * What follows from it:
+ *   - The final value is vn.  The sum of the final holdings may differ from it in the last bits.
+ *   - A flow settles at the target weights: contributions buy the target mix, withdrawals sell it.  A holding whose
+ *     share of a withdrawal exceeds it turns NEGATIVE and compounds as such until the next rebalance; the contract does
+ *     not clamp it, and the value alone decides depletion.  Buy and hold with long withdrawals gets there.
+ *   - Zero flows (amount = fraction = 0, floor = 0, no arrays) give smmc_engine_simulate_portfolio's final values and
+ *     holdings bit for bit, while every value stays finite and above 0.
+ *   - Table mode with K = 1, w_0 = 1 and any R gives smmc_engine_simulate_cashflow's final, paid, ruin_period and
+ *     depleted_at bit for bit on that column.
+ *   - A path depends only on (seed, global path id, table or means and factor, weights, R, schedule, floor), never on
+ *     first_path, the shard or the launch geometry. */
+typedef struct smmc_portfolio_cashflow_outputs {
+  uint32_t struct_size, reserved; /* = sizeof(smmc_portfolio_cashflow_outputs), 0 */
+  float *d_final;          /* n_paths final values, 0 for a depleted path */
+  float *d_holdings;       /* final holdings, asset-major K x n_paths */
+  float *d_paid;           /* n_paths totals paid out */
+  uint32_t *d_ruin_period; /* n_paths periods of depletion, 0 = never */
+  void *d_stats;           /* packed record of the final values, smmc_stats_bytes(n_bins), with the field rules of
+                              smmc_engine_simulate */
+  uint64_t *d_depleted_at; /* n_periods + 1 counts: [0] never depleted, [t] depleted at period t; their sum is n_paths */
+} smmc_portfolio_cashflow_outputs;
+
+/* Enqueues one such simulation on the engine stream and returns without waiting; the host arrays of cf may be reused on
+ * return.  out holds DEVICE pointers (4-byte aligned, d_stats and d_depleted_at 8-byte), any may be NULL; they are
+ * written, not accumulated into.  Integer fields, min, max, bucket counts and the depletion counts are exact; sum and
+ * sumsq are double sums in a fixed order with no floating-point atomics, so two identical calls give the same bytes.
+ * Shards merge by smmc_stats_merge and by adding d_depleted_at.  n_paths == 0 launches nothing and yields the empty
+ * record and zero counts.
+ * SMMC_ERR_INVALID with a text: everything smmc_engine_simulate_portfolio refuses for sim and pf, everything
+ * smmc_engine_simulate_cashflow refuses for cf and n_periods; a NULL or wrongly sized out, or reserved != 0; asset
+ * table, depletion counters and histogram beyond the device's LDS; 2^32 or more paths per workgroup (shard the
+ * request). */
+int smmc_engine_simulate_portfolio_cashflow(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                            const smmc_cashflow *cf, const smmc_portfolio_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                    const smmc_cashflow *cf, const smmc_portfolio_cashflow_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT (never SMMC_DIV_CHECKED), or an error of the call's argument checks.  Results never
+ * depend on the form.  The reciprocal-multiply form is used only where the host proves that every product h_k * a_k is
+ * exactly 0 or has a magnitude inside [2^-89, 2^127) (the device self-test of the form covers both signs); otherwise,
+ * or with SMMC_FLAG_EXACT_DIV, the IEEE divide.  With the per-asset multiplier bounds of
+ * smmc_engine_portfolio_divide_kind, a positive capital, every positively weighted asset starting above 0, every
+ * fraction 0 and (capital + the sum of |amount|) grown by the best asset in every period below 2^126, FAST holds for
+ *   contributions only   every amount <= 0: holdings only gain, and the portfolio rule's lower bound stands;
+ *   one constant amount  not 0, no arrays, and floor > 0 if a rebalance happens (0 < R < P): a holding that enters a
+ *                        product is the initial one, at least floor * w_k after a rebalance, or a binary32 difference
+ *                        with the share fl(amount * w_k), which is 0 or at least 2^-25 of that share; each of these
+ *                        times the asset's smallest multiplier stays above 2^-88.
+ * Anything else -- a fraction, varying withdrawals -- is EXACT ("Portfolio cash flows", has the proof). */
+int smmc_engine_portfolio_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                               const smmc_cashflow *cf);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

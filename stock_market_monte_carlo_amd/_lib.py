@@ -130,6 +130,21 @@ class PortfolioOutputs(C.Structure):
         ("stats", C.c_void_p),
     ]
 
+
+class PortfolioCashflowOutputs(C.Structure):
+    """smmc_portfolio_cashflow_outputs"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("final", C.c_void_p),
+        ("holdings", C.c_void_p),
+        ("paid", C.c_void_p),
+        ("ruin_period", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("depleted_at", C.c_void_p),
+    ]
+
+
 # the pointer fields of smmc_excursion_outputs, in the order of the structure
 EXCURSION_OUTPUTS = ("final", "peak", "low", "drawdown", "drawdown_period", "underwater", "first_below", "first_reach",
                      "stats", "drawdown_stats", "first_below_at", "first_reach_at")
@@ -194,6 +209,12 @@ SYMBOLS = [
     ("smmc_engine_simulate_portfolio_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioOutputs)]),
     ("smmc_engine_portfolio_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio)]),
+    ("smmc_engine_simulate_portfolio_cashflow", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_simulate_portfolio_cashflow_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_portfolio_cashflow_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -78,15 +78,15 @@ bool varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }
 float amount_at(const smmc_cashflow *cf, uint32_t t) { return cf->amounts ? cf->amounts[t] : cf->amount; }
 float fraction_at(const smmc_cashflow *cf, uint32_t t) { return cf->fractions ? cf->fractions[t] : cf->fraction; }
 
-int check_cashflow(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
-  int rc = smmc::host_check_sim(e, sim);
-  if (rc) return rc;
+int check_cf_struct(const smmc_cashflow *cf) {
   if (!cf) return host_fail(SMMC_ERR_INVALID, "cf is NULL");
   if (cf->struct_size != sizeof(smmc_cashflow))
     return host_fail(SMMC_ERR_INVALID, "smmc_cashflow.struct_size is %u, this library expects %zu", cf->struct_size,
                      sizeof(smmc_cashflow));
-  rc = smmc::host_require_v3(sim, "cash flows support");
-  if (rc) return rc;
+  return SMMC_OK;
+}
+
+int check_schedule(const smmc_sim *sim, const smmc_cashflow *cf) {
   if (sim->n_periods == 0) return host_fail(SMMC_ERR_INVALID, "n_periods is 0: a cash flow needs at least one period");
   if (sim->n_periods > SMMC_MAX_CASHFLOW_PERIODS)
     return host_fail(SMMC_ERR_INVALID, "n_periods %u exceeds SMMC_MAX_CASHFLOW_PERIODS %d", sim->n_periods,
@@ -101,6 +101,41 @@ int check_cashflow(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflo
     if (cf->amounts && !std::isfinite(cf->amounts[t])) return host_fail(SMMC_ERR_INVALID, "amounts[%u] is not finite", t);
     if (cf->fractions && !std::isfinite(cf->fractions[t])) return host_fail(SMMC_ERR_INVALID, "fractions[%u] is not finite", t);
   }
+  return SMMC_OK;
+}
+
+int check_cashflow(const smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
+  int rc = smmc::host_check_sim(e, sim);
+  if (rc) return rc;
+  rc = check_cf_struct(cf);
+  if (rc) return rc;
+  rc = smmc::host_require_v3(sim, "cash flows support");
+  if (rc) return rc;
+  return check_schedule(sim, cf);
+}
+
+// Copies the arrays of a varying schedule into a free staging slot and enqueues their upload on the engine stream; c
+// gets the device copy and its stride.  Device must be current.
+int stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, smmc::CashflowArgs *c) {
+  const smmc::EngineView view = smmc::engine_view(e);
+  CashflowState *st = nullptr;
+  const int rc = state_of(e, &st);
+  if (rc) return rc;
+  const int slot = st->next;
+  if (st->in_flight[slot]) SMMC_HIP(hipEventSynchronize(st->uploaded[slot]));
+  st->in_flight[slot] = false;
+  const uint32_t stride = (sim->n_periods + 7u) & ~7u;
+  float *h = st->h_slots.p + static_cast<size_t>(slot) * 2u * kStrideMax;
+  for (uint32_t t = 0; t < stride; ++t) {
+    h[t] = t < sim->n_periods ? amount_at(cf, t) : 0.0f;
+    h[stride + t] = t < sim->n_periods ? fraction_at(cf, t) : 0.0f;
+  }
+  SMMC_HIP(hipMemcpyAsync(st->d_schedule.p, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
+  SMMC_HIP(hipEventRecord(st->uploaded[slot], view.stream));
+  st->in_flight[slot] = true;
+  st->next = (slot + 1) % kSlots;
+  c->schedule = st->d_schedule.p;
+  c->stride = stride;
   return SMMC_OK;
 }
 
@@ -150,6 +185,16 @@ int check_outputs(const void *fin, const void *paid, const void *ruin, const voi
 
 }  // namespace
 
+namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_internal.h)
+int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf) {
+  const int rc = check_cf_struct(cf);
+  return rc ? rc : check_schedule(sim, cf);
+}
+int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c) {
+  return stage_schedule(e, sim, cf, c);
+}
+}  // namespace smmc
+
 extern "C" {
 
 int smmc_engine_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf) {
@@ -185,24 +230,8 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   c.d_paid = d_paid;
   c.d_ruin_period = d_ruin_period;
   if (varying(cf) && grid) {
-    CashflowState *st = nullptr;
-    rc = state_of(e, &st);
+    rc = stage_schedule(e, sim, cf, &c);
     if (rc) return rc;
-    const int slot = st->next;
-    if (st->in_flight[slot]) SMMC_HIP(hipEventSynchronize(st->uploaded[slot]));
-    st->in_flight[slot] = false;
-    const uint32_t stride = (sim->n_periods + 7u) & ~7u;
-    float *h = st->h_slots.p + static_cast<size_t>(slot) * 2u * kStrideMax;
-    for (uint32_t t = 0; t < stride; ++t) {
-      h[t] = t < sim->n_periods ? amount_at(cf, t) : 0.0f;
-      h[stride + t] = t < sim->n_periods ? fraction_at(cf, t) : 0.0f;
-    }
-    SMMC_HIP(hipMemcpyAsync(st->d_schedule.p, h, sizeof(float) * 2u * stride, hipMemcpyHostToDevice, view.stream));
-    SMMC_HIP(hipEventRecord(st->uploaded[slot], view.stream));
-    st->in_flight[slot] = true;
-    st->next = (slot + 1) % kSlots;
-    c.schedule = st->d_schedule.p;
-    c.stride = stride;
   }
   a.d_final = d_final;
   smmc::ZeroLease lease;

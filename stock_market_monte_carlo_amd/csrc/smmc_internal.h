@@ -230,6 +230,17 @@ constexpr uint32_t portfolio_row_words(uint32_t n_assets) { return n_assets == 3
 // wave_walk_group_paths(mode) consecutive paths.
 hipError_t launch_portfolio(const KernelArgs &a, const PortfolioArgs &p, bool exact_div, uint32_t grid, hipStream_t stream);
 size_t portfolio_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_bins);
+// portfolio_cashflow_kernel (smmc_engine_simulate_portfolio_cashflow, csrc/smmc_portfolio_cashflow.cpp; counter stream
+// v3 only): portfolio_kernel's holdings and joint draws with cashflow_kernel's step on their sum after every period
+// ("Portfolio cash flows").  p and c as launch_portfolio and launch_cashflow take them; a.partials, a.d_hist
+// and c.d_depleted as launch_cashflow.
+struct PortfolioCashflowArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+};
+hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
+                                     hipStream_t stream);
+size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
@@ -322,5 +333,18 @@ typedef int (*HostEnqueue)(smmc_engine *e, const smmc_sim *part, float *d_final,
                            void *d_stats, const void *ctx);
 int host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final, float *host_chunk_mean, float *host_chunk_var,
                           volatile int64_t *progress, smmc_stats *stats, uint64_t *hist, HostEnqueue enqueue, const void *ctx);
+
+// ---- what smmc_portfolio.cpp and smmc_cashflow.cpp lend to smmc_portfolio_cashflow.cpp -----------------------------
+// Each rule is stated once, in the unit that owns it; neither unit refers to the borrower.
+// smmc_portfolio.cpp: every argument check of smmc_engine_simulate_portfolio on (e, sim, pf), the asset table included;
+int portfolio_check(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf);
+// bounds on asset k's multiplier a_k, false if there are none that keep it positive (the divide rule's);
+bool portfolio_asset_bounds(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, uint32_t k, double *lo_a, double *hi_a);
+// the KernelArgs and PortfolioArgs of a checked request (the asset table, the draw at scale 1, weights, s_k, L).
+void portfolio_launch_args(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, KernelArgs *a, PortfolioArgs *p);
+// smmc_cashflow.cpp: the checks of smmc_engine_simulate_cashflow on cf itself and on n_periods;
+int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf);
+// the arrays of a varying schedule staged and their upload enqueued: c->schedule, c->stride.  Device must be current.
+int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c);
 
 }  // namespace smmc

@@ -2518,6 +2518,120 @@ void portfolio_kernel(const KernelArgs k, const PortfolioArgs p) {
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- portfolio cash flows: a schedule on a rebalanced portfolio ------------------------------------
+//
+// smmc_engine_simulate_portfolio_cashflow (csrc/smmc_portfolio_cashflow.cpp; include/smmc.h and DESIGN.md, "Portfolio
+// cash flows", state the contract): portfolio_kernel's K holdings and joint draws with cashflow_kernel's step on their
+// sum after every period's return, every operation a binary32 rounding of its own:
+//   h_k = (h_k * a_k) / 100 for every asset;  g = ((h_0 + h_1) + h_2) + h_3
+//   w = amount + g * fraction,  vn = g - w
+//   live lane, vn > floor:     paid += w, v = vn, and h_k = vn * w_k at a rebalance, else h_k -= w * w_k
+//   live lane, !(vn > floor):  depleted at this period: every h_k = 0, v = 0, paid += max(g, 0), ruin_period = t
+//   depleted lane:             nothing changes; its draws are still made
+// The rebalance stays the uniform branch behind portfolio_kernel's scalar countdown, "live" is cashflow_kernel's lane
+// mask combined with the compare, control flow is wave-uniform.  A depleted lane's holdings are SET to 0 every period
+// (the select that also applies the step), so a product 0 * inf cannot carry a NaN along.  Bound like its parents:
+// VALU issue.  By source, on top of the K compounding chains: K - 1 adds (g), multiply, add, subtract, compare (w, vn,
+// live), K multiplies and K subtracts (or K multiplies at a rebalance), K + 1 selects (h_k, v), max, select, add
+// (paid), select (ruin_period): 4 K + 8.
+//
+// LDS: the asset table (or the v3 draw tables at scale 1) at address 0, then the [n_periods + 1] depletion counters,
+// then the [n_bins] buckets.  Schedule: as cashflow_kernel -- kernel arguments when constant, else one block's entries
+// through the constant address space, issued before the block's draws; no per-lane global load in the loop.
+template <int kMode, bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    float a[kDraws][K];
+    float am[kDraws], fr[kDraws];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) {
+#pragma unroll
+          for (int j = 0; j < kDraws; ++j) {  // the block's schedule entries (padded to whole blocks)
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+          portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a);
+        },
+        [&](int j, uint32_t t) {
+#pragma unroll
+          for (int y = 0; y < K; ++y) h[y] = compound<kExactDiv>(h[y], a[j][y]);
+          const float g = portfolio_value<K>(h);
+          const float w = __fadd_rn(am[j], __fmul_rn(g, fr[j]));
+          const float vn = __fsub_rn(g, w);
+          const bool goes_on = alive && vn > c.floor;  // false for NaN
+          const bool dies = alive && !goes_on;
+          float hn[K];
+          bool rebalance = false;
+          if (--until == 0u) {  // uniform: t mod every == 0
+            until = every;
+            rebalance = t != k.n_periods;  // the final holdings are formed before any rebalance at P
+          }
+          if (rebalance) {
+#pragma unroll
+            for (int y = 0; y < K; ++y) hn[y] = __fmul_rn(vn, p.weights[y]);
+          } else {  // the flow settles at the target weights
+#pragma unroll
+            for (int y = 0; y < K; ++y) hn[y] = __fsub_rn(h[y], __fmul_rn(w, p.weights[y]));
+          }
+#pragma unroll
+          for (int y = 0; y < K; ++y) h[y] = goes_on ? hn[y] : 0.0f;
+          v = goes_on ? vn : 0.0f;
+          // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0), and paid + 0 is paid (paid is never -0)
+          paid = __fadd_rn(paid, goes_on ? w : fmaxf(g, 0.0f));
+          ruin = dies ? t : ruin;
+          alive = goes_on;
+        });
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 }  // namespace
 
 hipError_t launch_selftest(uint32_t lo, uint32_t hi, unsigned long long *d_count, uint32_t grid,
@@ -2585,6 +2699,18 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(portfolio_kernel<SMMC_MODE_TABLE, true, false, K>)
       SMMC_PORTFOLIO_KERNELS(1), SMMC_PORTFOLIO_KERNELS(2), SMMC_PORTFOLIO_KERNELS(3), SMMC_PORTFOLIO_KERNELS(4),
 #undef SMMC_PORTFOLIO_KERNELS
+#define SMMC_PORTFOLIO_CASHFLOW_KERNELS(K, V)                                                                               \
+  reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),                         \
+      reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),                      \
+      reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_TABLE, false, true, K, V>),                         \
+      reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_TABLE, true, true, K, V>),                          \
+      reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_TABLE, false, false, K, V>),                        \
+      reinterpret_cast<const void *>(portfolio_cashflow_kernel<SMMC_MODE_TABLE, true, false, K, V>)
+      SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, false), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, false),
+      SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, false), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, false),
+      SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, true),
+      SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, true),
+#undef SMMC_PORTFOLIO_CASHFLOW_KERNELS
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -2968,6 +3094,39 @@ hipError_t launch_portfolio(const KernelArgs &a, const PortfolioArgs &p, bool ex
   if (a.stream != 3 || p.n_assets < 1 || p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
   if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
   return launch_wave_walk<PortfolioFamily>(a, p, exact_div, grid, portfolio_lds_bytes(a.mode, a.table_len, p.n_assets, a.n_bins), stream);
+}
+
+// ---- portfolio cash flows ----
+
+size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins) {
+  // the padded rows in the table's place; counters: depletion [n_periods + 1], histogram [n_bins]; one partial per wave
+  return wave_walk_lds_bytes(mode, n_rows * portfolio_row_words(n_assets), static_cast<size_t>(n_periods) + 1u + n_bins, 1u);
+}
+
+struct PortfolioCashflowFamily {
+  template <int kMode, bool kExactDiv, bool kDense, int K>
+  static WalkKernel<PortfolioCashflowArgs> schedule(const PortfolioCashflowArgs &x) {
+    return x.c.schedule ? portfolio_cashflow_kernel<kMode, kExactDiv, kDense, K, true>
+                        : portfolio_cashflow_kernel<kMode, kExactDiv, kDense, K, false>;
+  }
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<PortfolioCashflowArgs> get(const PortfolioCashflowArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return schedule<kMode, kExactDiv, kDense, 1>(x);
+      case 2: return schedule<kMode, kExactDiv, kDense, 2>(x);
+      case 3: return schedule<kMode, kExactDiv, kDense, 3>(x);
+      default: return schedule<kMode, kExactDiv, kDense, 4>(x);
+    }
+  }
+};
+hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
+                                     hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
+  return launch_wave_walk<PortfolioCashflowFamily>(
+      a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
 }
 
 }  // namespace smmc

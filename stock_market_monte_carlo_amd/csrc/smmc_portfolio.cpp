@@ -169,14 +169,9 @@ struct Plan {
   smmc::PortfolioArgs p;
   uint32_t grid;
 };
-int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bool want_stats, Plan *out) {
-  const smmc::EngineView view = smmc::engine_view(e);
-  int rc = smmc::host_wave_walk_grid(view, sim->n_paths, smmc::wave_walk_group_paths(sim->mode), kPortfolioGroupsPerCU, view.max_grid,
-                                     &out->grid);
-  if (rc) return rc;
-  smmc::KernelArgs &a = out->a;
+void launch_args(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, smmc::KernelArgs *args, smmc::PortfolioArgs *pa) {
+  smmc::KernelArgs &a = *args;
   a = smmc::host_make_args(e, sim);
-  if (!want_stats) a.n_bins = 0;
   a.table_a = nullptr;
   a.table_len = 0;
   if (sim->mode == SMMC_MODE_TABLE) {
@@ -187,7 +182,7 @@ int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bo
   a.gauss_mean = 0.0f;  // the staged draw yields standard normals: scale 1, shift 0
   a.gauss_std = 1.0f;
   a.gauss_shift100 = 0.0f;
-  smmc::PortfolioArgs &p = out->p;
+  smmc::PortfolioArgs &p = *pa;
   std::memset(&p, 0, sizeof p);
   p.n_assets = pf->n_assets;
   p.rebalance_every = pf->rebalance_every;
@@ -196,6 +191,16 @@ int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bo
     p.shift100[k] = 100.0f + pf->means[k];
   }
   std::memcpy(p.factor, pf->factor, sizeof p.factor);
+}
+int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bool want_stats, Plan *out) {
+  const smmc::EngineView view = smmc::engine_view(e);
+  int rc = smmc::host_wave_walk_grid(view, sim->n_paths, smmc::wave_walk_group_paths(sim->mode), kPortfolioGroupsPerCU, view.max_grid,
+                                     &out->grid);
+  if (rc) return rc;
+  launch_args(e, sim, pf, &out->a, &out->p);
+  smmc::KernelArgs &a = out->a;
+  if (!want_stats) a.n_bins = 0;
+  const smmc::PortfolioArgs &p = out->p;
   const size_t lds = smmc::portfolio_lds_bytes(a.mode, a.table_len, p.n_assets, a.n_bins);
   if (lds + 2048 > view.max_lds)
     return host_fail(SMMC_ERR_INVALID, "asset table, histogram and partials need %zu bytes of LDS, device allows %zu", lds, view.max_lds);
@@ -203,6 +208,16 @@ int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bo
 }
 
 }  // namespace
+
+namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_internal.h)
+int portfolio_check(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf) { return check_portfolio(e, sim, pf); }
+bool portfolio_asset_bounds(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, uint32_t k, double *lo_a, double *hi_a) {
+  return asset_bounds(e, sim, pf, k, lo_a, hi_a);
+}
+void portfolio_launch_args(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, KernelArgs *a, PortfolioArgs *p) {
+  launch_args(e, sim, pf, a, p);
+}
+}  // namespace smmc
 
 extern "C" {
 

@@ -238,6 +238,14 @@ class PortfolioResult:
     stats: Stats = None      # record of the final values
 
 
+@dataclasses.dataclass
+class PortfolioCashflowResult(CashflowResult):
+    """What Engine.simulate_portfolio_cashflow returns: CashflowResult's outputs (survival() included) of the portfolio's
+    value, and the final holdings."""
+    n_assets: int = 0
+    holdings: object = None  # torch.float32 [n_assets, n_paths]: the final holdings (no rebalance at P), 0 for a depleted path
+
+
 def cholesky_factor(stds, corr):
     """The lower-triangular factor L (float32 [K, K], percent) of diag(stds) corr diag(stds), for
     Engine.simulate_portfolio(factor=...): numpy's float64 Cholesky, cast once.  Raises ValueError for a matrix that
@@ -913,6 +921,93 @@ class Engine:
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_portfolio uses for this request (results never depend on it)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         rc = self._L.smmc_engine_portfolio_divide_kind(self._h, C.byref(sim), C.byref(pf))
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- portfolio cash flows: a schedule on a rebalanced portfolio (smmc_engine_simulate_portfolio_cashflow) -----
+    _PFCF_OUTPUTS = (("final", "final"), ("holdings", "holdings"), ("paid", "paid"), ("ruin_period", "ruin_period"),
+                     ("stats", "stats_raw"), ("depleted_at", "depleted_at"))
+
+    def simulate_portfolio_cashflow(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                                    fractions=None, means=None, factor=None, want_final=True, want_holdings=False,
+                                    want_paid=False, want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """simulate_portfolio's portfolio with simulate_cashflow's schedule taken out of its value after every period: the
+        flow settles at the target weights, a rebalance sets the holdings to the weights' shares of what is left, and a
+        path whose value would not stay above `floor` is depleted.  Returns a PortfolioCashflowResult; per-path outputs
+        stay on the device, stats and depleted_at are read back (that waits).  include/smmc.h states the arithmetic."""
+        raw = self.simulate_portfolio_cashflow_raw(sim, weights, rebalance_every, amount, fraction, floor, amounts, fractions,
+                                                   means, factor, want_final, want_holdings, want_paid, want_ruin_period,
+                                                   want_stats, want_depleted_at)
+        res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                      n_assets=raw["n_assets"], holdings=raw["holdings"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_portfolio_cashflow_raw(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
+                                        amounts=None, fractions=None, means=None, factor=None, want_final=True,
+                                        want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                                        want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, holdings, paid (float32),
+        ruin_period (int32 holding uint32 values), stats_raw (uint8, the packed record) and depleted_at (int64 holding
+        uint64 counts, n_periods + 1); None for what was not asked for."""
+        torch = self._torch
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
+               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        del keep
+        return res
+
+    def simulate_portfolio_cashflow_to_host(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
+                                            amounts=None, fractions=None, means=None, factor=None, want_final=True,
+                                            want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                                            want_depleted_at=True):
+        """The same through smmc_engine_simulate_portfolio_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        del keep
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def portfolio_cashflow_divide_kind(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                                       fractions=None, means=None, factor=None):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_portfolio_cashflow uses for this request (results never depend on it)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        rc = self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
+        del keep
         if rc < 0:
             _lib.check(rc)
         return rc
