@@ -183,6 +183,12 @@ def test_the_divide_form(oracle, engines):
     try:
         e2.set_asset_table(doubling)
         assert e2.portfolio_divide_kind(_sim("t37", n, 360), ref.WEIGHTS[2], 12) == _lib.DIV_EXACT
+        # ... and the run the host then makes with the IEEE divide is the restatement's, +100 % months included
+        values, holdings = ref.simulate(ref.table_multipliers(oracle, doubling, ref.SEED, ref.FIRST_PATH, n, 360), ref.WEIGHTS[2], 12)
+        assert (values[:, 1:] > 1.4 * values[:, :-1]).any()  # a value up by 40 % in one month: the planted month is drawn
+        r = e2.simulate_portfolio(_sim("t37", n, 360), ref.WEIGHTS[2], 12, want_holdings=True)
+        assert np.array_equal(_bits(r.final.cpu().numpy()), _bits(values[:, 360]))
+        assert np.array_equal(_bits(r.holdings.cpu().numpy()), _bits(holdings))
     finally:
         e2.close()
 

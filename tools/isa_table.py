@@ -15,11 +15,19 @@ import isa_loop_count as I  # noqa: E402
 import isa_loops as L  # noqa: E402
 
 
+def instantiations(path, kernel, lines=None):
+    """(symbol prefix, symbols) of every instantiation of smmc::(anon)::<kernel> in the .s file: names only, which is all
+    tests/test_feature_matrix_cpu.py needs of rows() -- the per-row loop analysis below takes seconds per kernel."""
+    lines = open(path).read().splitlines() if lines is None else lines
+    prefix = f"_ZN4smmc12_GLOBAL__N_1{len(kernel)}{kernel}"
+    return prefix, [l.split(":")[0] for l in lines if l.startswith(prefix) and ": ; @" in l]
+
+
 def rows(path, kernel):
     lines = open(path).read().splitlines()
-    prefix = f"_ZN4smmc12_GLOBAL__N_1{len(kernel)}{kernel}"
+    prefix, symbols = instantiations(path, kernel, lines)
     out = {}
-    for sym in [l.split(":")[0] for l in lines if l.startswith(prefix) and ": ; @" in l]:
+    for sym in symbols:
         variant = sym[len(prefix):]
         meta = {}
         for l in lines:
