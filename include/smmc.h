@@ -591,6 +591,57 @@ int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_s
 int smmc_engine_portfolio_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                const smmc_cashflow *cf);
 
+/* ---- allocation sweeps: up to eight portfolio strategies on one set of draws, one launch ------- */
+
+/* "Which mix, rebalanced how often, still carries this withdrawal?": n_scenarios (1 .. SMMC_MAX_SWEEP) strategies
+ * stepped on the same jointly drawn paths, the draw made once per period (common random numbers, as in
+ * smmc_engine_simulate_cashflow_sweep).  Counter stream v3 only.  pfs and cfs are HOST arrays of n_scenarios entries
+ * each and may be reused on return; scenario s is (pfs[s], cfs[s]).
+ *   - Every pfs[s] passes the checks of smmc_engine_simulate_portfolio on its own.  All of them share the joint law:
+ *     n_assets, means and factor equal pfs[0]'s bit for bit; weights and rebalance_every are per scenario.  Table mode
+ *     uses the engine's asset table (smmc_engine_set_asset_table).
+ *   - Every cfs[s] is a CONSTANT schedule (amounts and fractions NULL); amount, fraction and floor are per scenario.
+ * Scenario s IS smmc_engine_simulate_portfolio_cashflow(sim, &pfs[s], &cfs[s]): final, holdings, paid, ruin_period,
+ * depleted_at and the record's integer fields, min, max and bucket counts are that call's bit for bit; sum and sumsq
+ * are double sums in a fixed order of the sweep's own (no floating-point atomics: two identical sweeps give the same
+ * bytes) and agree with the single call's to 1e-12 relative.  A path depends on (seed, global path id, law, its own
+ * scenario) only: not on the other scenarios, on n_scenarios, on first_path or on the launch geometry.  Shards merge
+ * by smmc_stats_merge and by adding d_depleted_at, scenario by scenario.
+ *
+ * Divide by 100: the reciprocal-multiply form if and only if smmc_engine_portfolio_cashflow_divide_kind says
+ * SMMC_DIV_FAST for EVERY scenario; otherwise, or with SMMC_FLAG_EXACT_DIV, the IEEE divide for all of them
+ * (smmc_engine_allocation_sweep_divide_kind says which).  Results never depend on the form. */
+typedef struct smmc_allocation_sweep_outputs {
+  uint32_t struct_size, reserved; /* = sizeof(smmc_allocation_sweep_outputs), 0 */
+  float *d_final;          /* [n_scenarios][n_paths] final values, 0 for a depleted path */
+  float *d_holdings;       /* [n_scenarios][K][n_paths] final holdings, asset-major inside a scenario */
+  float *d_paid;           /* [n_scenarios][n_paths] totals paid out */
+  uint32_t *d_ruin_period; /* [n_scenarios][n_paths] periods of depletion, 0 = never */
+  void *d_stats;           /* n_scenarios packed records of smmc_stats_bytes(n_bins) bytes each */
+  uint64_t *d_depleted_at; /* [n_scenarios][n_periods + 1] counts; every row sums to n_paths */
+} smmc_allocation_sweep_outputs;
+
+/* Enqueues one sweep on the engine stream and returns without waiting.  out holds DEVICE pointers (4-byte aligned,
+ * d_stats and d_depleted_at 8-byte), any may be NULL; they are written, not accumulated into.  n_paths == 0 launches
+ * nothing and yields empty records and zero counts.
+ * SMMC_ERR_INVALID with a text, before any device work: everything smmc_engine_simulate_portfolio_cashflow refuses, for
+ * any scenario; NULL pfs or cfs; n_scenarios 0 or above SMMC_MAX_SWEEP; a scenario with amounts or fractions; a
+ * scenario whose n_assets, means or factor differ from pfs[0]'s (the text names the scenario and the field);
+ * n_scenarios * (n_periods + 1 + n_bins) above SMMC_MAX_SWEEP_COUNTERS, n_bins counting as 0 when d_stats is NULL;
+ * asset table, counters and partials beyond the device's LDS; 2^32 paths or more per workgroup (shard the request); a
+ * NULL or wrongly sized out, or reserved != 0. */
+int smmc_engine_simulate_allocation_sweep(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs,
+                                          const smmc_cashflow *cfs, uint32_t n_scenarios,
+                                          const smmc_allocation_sweep_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_allocation_sweep_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs,
+                                                  const smmc_cashflow *cfs, uint32_t n_scenarios,
+                                                  const smmc_allocation_sweep_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT: the divide a sweep of (sim, pfs, cfs) uses, or an error of that call's checks on
+ * the scenarios. */
+int smmc_engine_allocation_sweep_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs,
+                                             const smmc_cashflow *cfs, uint32_t n_scenarios);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

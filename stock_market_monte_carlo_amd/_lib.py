@@ -30,7 +30,7 @@ MAX_RANKS = 8
 MAX_CHECKPOINTS = 64
 MAX_CHECKPOINT_BINS = 8192  # largest n_checkpoints * n_bins of one simulate_checkpoints call
 MAX_CASHFLOW_PERIODS = 4096  # largest n_periods of a simulate_cashflow call
-MAX_SWEEP = 8  # most scenarios of a simulate_cashflow_sweep call
+MAX_SWEEP = 8  # most scenarios of a simulate_cashflow_sweep or simulate_allocation_sweep call
 MAX_SWEEP_COUNTERS = 8192  # largest n_scenarios * (n_periods + 1 + n_bins) of one
 MAX_EXCURSION_PERIODS = 4096  # largest n_periods of a simulate_excursions call
 MAX_ASSETS = 4  # most assets of a simulate_portfolio call
@@ -145,6 +145,11 @@ class PortfolioCashflowOutputs(C.Structure):
     ]
 
 
+class AllocationSweepOutputs(C.Structure):
+    """smmc_allocation_sweep_outputs"""
+    _fields_ = PortfolioCashflowOutputs._fields_  # the same pointers, scenario-major
+
+
 # the pointer fields of smmc_excursion_outputs, in the order of the structure
 EXCURSION_OUTPUTS = ("final", "peak", "low", "drawdown", "drawdown_period", "underwater", "first_below", "first_reach",
                      "stats", "drawdown_stats", "first_below_at", "first_reach_at")
@@ -215,6 +220,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(PortfolioCashflowOutputs)]),
     ("smmc_engine_portfolio_cashflow_divide_kind", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow)]),
+    ("smmc_engine_simulate_allocation_sweep", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_uint32, C.POINTER(AllocationSweepOutputs)]),
+    ("smmc_engine_simulate_allocation_sweep_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_uint32, C.POINTER(AllocationSweepOutputs)]),
+    ("smmc_engine_allocation_sweep_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_uint32]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -241,6 +241,26 @@ struct PortfolioCashflowArgs {
 hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
                                      hipStream_t stream);
 size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// allocation_sweep_kernel (smmc_engine_simulate_allocation_sweep, csrc/smmc_allocation_sweep.cpp; counter stream v3
+// only): n constant-schedule strategies (weights, rebalance_every, amount, fraction, floor) stepped on ONE joint draw
+// per period ("Allocation sweeps").  p: the law as launch_portfolio takes it (n_assets, shift100, factor;
+// p.weights and p.rebalance_every are not read), p.d_holdings: [n][n_assets][n_paths].  The kernel is compiled for 4 and
+// 8 scenarios: entries n .. allocation_sweep_width(n) - 1 are copies of entry n - 1 and leave no output.
+struct AllocationSweepArgs {
+  PortfolioArgs p;
+  uint32_t n;  // 1 .. SMMC_MAX_SWEEP: the scenarios whose outputs are written
+  float weights[SMMC_MAX_SWEEP][SMMC_MAX_ASSETS];
+  uint32_t rebalance_every[SMMC_MAX_SWEEP];
+  float amount[SMMC_MAX_SWEEP], fraction[SMMC_MAX_SWEEP], floor[SMMC_MAX_SWEEP];
+  float *d_paid;                   // nullable: [n][n_paths]
+  uint32_t *d_ruin_period;         // nullable: [n][n_paths]
+  unsigned long long *d_depleted;  // nullable: [n][n_periods + 1] counters, zero before the launch
+};
+constexpr uint32_t allocation_sweep_width(uint32_t n) { return n <= 4u ? 4u : 8u; }
+// a.d_final: [n][n_paths]; a.partials: [n][grid] entries or null; a.d_hist: [n][a.n_bins] counters, zero before the
+// launch (folded by launch_finalize_sweep, the depletion counts by launch_finalize_depleted).
+hipError_t launch_allocation_sweep(const KernelArgs &a, const AllocationSweepArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
+size_t allocation_sweep_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins, uint32_t n_scenarios);
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0

@@ -2538,6 +2538,44 @@ void portfolio_kernel(const KernelArgs k, const PortfolioArgs p) {
 // LDS: the asset table (or the v3 draw tables at scale 1) at address 0, then the [n_periods + 1] depletion counters,
 // then the [n_bins] buckets.  Schedule: as cashflow_kernel -- kernel arguments when constant, else one block's entries
 // through the constant address space, issued before the block's draws; no per-lane global load in the loop.
+// One period of that recurrence for one strategy: the draw's K multipliers a, the strategy's weights, flow and floor,
+// its state h, v, paid, ruin, `alive` (a lane mask) and `until`, the scalar countdown to its next rebalance (`every` = 0:
+// the countdown never ends).  portfolio_cashflow_kernel makes one per draw, allocation_sweep_kernel one per draw and
+// scenario.
+template <bool kExactDiv, int K>
+__device__ __forceinline__ void portfolio_cashflow_step(const float (&a)[K], const float (&weights)[SMMC_MAX_ASSETS], float amount,
+                                                        float fraction, float floor, uint32_t every, uint32_t n_periods, uint32_t t,
+                                                        float (&h)[K], float &v, float &paid, uint32_t &ruin, bool &alive,
+                                                        uint32_t &until) {
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = compound<kExactDiv>(h[y], a[y]);
+  const float g = portfolio_value<K>(h);
+  const float w = __fadd_rn(amount, __fmul_rn(g, fraction));
+  const float vn = __fsub_rn(g, w);
+  const bool goes_on = alive && vn > floor;  // false for NaN
+  const bool dies = alive && !goes_on;
+  float hn[K];
+  bool rebalance = false;
+  if (--until == 0u) {  // uniform: t mod every == 0
+    until = every;
+    rebalance = t != n_periods;  // the final holdings are formed before any rebalance at P
+  }
+  if (rebalance) {
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fmul_rn(vn, weights[y]);
+  } else {  // the flow settles at the target weights
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fsub_rn(h[y], __fmul_rn(w, weights[y]));
+  }
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = goes_on ? hn[y] : 0.0f;
+  v = goes_on ? vn : 0.0f;
+  // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0), and paid + 0 is paid (paid is never -0)
+  paid = __fadd_rn(paid, goes_on ? w : fmaxf(g, 0.0f));
+  ruin = dies ? t : ruin;
+  alive = goes_on;
+}
+
 template <int kMode, bool kExactDiv, bool kDense, int K, bool kVarying>
 __global__ __launch_bounds__(64 * walk_waves(kMode))
 void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x) {
@@ -2584,33 +2622,8 @@ void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x
           portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a);
         },
         [&](int j, uint32_t t) {
-#pragma unroll
-          for (int y = 0; y < K; ++y) h[y] = compound<kExactDiv>(h[y], a[j][y]);
-          const float g = portfolio_value<K>(h);
-          const float w = __fadd_rn(am[j], __fmul_rn(g, fr[j]));
-          const float vn = __fsub_rn(g, w);
-          const bool goes_on = alive && vn > c.floor;  // false for NaN
-          const bool dies = alive && !goes_on;
-          float hn[K];
-          bool rebalance = false;
-          if (--until == 0u) {  // uniform: t mod every == 0
-            until = every;
-            rebalance = t != k.n_periods;  // the final holdings are formed before any rebalance at P
-          }
-          if (rebalance) {
-#pragma unroll
-            for (int y = 0; y < K; ++y) hn[y] = __fmul_rn(vn, p.weights[y]);
-          } else {  // the flow settles at the target weights
-#pragma unroll
-            for (int y = 0; y < K; ++y) hn[y] = __fsub_rn(h[y], __fmul_rn(w, p.weights[y]));
-          }
-#pragma unroll
-          for (int y = 0; y < K; ++y) h[y] = goes_on ? hn[y] : 0.0f;
-          v = goes_on ? vn : 0.0f;
-          // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0), and paid + 0 is paid (paid is never -0)
-          paid = __fadd_rn(paid, goes_on ? w : fmaxf(g, 0.0f));
-          ruin = dies ? t : ruin;
-          alive = goes_on;
+          portfolio_cashflow_step<kExactDiv, K>(a[j], p.weights, am[j], fr[j], c.floor, every, k.n_periods, t, h, v, paid, ruin, alive,
+                                                until);
         });
     if (active) {
       if (k.d_final) k.d_final[i] = v;
@@ -2630,6 +2643,100 @@ void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x
   if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
   if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
+// ---- allocation sweeps: up to eight portfolio strategies on one set of draws ------------------------
+//
+// smmc_engine_simulate_allocation_sweep (csrc/smmc_allocation_sweep.cpp; include/smmc.h and DESIGN.md, "Allocation
+// sweeps", state the contract): scenario sc of a sweep is portfolio_cashflow_kernel<..., kVarying = false> with
+// (weights, rebalance_every, amount, fraction, floor)[sc] on the law of x.p.  The joint draw of a period depends on (seed,
+// path id, period, law) alone, so ONE portfolio_multipliers per Philox block serves all scenarios; per draw an unrolled
+// loop makes the kS portfolio_cashflow_steps, each on its own h[K], v, paid, ruin, `alive` (a lane mask in a scalar
+// register pair) and its own scalar rebalance countdown -- the scenarios may differ in R, every countdown is
+// wave-uniform, and so is all control flow.  The (K + 4) kS parameters are kernel arguments; the loop loads nothing
+// beyond the draw's gathers.  By source a scenario and period cost the parent's step: K compounding chains and 4 K + 8.
+//
+// kS is 4 or 8: the host pads a request to the next of them with copies of its last scenario, and x.n says how many are
+// real -- a padded scenario is stepped and nothing of it is ever stored, counted or recorded, as in
+// cashflow_sweep_kernel.  Records, LDS and epilogue are that kernel's too: wave_record_add into per-wave, per-scenario
+// partials, [asset table or v3 draw tables][x.n][n_periods + 1] depletion][x.n][n_bins] buckets][pad][kS][kW] partials],
+// thread sc folds scenario sc's partials into k.partials[sc][workgroup], flush_counters takes both counter arrays.
+template <int kMode, bool kExactDiv, bool kDense, int K, int kS>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void allocation_sweep_kernel(const KernelArgs k, const AllocationSweepArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  static_assert(kS == 4 || kS == 8, "two widths");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const uint32_t n_at = k.n_periods + 1u;
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), x.n * (n_at + k.n_bins));  // wave_part: [kS][kW]
+  uint32_t *lds_dep = s.counters;             // [x.n][n_periods + 1]
+  uint32_t *lds_hist = lds_dep + x.n * n_at;  // [x.n][n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = x.d_depleted != nullptr;
+  const uint32_t lane = s.lane;
+  BlockPartial *part = s.wave_part + s.wave;  // scenario sc: part[sc * kW], this wave's own until the barrier
+  if (lane == 0) {
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) partial_identity(part[sc * kW]);
+  }
+  const DrawRegs dr = make_draw_regs(k);
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[kS][K], v[kS], paid[kS];
+    uint32_t ruin[kS], until[kS];
+    bool alive[kS];
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) {
+#pragma unroll
+      for (int y = 0; y < K; ++y) h[sc][y] = __fmul_rn(k.initial_capital, x.weights[sc][y]);
+      v[sc] = 0.0f;  // set by the first period (n_periods >= 1)
+      paid[sc] = 0.0f;
+      ruin[sc] = 0u;
+      alive[sc] = true;
+      until[sc] = x.rebalance_every[sc];
+    }
+    float a[kDraws][K];
+    walk_blocks<kDraws>(
+        k.n_periods, [&](uint32_t blk) { portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a); },
+        [&](int j, uint32_t t) {
+#pragma unroll
+          for (int sc = 0; sc < kS; ++sc)
+            portfolio_cashflow_step<kExactDiv, K>(a[j], x.weights[sc], x.amount[sc], x.fraction[sc], x.floor[sc], x.rebalance_every[sc],
+                                                  k.n_periods, t, h[sc], v[sc], paid[sc], ruin[sc], alive[sc], until[sc]);
+        });
+#pragma unroll
+    for (int sc = 0; sc < kS; ++sc) {
+      if (static_cast<uint32_t>(sc) >= x.n) continue;  // uniform: a padded scenario leaves nothing
+      const size_t at = static_cast<size_t>(sc) * k.n_paths + i;
+      if (active) {
+        if (k.d_final) k.d_final[at] = v[sc];
+        if (p.d_holdings) {
+#pragma unroll
+          for (int y = 0; y < K; ++y) p.d_holdings[(static_cast<size_t>(sc) * K + y) * k.n_paths + i] = h[sc][y];
+        }
+        if (x.d_paid) x.d_paid[at] = paid[sc];
+        if (x.d_ruin_period) x.d_ruin_period[at] = ruin[sc];
+        if (want_dep) atomicAdd(&lds_dep[sc * n_at + ruin[sc]], 1u);  // ruin <= n_periods
+      }
+      if (want_stats)  // uniform: the whole wave
+        wave_record_add(part + sc * kW, v[sc], active, lane, k.below_threshold, k.hist_lo, k.hist_hi, k.hist_inv,
+                        want_hist ? k.n_bins : 0u, lds_hist + sc * k.n_bins);
+    }
+  });
+
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x < x.n)
+    fold_wave_partials<kW>(s.wave_part + threadIdx.x * kW, &k.partials[static_cast<size_t>(threadIdx.x) * gridDim.x + blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, x.n * n_at, x.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, x.n * k.n_bins, k.d_hist);
 }
 
 }  // namespace
@@ -2711,6 +2818,17 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_KERNELS
+#define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                                 \
+  reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, false, false, K, S>),                           \
+      reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, true, false, K, S>),                        \
+      reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, false, true, K, S>),                           \
+      reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, true, true, K, S>),                            \
+      reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, false, false, K, S>),                          \
+      reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, true, false, K, S>)
+      SMMC_ALLOCATION_SWEEP_KERNELS(1, 4), SMMC_ALLOCATION_SWEEP_KERNELS(2, 4), SMMC_ALLOCATION_SWEEP_KERNELS(3, 4),
+      SMMC_ALLOCATION_SWEEP_KERNELS(4, 4), SMMC_ALLOCATION_SWEEP_KERNELS(1, 8), SMMC_ALLOCATION_SWEEP_KERNELS(2, 8),
+      SMMC_ALLOCATION_SWEEP_KERNELS(3, 8), SMMC_ALLOCATION_SWEEP_KERNELS(4, 8),
+#undef SMMC_ALLOCATION_SWEEP_KERNELS
   };
   for (const void *kernel : kernels) {
     hipFuncAttributes attr;
@@ -3127,6 +3245,44 @@ hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflo
   if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
   return launch_wave_walk<PortfolioCashflowFamily>(
       a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
+}
+
+// ---- allocation sweeps ----
+
+size_t allocation_sweep_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins,
+                                  uint32_t n_scenarios) {
+  // the padded rows in the table's place; counters: per scenario depletion [n_periods + 1] and histogram [n_bins];
+  // allocation_sweep_width(n_scenarios) partials per wave
+  return wave_walk_lds_bytes(mode, n_rows * portfolio_row_words(n_assets),
+                             static_cast<size_t>(n_scenarios) * (static_cast<size_t>(n_periods) + 1u + n_bins),
+                             allocation_sweep_width(n_scenarios));
+}
+
+struct AllocationSweepFamily {
+  template <int kMode, bool kExactDiv, bool kDense, int K>
+  static WalkKernel<AllocationSweepArgs> width(const AllocationSweepArgs &x) {
+    return allocation_sweep_width(x.n) == 4u ? allocation_sweep_kernel<kMode, kExactDiv, kDense, K, 4>
+                                             : allocation_sweep_kernel<kMode, kExactDiv, kDense, K, 8>;
+  }
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<AllocationSweepArgs> get(const AllocationSweepArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return width<kMode, kExactDiv, kDense, 1>(x);
+      case 2: return width<kMode, kExactDiv, kDense, 2>(x);
+      case 3: return width<kMode, kExactDiv, kDense, 3>(x);
+      default: return width<kMode, kExactDiv, kDense, 4>(x);
+    }
+  }
+};
+// The entries of x from x.n up to allocation_sweep_width(x.n) must be copies of entry x.n - 1.
+hipError_t launch_allocation_sweep(const KernelArgs &a, const AllocationSweepArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.n < 1 || x.n > SMMC_MAX_SWEEP) return hipErrorInvalidValue;
+  if (static_cast<uint64_t>(x.n) * (static_cast<uint64_t>(a.n_periods) + 1u + a.n_bins) > SMMC_MAX_SWEEP_COUNTERS) return hipErrorInvalidValue;
+  return launch_wave_walk<AllocationSweepFamily>(
+      a, x, exact_div, grid, allocation_sweep_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins, x.n), stream);
 }
 
 }  // namespace smmc

@@ -187,6 +187,20 @@ class SweepResult:
         return best
 
 
+@dataclasses.dataclass
+class AllocationSweepResult(SweepResult):
+    """What Engine.simulate_allocation_sweep returns: SweepResult's outputs (survival() and depleted_share() included) of
+    S portfolio strategies on the same jointly drawn paths, and the final holdings."""
+    weights: np.ndarray = None          # float32 [S, K]: the strategies as they were run
+    rebalance_every: np.ndarray = None  # uint32 [S]
+    n_assets: int = 0
+    holdings: object = None             # torch.float32 [S, K, n_paths]: the final holdings (no rebalance at P)
+
+    def surviving(self, confidence):
+        """The indices of the scenarios whose share of paths alive after the last period is at least `confidence` (0 .. 1)."""
+        return [int(s) for s in np.flatnonzero(self.survival()[:, -1] >= float(confidence))]
+
+
 def _by_period(counts, what):
     """Cumulative share of paths whose first passage lies at or before each period, from a [n_periods + 1] count
     array ([0]: never, [t]: first at period t)."""
@@ -1008,6 +1022,113 @@ class Engine:
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rc = self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
         del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- allocation sweeps: up to MAX_SWEEP portfolio strategies on one set of draws (smmc_engine_simulate_allocation_sweep) --
+    @staticmethod
+    def make_allocation_sweep(weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None, factor=None):
+        """(array of smmc_portfolio, array of smmc_cashflow, weights float32 [S, K], rebalance_every uint32 [S], amounts,
+        fractions, floors float32 [S]): `weights` is a list of S weight vectors of one length K; a scalar rebalance_every,
+        amount, fraction or floor broadcasts over the scenarios, a list gives one value per scenario; means and factor
+        (Gaussian mode) are the one joint law all scenarios share."""
+        w = np.asarray(weights, dtype=np.float32)
+        if w.ndim != 2 or not 1 <= w.shape[1] <= _lib.MAX_ASSETS:
+            raise ValueError(f"weights must be a list of weight vectors of one length, 1 .. {_lib.MAX_ASSETS} assets")
+        S = int(w.shape[0])
+        try:
+            every, am, fr, fl = (np.broadcast_to(np.asarray(x, dtype=t), (S,)).copy() for x, t in
+                                 ((rebalance_every, np.uint32), (amounts, np.float32), (fractions, np.float32), (floors, np.float32)))
+        except ValueError:
+            raise ValueError("rebalance_every, amounts, fractions and floors must be scalars or hold one value per scenario") from None
+        pfs, cfs = (_lib.Portfolio * max(S, 1))(), (_lib.Cashflow * max(S, 1))()
+        for s in range(S):
+            pfs[s] = Engine.make_portfolio(w[s], int(every[s]), means, factor)
+            cfs[s].struct_size = C.sizeof(_lib.Cashflow)
+            cfs[s].amount, cfs[s].fraction, cfs[s].floor = float(am[s]), float(fr[s]), float(fl[s])
+        return pfs, cfs, w.copy(), every, am, fr, fl
+
+    def simulate_allocation_sweep(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None,
+                                  factor=None, want_final=False, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                  want_stats=False, want_depleted_at=True):
+        """Up to MAX_SWEEP portfolio strategies on the SAME jointly drawn paths in one launch: scenario s holds weights[s],
+        rebalances every rebalance_every[s] periods, takes amounts[s] + fractions[s] * value out after every period and is
+        depleted at floors[s], exactly as simulate_portfolio_cashflow with those five.  Returns an AllocationSweepResult;
+        per-path outputs stay on the device, stats and depleted_at are read back (that waits).  include/smmc.h states the
+        contract."""
+        raw = self.simulate_allocation_sweep_raw(sim, weights, rebalance_every, amounts, fractions, floors, means, factor,
+                                                 want_final, want_holdings, want_paid, want_ruin_period, want_stats,
+                                                 want_depleted_at)
+        _, _, w, every, am, fr, fl = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
+        res = AllocationSweepResult(int(sim.n_paths), int(sim.n_periods), am, fr, fl, raw["final"], raw["paid"], raw["ruin_period"],
+                                    weights=w, rebalance_every=every, n_assets=raw["n_assets"], holdings=raw["holdings"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            host, rec = raw["stats_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
+            res.stats = []
+            for s in range(am.size):
+                st = stats_from_bytes(host[s * rec:(s + 1) * rec])
+                st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+                res.stats.append(st)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_allocation_sweep_raw(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None,
+                                      factor=None, want_final=False, want_holdings=False, want_paid=False,
+                                      want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Enqueues the sweep and returns its device tensors without waiting: a dict with final, paid (float32
+        [S, n_paths]), holdings (float32 [S, K, n_paths]), ruin_period (int32 holding uint32 values), stats_raw (uint8
+        [S, smmc_stats_bytes(n_bins)]) and depleted_at (int64 holding uint64 counts, [S, n_periods + 1]); None for what
+        was not asked for."""
+        torch = self._torch
+        pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
+        n, p, (S, K) = int(sim.n_paths), int(sim.n_periods), w.shape
+        new = lambda want, shape, dtype: torch.empty((S,) + shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, (n,), torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
+               "paid": new(want_paid, (n,), torch.float32), "ruin_period": new(want_ruin_period, (n,), torch.int32),
+               "stats_raw": new(want_stats, (int(self._L.smmc_stats_bytes(sim.n_bins)),), torch.uint8),
+               "depleted_at": new(want_depleted_at, (p + 1,), torch.int64)}
+        o = _lib.AllocationSweepOutputs()
+        o.struct_size = C.sizeof(_lib.AllocationSweepOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_allocation_sweep(self._h, C.byref(sim), pfs, cfs, S, C.byref(o)))
+        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        return res
+
+    def simulate_allocation_sweep_to_host(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0,
+                                          means=None, factor=None, want_final=False, want_holdings=False, want_paid=False,
+                                          want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_allocation_sweep_to_host: a dict of numpy arrays, scenario-major
+        (stats_raw: the S packed records as bytes)."""
+        pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
+        n, p, (S, K) = int(sim.n_paths), int(sim.n_periods), w.shape
+        new = lambda want, shape, dtype: np.zeros((S,) + shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, (n,), np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, (n,), np.float32), "ruin_period": new(want_ruin_period, (n,), np.uint32),
+               "stats_raw": new(want_stats, (int(self._L.smmc_stats_bytes(sim.n_bins)) // 8,), np.uint64),
+               "depleted_at": new(want_depleted_at, (p + 1,), np.uint64)}
+        o = _lib.AllocationSweepOutputs()
+        o.struct_size = C.sizeof(_lib.AllocationSweepOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_allocation_sweep_to_host(self._h, C.byref(sim), pfs, cfs, S, C.byref(o)))
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def allocation_sweep_divide_kind(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None,
+                                     factor=None):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_allocation_sweep uses for this request: FAST only if every
+        scenario's own rule says so (results never depend on it)."""
+        pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
+        rc = self._L.smmc_engine_allocation_sweep_divide_kind(self._h, C.byref(sim), pfs, cfs, int(w.shape[0]))
         if rc < 0:
             _lib.check(rc)
         return rc
