@@ -642,6 +642,87 @@ int smmc_engine_simulate_allocation_sweep_to_host(smmc_engine *e, const smmc_sim
 int smmc_engine_allocation_sweep_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs,
                                              const smmc_cashflow *cfs, uint32_t n_scenarios);
 
+/* ---- real cash flows: the schedule in money of period 0, inflation drawn jointly with the assets ---- */
+
+/* "4 % of the starting capital, raised with prices every year": smmc_engine_simulate_portfolio_cashflow with the
+ * schedule's amounts and floor stated in money of period 0 and a price index that differs per path, because inflation
+ * is one more series of the joint law: the same resampled month as the returns (table mode), correlated normals
+ * (Gaussian mode).  Counter stream v3 only.
+ *
+ * pf is an smmc_portfolio with n_assets = K INVESTED assets, 1 <= K <= SMMC_MAX_ASSETS - 1.  The joint law has K + 1
+ * series and series K is inflation in percent per period:
+ *   - table mode: the engine's asset table (smmc_engine_set_asset_table) must have exactly K + 1 columns; the row of
+ *     period t is the portfolio contract's row i_t;
+ *   - Gaussian mode: means[K] and row K of factor describe inflation and may be non-zero; series K takes the Philox
+ *     blocks with fourth word 1 + 2 K and the same chain of fused multiply-adds as any asset;
+ *   - weights[K] must be 0, and every entry beyond K + 1 must be 0: the checks of smmc_engine_simulate_portfolio apply
+ *     with the law's width K + 1.
+ * cf is an smmc_cashflow with unchanged meaning and checks, except that amount / amounts[] and floor are in money of
+ * period 0.  Fractions are fractions of the nominal value, as before.
+ *
+ * Per path, every operation ONE binary32 rounding, nothing fused, every comparison false for NaN; a_k(t), k = 0 .. K,
+ * are the joint multipliers of the portfolio contract at width K + 1:
+ *   start        h_k = fl(capital * w_k) (k < K);  I = 1.0f;  paid = 0;  ruin = 0;  alive
+ *   t = 1 .. P   h_k = fl(fl(h_k * a_k(t)) / 100.0f)               k < K, as the portfolio step
+ *                I   = fl(fl(I * a_K(t)) / 100.0f)                 the price index; on every path, depleted or not
+ *                g   = (h_0 + h_1) + h_2                           left to right over K
+ *                w   = fl(fl(amount[t-1] * I) + fl(g * fraction[t-1]))
+ *                vn  = fl(g - w)
+ *     live, vn > fl(floor * I):   exactly the live branch of smmc_engine_simulate_portfolio_cashflow (paid += w,
+ *                                 rebalance or settle at the weights)
+ *     live, otherwise:            exactly its depletion branch (h_k = 0, v = 0, paid += fmaxf(g, 0), ruin = t)
+ *     depleted:                   nothing but I changes
+ *   final = v;  index = I after period P;  final_real = v / I  (ONE IEEE-correct binary32 division per path, after the
+ *   loop, whatever the form of the divide by 100)
+ * paid is NOMINAL money.  A path depends only on (seed, global path id, law, weights, R, schedule, floor).
+ *
+ * Identities:
+ *   1. Inflation identically 0 % -- a column of zeros; means[K] = 0 with row K of factor zero -- gives I == 1 throughout:
+ *      final, holdings, paid, ruin_period, depleted_at and the record are those of
+ *      smmc_engine_simulate_portfolio_cashflow on the first K series, bit for bit, and final_real == final.
+ *   2. amount = 0, no amounts[] and floor = 0: the nominal outputs are the parent's on the first K series bit for bit,
+ *      whatever the inflation series is (table mode: the row depends on n_rows only; Gaussian mode: asset j's normals
+ *      depend on j only) -- while the index stays finite: 0 * inf is NaN.
+ *   3. A constant inflation column c in table mode gives one deterministic sequence I_t; with floor = 0 the nominal
+ *      outputs are the parent's with amounts[t-1] = fl(amount * I_t), bit for bit. */
+typedef struct smmc_real_cashflow_outputs {
+  uint32_t struct_size, reserved; /* = sizeof(smmc_real_cashflow_outputs), 0 */
+  float *d_final;          /* n_paths nominal final values, 0 for a depleted path */
+  float *d_final_real;     /* n_paths final values in money of period 0: final / index */
+  float *d_index;          /* n_paths price indices after period P */
+  float *d_holdings;       /* nominal final holdings, asset-major K x n_paths */
+  float *d_paid;           /* n_paths totals paid out, nominal */
+  uint32_t *d_ruin_period; /* n_paths periods of depletion, 0 = never */
+  void *d_stats;           /* packed record of the REAL final values, smmc_stats_bytes(n_bins) */
+  uint64_t *d_depleted_at; /* n_periods + 1 counts: [0] never depleted, [t] depleted at period t; their sum is n_paths */
+} smmc_real_cashflow_outputs;
+
+/* Enqueues one such simulation on the engine stream and returns without waiting; the host arrays of cf may be reused on
+ * return.  out holds DEVICE pointers (4-byte aligned, d_stats and d_depleted_at 8-byte), any may be NULL; they are
+ * written, not accumulated into.  Exactness of the record's fields, determinism (two identical calls give the same
+ * bytes), shard merging (smmc_stats_merge, adding d_depleted_at) and n_paths == 0 (no launch, the empty record, zero
+ * counts) are as in smmc_engine_simulate_portfolio_cashflow.
+ * SMMC_ERR_INVALID with a text, and no launch: everything smmc_engine_simulate_portfolio_cashflow refuses, checked with
+ * the law's width K + 1; n_assets == SMMC_MAX_ASSETS; weights[K] != 0; an asset table whose column count is not K + 1;
+ * a NULL or wrongly sized out, or reserved != 0. */
+int smmc_engine_simulate_real_cashflow(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf,
+                                       const smmc_real_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_real_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                               const smmc_cashflow *cf, const smmc_real_cashflow_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT (never SMMC_DIV_CHECKED), or an error of the call's argument checks.  Results never
+ * depend on the form.  The nominal amount varies with the index, so the parent's proof for "one constant amount" does
+ * not carry over; the reciprocal-multiply form is used only when BOTH hold, with the multiplier bounds of
+ * smmc_engine_portfolio_divide_kind for every series (lo_I, hi_I: those of series K, divided by 100):
+ *   the index stays in the window   lo_I^P >= 2^-88 and hi_I^P < 2^126: every product I * a_K is inside [2^-89, 2^127);
+ *   contributions only              every amount <= 0 and every fraction 0, a positive capital, every positively
+ *                                   weighted asset starting above 0, and (capital + the sum of |amount| *
+ *                                   max(1, hi_I)^P) grown by the best asset in every period below 2^126: holdings only
+ *                                   gain, and the portfolio rule's lower bound stands.
+ * Everything else, or SMMC_FLAG_EXACT_DIV, is the IEEE divide ("Real cash flows", has the proof). */
+int smmc_engine_real_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                          const smmc_cashflow *cf);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

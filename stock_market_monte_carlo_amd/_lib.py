@@ -145,6 +145,22 @@ class PortfolioCashflowOutputs(C.Structure):
     ]
 
 
+class RealCashflowOutputs(C.Structure):
+    """smmc_real_cashflow_outputs"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("final", C.c_void_p),
+        ("final_real", C.c_void_p),
+        ("index", C.c_void_p),
+        ("holdings", C.c_void_p),
+        ("paid", C.c_void_p),
+        ("ruin_period", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("depleted_at", C.c_void_p),
+    ]
+
+
 class AllocationSweepOutputs(C.Structure):
     """smmc_allocation_sweep_outputs"""
     _fields_ = PortfolioCashflowOutputs._fields_  # the same pointers, scenario-major
@@ -226,6 +242,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_uint32, C.POINTER(AllocationSweepOutputs)]),
     ("smmc_engine_allocation_sweep_divide_kind", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_uint32]),
+    ("smmc_engine_simulate_real_cashflow", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(RealCashflowOutputs)]),
+    ("smmc_engine_simulate_real_cashflow_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(RealCashflowOutputs)]),
+    ("smmc_engine_real_cashflow_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

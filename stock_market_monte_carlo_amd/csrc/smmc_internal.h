@@ -241,6 +241,19 @@ struct PortfolioCashflowArgs {
 hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
                                      hipStream_t stream);
 size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// real_cashflow_kernel (smmc_engine_simulate_real_cashflow, csrc/smmc_real_cashflow.cpp; counter stream v3 only):
+// portfolio_cashflow_kernel's step with the schedule's amounts and floor in money of period 0, indexed by a price index
+// that the LAST series of the joint law compounds ("Real cash flows").  p is the law as launch_portfolio
+// takes it, p.n_assets = K + 1 series wide (table rows included): K invested assets, then inflation in percent per
+// period; p.weights[K] is 0 and p.d_holdings is K x n_paths.  c, a.partials, a.d_hist and c.d_depleted as
+// launch_portfolio_cashflow; the record is of the REAL final values.  LDS: portfolio_cashflow_lds_bytes at width K + 1.
+struct RealCashflowArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  float *d_final_real;  // nullable: n_paths final values divided by the final index
+  float *d_index;       // nullable: n_paths price indices after the last period
+};
+hipError_t launch_real_cashflow(const KernelArgs &a, const RealCashflowArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
 // allocation_sweep_kernel (smmc_engine_simulate_allocation_sweep, csrc/smmc_allocation_sweep.cpp; counter stream v3
 // only): n constant-schedule strategies (weights, rebalance_every, amount, fraction, floor) stepped on ONE joint draw
 // per period ("Allocation sweeps").  p: the law as launch_portfolio takes it (n_assets, shift100, factor;

@@ -2645,6 +2645,130 @@ void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- real cash flows: the schedule in money of period 0, indexed by a jointly drawn inflation series ----
+//
+// smmc_engine_simulate_real_cashflow (csrc/smmc_real_cashflow.cpp; include/smmc.h and DESIGN.md, "Real cash flows",
+// state the contract): portfolio_cashflow_kernel's K holdings and step on a joint law of K + 1 series.  Series K is
+// inflation in percent per period: it compounds a price index I from 1.0f as a holding compounds, on every lane,
+// depleted or not, and the period's nominal amount and floor are fl(amount * I) and fl(floor * I) with the index AFTER
+// that period's inflation:
+//   h_k = (h_k * a_k) / 100 for k < K;  I = (I * a_K) / 100;  g = (h_0 + h_1) + h_2
+//   w = amount * I + g * fraction,  vn = g - w,  live while vn > floor * I;  the two branches are the parent's
+// The draw is portfolio_multipliers<kMode, kDense, K + 1>: table rows are K + 1 wide in LDS (one ds_read_b64 / b128 per
+// period), a Gaussian period takes K + 1 Philox chains.  The step is a sibling of portfolio_cashflow_step, not a
+// parameter of it: the parent's and the sweep's instruction sequences stay what they are.  After the loop
+// final_real = v / I is ONE IEEE division (__fdiv_rn, whatever kExactDiv says) and feeds the record.  By source, on top
+// of the parent's step of the same K: the index chain (multiply and the divide), one multiply for the amount and one
+// for the floor.  LDS layout, schedule loads and epilogue are the parent's.
+template <bool kExactDiv, int K>
+__device__ __forceinline__ void real_cashflow_step(const float (&a)[K + 1], const float (&weights)[SMMC_MAX_ASSETS], float amount,
+                                                   float fraction, float floor, uint32_t every, uint32_t n_periods, uint32_t t,
+                                                   float (&h)[K], float &index, float &v, float &paid, uint32_t &ruin, bool &alive,
+                                                   uint32_t &until) {
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = compound<kExactDiv>(h[y], a[y]);
+  index = compound<kExactDiv>(index, a[K]);
+  const float g = portfolio_value<K>(h);
+  const float w = __fadd_rn(__fmul_rn(amount, index), __fmul_rn(g, fraction));
+  const float vn = __fsub_rn(g, w);
+  const bool goes_on = alive && vn > __fmul_rn(floor, index);  // false for NaN
+  const bool dies = alive && !goes_on;
+  float hn[K];
+  bool rebalance = false;
+  if (--until == 0u) {  // uniform: t mod every == 0
+    until = every;
+    rebalance = t != n_periods;  // the final holdings are formed before any rebalance at P
+  }
+  if (rebalance) {
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fmul_rn(vn, weights[y]);
+  } else {  // the flow settles at the target weights
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fsub_rn(h[y], __fmul_rn(w, weights[y]));
+  }
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = goes_on ? hn[y] : 0.0f;
+  v = goes_on ? vn : 0.0f;
+  // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0), and paid + 0 is paid (paid is never -0)
+  paid = __fadd_rn(paid, goes_on ? w : fmaxf(g, 0.0f));
+  ruin = dies ? t : ruin;
+  alive = goes_on;
+}
+
+template <int kMode, bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void real_cashflow_kernel(const KernelArgs k, const RealCashflowArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  static_assert(K >= 1 && K + 1 <= SMMC_MAX_ASSETS, "K invested assets and the inflation series");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;  // the law of K + 1 series; weights[K] is 0 and never read
+  const CashflowArgs &c = x.c;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K + 1);
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float index = 1.0f;
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    float a[kDraws][K + 1];
+    float am[kDraws], fr[kDraws];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) {
+#pragma unroll
+          for (int j = 0; j < kDraws; ++j) {  // the block's schedule entries (padded to whole blocks)
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+          portfolio_multipliers<kMode, kDense, K + 1>(k, p, dr, s.table, path_lo, path_hi, blk, a);
+        },
+        [&](int j, uint32_t t) {
+          real_cashflow_step<kExactDiv, K>(a[j], p.weights, am[j], fr[j], c.floor, every, k.n_periods, t, h, index, v, paid, ruin,
+                                           alive, until);
+        });
+    const float v_real = __fdiv_rn(v, index);
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (x.d_final_real) x.d_final_real[i] = v_real;
+      if (x.d_index) x.d_index[i] = index;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v_real, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 // ---- allocation sweeps: up to eight portfolio strategies on one set of draws ------------------------
 //
 // smmc_engine_simulate_allocation_sweep (csrc/smmc_allocation_sweep.cpp; include/smmc.h and DESIGN.md, "Allocation
@@ -2818,6 +2942,16 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_KERNELS
+#define SMMC_REAL_CASHFLOW_KERNELS(K, V)                                                                                     \
+  reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),                              \
+      reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),                           \
+      reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_TABLE, false, true, K, V>),                              \
+      reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_TABLE, true, true, K, V>),                               \
+      reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_TABLE, false, false, K, V>),                             \
+      reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_TABLE, true, false, K, V>)
+      SMMC_REAL_CASHFLOW_KERNELS(1, false), SMMC_REAL_CASHFLOW_KERNELS(2, false), SMMC_REAL_CASHFLOW_KERNELS(3, false),
+      SMMC_REAL_CASHFLOW_KERNELS(1, true), SMMC_REAL_CASHFLOW_KERNELS(2, true), SMMC_REAL_CASHFLOW_KERNELS(3, true),
+#undef SMMC_REAL_CASHFLOW_KERNELS
 #define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                                 \
   reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, false, false, K, S>),                           \
       reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, true, false, K, S>),                        \
@@ -3244,6 +3378,32 @@ hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflo
   if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
   if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
   return launch_wave_walk<PortfolioCashflowFamily>(
+      a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
+}
+
+// ---- real cash flows ----
+
+struct RealCashflowFamily {
+  template <int kMode, bool kExactDiv, bool kDense, int K>
+  static WalkKernel<RealCashflowArgs> schedule(const RealCashflowArgs &x) {
+    return x.c.schedule ? real_cashflow_kernel<kMode, kExactDiv, kDense, K, true> : real_cashflow_kernel<kMode, kExactDiv, kDense, K, false>;
+  }
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<RealCashflowArgs> get(const RealCashflowArgs &x) {
+    switch (x.p.n_assets) {  // the law's width: K invested assets and the inflation series
+      case 2: return schedule<kMode, kExactDiv, kDense, 1>(x);
+      case 3: return schedule<kMode, kExactDiv, kDense, 2>(x);
+      default: return schedule<kMode, kExactDiv, kDense, 3>(x);
+    }
+  }
+};
+hipError_t launch_real_cashflow(const KernelArgs &a, const RealCashflowArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 2 || x.p.n_assets > SMMC_MAX_ASSETS || x.p.weights[x.p.n_assets - 1] != 0.0f) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
+  // LDS: the parent's layout with rows of the law's width
+  return launch_wave_walk<RealCashflowFamily>(
       a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
 }
 

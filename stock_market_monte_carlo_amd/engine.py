@@ -260,6 +260,14 @@ class PortfolioCashflowResult(CashflowResult):
     holdings: object = None  # torch.float32 [n_assets, n_paths]: the final holdings (no rebalance at P), 0 for a depleted path
 
 
+@dataclasses.dataclass
+class RealCashflowResult(PortfolioCashflowResult):
+    """What Engine.simulate_real_cashflow returns: PortfolioCashflowResult's nominal outputs (survival() included), the
+    final values in money of period 0 and the price index they were divided by; stats is the record of final_real."""
+    final_real: object = None  # torch.float32 [n_paths]: final / index
+    index: object = None       # torch.float32 [n_paths]: the price index after the last period (1.0 at the start)
+
+
 def cholesky_factor(stds, corr):
     """The lower-triangular factor L (float32 [K, K], percent) of diag(stds) corr diag(stds), for
     Engine.simulate_portfolio(factor=...): numpy's float64 Cholesky, cast once.  Raises ValueError for a matrix that
@@ -1021,6 +1029,119 @@ class Engine:
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rc = self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
+        del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- real cash flows: the schedule in money of period 0, inflation drawn jointly (smmc_engine_simulate_real_cashflow) --
+    _REAL_OUTPUTS = (("final", "final"), ("final_real", "final_real"), ("index", "index"), ("holdings", "holdings"), ("paid", "paid"),
+                     ("ruin_period", "ruin_period"), ("stats", "stats_raw"), ("depleted_at", "depleted_at"))
+
+    @staticmethod
+    def make_real_portfolio(weights, rebalance_every=0, means=None, factor=None):
+        """smmc_portfolio of K = len(weights) invested assets for the real cash-flow calls; means [K + 1] and factor
+        [K + 1, K + 1] (lower triangular) describe the joint law in Gaussian mode, the last series being inflation."""
+        w = np.asarray(weights, dtype=np.float32).ravel()
+        K = int(w.size)
+        if not 1 <= K <= _lib.MAX_ASSETS - 1:
+            raise ValueError(f"1 .. {_lib.MAX_ASSETS - 1} invested assets: the law's last series is inflation")
+        pf = Engine.make_portfolio(np.append(w, np.float32(0.0)), rebalance_every, means, factor)  # checks the law at K + 1
+        pf.n_assets = K
+        return pf
+
+    def make_real_cashflow_outputs(self, sim, n_assets, want_final=True, want_final_real=True, want_index=False,
+                                   want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                                   want_depleted_at=True):
+        """(smmc_real_cashflow_outputs, dict of the device tensors it points to) for a request of sim's size with
+        n_assets invested assets; None for what was not asked for."""
+        torch = self._torch
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(n_assets)
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "final_real": new(want_final_real, n, torch.float32),
+               "index": new(want_index, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
+               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        o = _lib.RealCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.RealCashflowOutputs)
+        for name, key in self._REAL_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        return o, res
+
+    def simulate_real_cashflow(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                               fractions=None, means=None, factor=None, want_final=True, want_final_real=True, want_index=False,
+                               want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                               want_depleted_at=True):
+        """simulate_portfolio_cashflow with `amount` / `amounts` and `floor` in money of period 0: K = len(weights)
+        invested assets and one more series of the joint law, inflation in percent per period -- the last column of
+        set_asset_table's table, or the last entry of means [K + 1] and last row of factor [K + 1, K + 1] -- compound
+        a price index per path that scales the period's amount and floor.  Returns a RealCashflowResult; per-path
+        outputs stay on the device, stats (of final_real) and depleted_at are read back (that waits).  include/smmc.h
+        states the arithmetic."""
+        raw = self.simulate_real_cashflow_raw(sim, weights, rebalance_every, amount, fraction, floor, amounts, fractions, means,
+                                              factor, want_final, want_final_real, want_index, want_holdings, want_paid,
+                                              want_ruin_period, want_stats, want_depleted_at)
+        res = RealCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                 n_assets=raw["n_assets"], holdings=raw["holdings"], final_real=raw["final_real"], index=raw["index"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_real_cashflow_raw(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                                   fractions=None, means=None, factor=None, want_final=True, want_final_real=True,
+                                   want_index=False, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                   want_stats=False, want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, final_real, index,
+        holdings, paid (float32), ruin_period (int32 holding uint32 values), stats_raw (uint8, the packed record of
+        final_real) and depleted_at (int64 holding uint64 counts, n_periods + 1); None for what was not asked for."""
+        pf = self.make_real_portfolio(weights, rebalance_every, means, factor)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        o, res = self.make_real_cashflow_outputs(sim, pf.n_assets, want_final, want_final_real, want_index, want_holdings,
+                                                 want_paid, want_ruin_period, want_stats, want_depleted_at)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_real_cashflow(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        self._leave(cur, *[res[key] for _, key in self._REAL_OUTPUTS])
+        del keep
+        return res
+
+    def simulate_real_cashflow_to_host(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                                       fractions=None, means=None, factor=None, want_final=True, want_final_real=True,
+                                       want_index=False, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                       want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_real_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_real_portfolio(weights, rebalance_every, means, factor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, np.float32), "final_real": new(want_final_real, n, np.float32),
+               "index": new(want_index, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        o = _lib.RealCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.RealCashflowOutputs)
+        for name, key in self._REAL_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_real_cashflow_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        del keep
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def real_cashflow_divide_kind(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                                  fractions=None, means=None, factor=None):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_real_cashflow uses for this request (results never depend on it)."""
+        pf = self.make_real_portfolio(weights, rebalance_every, means, factor)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        rc = self._L.smmc_engine_real_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
         del keep
         if rc < 0:
             _lib.check(rc)
