@@ -3,19 +3,19 @@
 // rebalancing, a constant cash flow and a floor each -- stepped on the same jointly drawn paths in one launch.
 //
 // A translation unit of its own, like smmc_sweep.cpp and smmc_portfolio_cashflow.cpp: no other unit calls into this
-// file.  A scenario's argument checks are lent by smmc_portfolio.cpp and smmc_cashflow.cpp (smmc_internal.h, "lend"),
+// file.  A scenario's argument checks are lent by smmc_portfolio.cpp and smmc_cashflow.cpp (smmc_host.h, "lend"),
 // its divide is smmc_engine_portfolio_cashflow_divide_kind's, asked scenario by scenario -- the rule and its proof stay
 // in smmc_portfolio_cashflow.cpp.  What is this unit's own: the checks across scenarios (one joint law, constant
-// schedules), the padding to the kernel's widths, the counter cap, the LDS need and the launch.  The launch is a wave
-// walk on the shared host side (host_wave_walk_grid, engine_acc_lease, host_timed_launch, host_outputs_to_host); the
-// scenarios travel as kernel arguments: nothing is staged, the unit keeps no state per engine.
+// schedules), the padding to the kernel's widths, the counter cap, the LDS need and the kernel arguments.  The launch is
+// a wave walk and its run the shared one (smmc_host.h, host_wave_walk_run, with the per-scenario fold); the scenarios
+// travel as kernel arguments: nothing is staged, the unit keeps no state per engine.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
@@ -25,10 +25,6 @@ using smmc::host_fail;
 // Workgroups per CU, as cashflow_sweep_kernel; a workgroup leaves one partial per scenario in the engine's max_grid
 // partials, so the grid is capped at max_grid / width as well.
 constexpr uint32_t kGroupsPerCU = 32;
-// The engine's accumulator: [scenario][bucket] from 0, [scenario][period] from kDepletedAt.
-constexpr size_t kDepletedAt = SMMC_MAX_SWEEP_COUNTERS;
-static_assert(2u * SMMC_MAX_SWEEP_COUNTERS <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
-              "the engine's accumulator holds a sweep's buckets and depletion counters");
 
 // The checks that need no output structure; *kind: SMMC_DIV_FAST iff every scenario's own rule says so.
 int check_scenarios(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs, const smmc_cashflow *cfs, uint32_t n_scenarios,
@@ -59,16 +55,6 @@ int check_scenarios(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *p
     if (one < 0) return one;
     if (one != SMMC_DIV_FAST) *kind = SMMC_DIV_EXACT;
   }
-  return SMMC_OK;
-}
-
-int check_outputs(const smmc_allocation_sweep_outputs *out) {
-  if (!out) return host_fail(SMMC_ERR_INVALID, "the smmc_allocation_sweep_outputs argument is NULL");
-  if (out->struct_size != sizeof(smmc_allocation_sweep_outputs))
-    return host_fail(SMMC_ERR_INVALID, "smmc_allocation_sweep_outputs.struct_size is %u, this library expects %zu", out->struct_size,
-                     sizeof(smmc_allocation_sweep_outputs));
-  if (out->reserved != 0)
-    return host_fail(SMMC_ERR_INVALID, "smmc_allocation_sweep_outputs.reserved is %u, it must be 0", out->reserved);
   return SMMC_OK;
 }
 
@@ -126,51 +112,25 @@ int smmc_engine_simulate_allocation_sweep(smmc_engine *e, const smmc_sim *sim, c
   int kind = SMMC_DIV_EXACT;
   int rc = check_scenarios(e, sim, pfs, cfs, n_scenarios, &kind);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_allocation_sweep_outputs");
   if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(out->d_final) | reinterpret_cast<uintptr_t>(out->d_holdings) | reinterpret_cast<uintptr_t>(out->d_paid) |
-       reinterpret_cast<uintptr_t>(out->d_ruin_period)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "d_final, d_holdings, d_paid and d_ruin_period must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->d_stats) | reinterpret_cast<uintptr_t>(out->d_depleted_at)) & 7u)
-    return host_fail(SMMC_ERR_INVALID, "d_stats and d_depleted_at must be 8-byte aligned");
+  rc = smmc::host_check_depletion_alignment(out);
+  if (rc) return rc;
   Plan pl;
   rc = plan(e, sim, pfs, cfs, n_scenarios, out->d_stats != nullptr, &pl);
   if (rc) return rc;
-  const smmc::EngineView view = smmc::engine_view(e);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
-  smmc::KernelArgs &a = pl.a;
   smmc::AllocationSweepArgs &x = pl.x;
-  a.d_final = out->d_final;
+  pl.a.d_final = out->d_final;
   x.p.d_holdings = out->d_holdings;
   x.d_paid = out->d_paid;
   x.d_ruin_period = out->d_ruin_period;
-  smmc::ZeroLease lease;
-  if ((out->d_stats && sim->n_bins) || out->d_depleted_at) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_lease(e, &lease);
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (out->d_stats) {
-    a.partials = view.d_partials;  // [scenario][grid]
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (out->d_depleted_at) x.d_depleted = acc + kDepletedAt;
-  if (pl.grid) {
-    const bool exact_div = kind != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_allocation_sweep",
-                                 [&] { return smmc::launch_allocation_sweep(a, x, exact_div, pl.grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (out->d_stats)
-    SMMC_HIP(smmc::launch_finalize_sweep(view.d_partials, pl.grid, n_scenarios, out->d_stats, sim->n_bins, sim->n_bins ? acc : nullptr,
-                                         view.stream));
-  if (out->d_depleted_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, n_scenarios * (sim->n_periods + 1u),
-                                            reinterpret_cast<unsigned long long *>(out->d_depleted_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const bool exact_div = kind != SMMC_DIV_FAST;
+  // pl.a.partials: [scenario][grid]
+  const smmc::WaveWalk walk = {"launch_allocation_sweep", pl.grid, sim->n_bins, {{out->d_stats, 0, 0, &pl.a.partials, &pl.a.d_hist}},
+                               {{out->d_depleted_at, smmc::kSweepDepletedAt, n_scenarios * (sim->n_periods + 1u), &x.d_depleted}}};
+  return smmc::host_wave_walk_run(e, walk, smmc::FoldScenarios{n_scenarios}, [&](hipStream_t stream) {
+    return smmc::launch_allocation_sweep(pl.a, x, exact_div, pl.grid, stream);
+  });
 }
 
 int smmc_engine_simulate_allocation_sweep_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pfs, const smmc_cashflow *cfs,
@@ -178,7 +138,7 @@ int smmc_engine_simulate_allocation_sweep_to_host(smmc_engine *e, const smmc_sim
   int kind = SMMC_DIV_EXACT;
   int rc = check_scenarios(e, sim, pfs, cfs, n_scenarios, &kind);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_allocation_sweep_outputs");
   if (rc) return rc;
   Plan pl;  // refuse before anything is allocated
   rc = plan(e, sim, pfs, cfs, n_scenarios, out->d_stats != nullptr, &pl);
@@ -186,22 +146,16 @@ int smmc_engine_simulate_allocation_sweep_to_host(smmc_engine *e, const smmc_sim
   const smmc::EngineView view = smmc::engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  typedef smmc_allocation_sweep_outputs O;
   const size_t per_path = sizeof(float) * sim->n_paths * n_scenarios;
-  const smmc::HostPiece pieces[6] = {{out->d_stats, static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) * n_scenarios},
-                                     {out->d_depleted_at, sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u) * n_scenarios},
-                                     {out->d_final, per_path},
-                                     {out->d_holdings, per_path * pfs[0].n_assets},
-                                     {out->d_paid, per_path},
-                                     {out->d_ruin_period, per_path}};
-  return smmc::host_outputs_to_host(e, "simulate_allocation_sweep_to_host", pieces, 6, [&](void *const *dev) {
-    smmc_allocation_sweep_outputs d = *out;
-    d.d_stats = dev[0];
-    d.d_depleted_at = static_cast<uint64_t *>(dev[1]);
-    d.d_final = static_cast<float *>(dev[2]);
-    d.d_holdings = static_cast<float *>(dev[3]);
-    d.d_paid = static_cast<float *>(dev[4]);
-    d.d_ruin_period = static_cast<uint32_t *>(dev[5]);
-    return smmc_engine_simulate_allocation_sweep(e, sim, pfs, cfs, n_scenarios, &d);
+  const smmc::OutputField fields[6] = {{offsetof(O, d_stats), static_cast<size_t>(smmc_stats_bytes(sim->n_bins)) * n_scenarios},
+                                       {offsetof(O, d_depleted_at), sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u) * n_scenarios},
+                                       {offsetof(O, d_final), per_path},
+                                       {offsetof(O, d_holdings), per_path * pfs[0].n_assets},
+                                       {offsetof(O, d_paid), per_path},
+                                       {offsetof(O, d_ruin_period), per_path}};
+  return smmc::host_outputs_struct_to_host(e, "simulate_allocation_sweep_to_host", *out, fields, [&](const O *d) {
+    return smmc_engine_simulate_allocation_sweep(e, sim, pfs, cfs, n_scenarios, d);
   });
 }
 

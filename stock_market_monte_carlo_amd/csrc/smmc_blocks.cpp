@@ -2,7 +2,7 @@
 // (include/smmc.h): table paths drawn in runs of consecutive months, the circular block bootstrap.
 //
 // A translation unit of its own, as smmc_cashflow.cpp and smmc_excursions.cpp: smmc_capi.cpp owns struct smmc_engine
-// and never calls into this file; what is needed of an engine comes through smmc_internal.h.  It keeps no state per
+// and never calls into this file; what is needed of an engine comes through smmc_host.h.  It keeps no state per
 // engine: the partials and the bucket accumulator are the engine's, used as smmc_engine_simulate uses them; the
 // stream refusal, the timed launch and the HIP check are the shared host_require_v3, host_timed_launch and SMMC_HIP.
 // The reference resamples single months (src/simulations.cpp:240-252); it has no block draw.

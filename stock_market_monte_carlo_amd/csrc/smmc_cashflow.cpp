@@ -2,11 +2,12 @@
 // contribution schedules with depletion statistics.
 //
 // A translation unit of its own: smmc_capi.cpp owns struct smmc_engine and never calls into this file; what is
-// needed of an engine comes through smmc_internal.h and smmc_host.h (engine_view, engine_acc_lease, ...), and what this file keeps
-// per engine -- the staged schedule -- hangs in this unit's extension slot of the engine (engine_ext), released by
-// smmc_engine_destroy.  The launch is a wave walk, and its host side is the shared one: host_require_v3,
-// host_wave_walk_grid, host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in
-// smmc_capi.cpp).  The reference has no counterpart: its README lists withdrawal strategies as open.
+// needed of an engine comes through smmc_host.h (engine_view, host_make_args, ...), and what this file keeps per engine
+// -- the staged schedule -- hangs in this unit's extension slot of the engine (engine_ext), released by
+// smmc_engine_destroy.  The launch is a wave walk, and its run is the shared one (smmc_host.h, host_wave_walk_run: device,
+// lease, wiring, launch, folds).  What is this unit's own: the schedule's checks and staging, the divide rule, the LDS
+// need, the kernel arguments, and which record and count array the launch leaves.  The reference has no counterpart: its
+// README lists withdrawal strategies as open.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -15,10 +16,10 @@
 #include <new>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
+using smmc::cashflow_varying;
 using smmc::DeviceGuard;
 using smmc::host_fail;
 
@@ -26,10 +27,6 @@ using smmc::host_fail;
 constexpr uint32_t kCashflowGroupsPerCU = 32;
 // schedule entries per array as staged: n_periods rounded up to whole Philox blocks (8 draws at the most)
 constexpr uint32_t kStrideMax = (SMMC_MAX_CASHFLOW_PERIODS + 7u) & ~7u;
-// The depletion counters take the engine's accumulator from copy 1 on (copy 0 holds the final-value histogram).
-constexpr size_t kDepletedAt = SMMC_MAX_BINS;
-static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
-              "the engine's accumulator holds the histogram and the depletion counters");
 
 // The staged schedule of an engine.  The caller's arrays may be reused on return, so a call copies them into one of
 // kSlots page-locked slots and enqueues the upload from there; a slot is reused only after the upload that read it
@@ -74,7 +71,6 @@ int state_of(smmc_engine *e, CashflowState **out) {
   return SMMC_OK;
 }
 
-bool varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }
 float amount_at(const smmc_cashflow *cf, uint32_t t) { return cf->amounts ? cf->amounts[t] : cf->amount; }
 float fraction_at(const smmc_cashflow *cf, uint32_t t) { return cf->fractions ? cf->fractions[t] : cf->fraction; }
 
@@ -148,11 +144,11 @@ int cashflow_divide(const smmc_engine *e, const smmc_sim *sim, const smmc_cashfl
   if (!(cap > 0.0) || !std::isfinite(cap)) return SMMC_DIV_EXACT;
   double lo_a, hi_a;
   if (!smmc::host_multiplier_bounds(e, sim, &lo_a, &hi_a)) return SMMC_DIV_EXACT;
-  const uint32_t n = sim->n_periods, n_sched = varying(cf) ? n : 1u;
+  const uint32_t n = sim->n_periods, n_sched = cashflow_varying(cf) ? n : 1u;
   double contributions = 0.0, max_amount = -INFINITY, min_fraction = INFINITY, max_fraction = -INFINITY;
   for (uint32_t t = 0; t < n_sched; ++t) {
     const double am = amount_at(cf, t), fr = fraction_at(cf, t);
-    if (am < 0.0) contributions += -am * (varying(cf) ? 1.0 : static_cast<double>(n));
+    if (am < 0.0) contributions += -am * (cashflow_varying(cf) ? 1.0 : static_cast<double>(n));
     max_amount = std::max(max_amount, am);
     min_fraction = std::min(min_fraction, fr);
     max_fraction = std::max(max_fraction, fr);
@@ -175,17 +171,9 @@ int cashflow_divide(const smmc_engine *e, const smmc_sim *sim, const smmc_cashfl
   return SMMC_DIV_FAST;
 }
 
-int check_outputs(const void *fin, const void *paid, const void *ruin, const void *stats, const void *dep) {
-  if ((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(paid) | reinterpret_cast<uintptr_t>(ruin)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "the final-value, paid and ruin-period pointers must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(dep)) & 7u)
-    return host_fail(SMMC_ERR_INVALID, "the statistics and depletion-count pointers must be 8-byte aligned");
-  return SMMC_OK;
-}
-
 }  // namespace
 
-namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_internal.h)
+namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_host.h)
 int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf) {
   const int rc = check_cf_struct(cf);
   return rc ? rc : check_schedule(sim, cf);
@@ -207,7 +195,7 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
                                   float *d_paid, uint32_t *d_ruin_period, void *d_stats, uint64_t *d_depleted_at) {
   int rc = check_cashflow(e, sim, cf);
   if (rc) return rc;
-  rc = check_outputs(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
+  rc = smmc::cashflow_check_pointers(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
   if (rc) return rc;
   const smmc::EngineView view = smmc::engine_view(e);
   uint32_t grid = 0;
@@ -219,9 +207,6 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   if (lds + 2048 > view.max_lds)
     return host_fail(SMMC_ERR_INVALID, "table, depletion counters and histogram need %zu bytes of LDS, device allows %zu", lds,
                      view.max_lds);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
   smmc::CashflowArgs c;
   std::memset(&c, 0, sizeof c);
   c.amount = cf->amount;
@@ -229,35 +214,13 @@ int smmc_engine_simulate_cashflow(smmc_engine *e, const smmc_sim *sim, const smm
   c.floor = cf->floor;
   c.d_paid = d_paid;
   c.d_ruin_period = d_ruin_period;
-  if (varying(cf) && grid) {
-    rc = stage_schedule(e, sim, cf, &c);
-    if (rc) return rc;
-  }
   a.d_final = d_final;
-  smmc::ZeroLease lease;
-  if ((d_stats && sim->n_bins) || d_depleted_at) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_lease(e, &lease);
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (d_stats) {
-    a.partials = view.d_partials;
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (d_depleted_at) c.d_depleted = acc + kDepletedAt;
-  if (grid) {
-    const bool exact_div = cashflow_divide(e, sim, cf) != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_cashflow", [&] { return smmc::launch_cashflow(a, c, exact_div, grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (d_stats)
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), sim->n_bins, view.stream,
-                                      sim->n_bins ? acc : nullptr, sim->n_bins ? 1u : 0u));
-  if (d_depleted_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
-                                               reinterpret_cast<unsigned long long *>(d_depleted_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const bool exact_div = grid && cashflow_divide(e, sim, cf) != SMMC_DIV_FAST;
+  const smmc::WaveWalk walk = {"launch_cashflow", grid, sim->n_bins, {{d_stats, 0, 0, &a.partials, &a.d_hist}},
+                               {{d_depleted_at, smmc::kDepletedAt, sim->n_periods + 1u, &c.d_depleted}}};
+  return smmc::host_wave_walk_run(
+      e, walk, smmc::FoldRecord(), [&](hipStream_t stream) { return smmc::launch_cashflow(a, c, exact_div, grid, stream); },
+      [&] { return cashflow_varying(cf) && grid ? stage_schedule(e, sim, cf, &c) : SMMC_OK; });
 }
 
 int smmc_engine_simulate_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, float *host_final,

@@ -2,10 +2,11 @@
 // extremes, time under water and the first passage of two levels, reduced along every path.
 //
 // A translation unit of its own, as smmc_cashflow.cpp: smmc_capi.cpp owns struct smmc_engine and never calls into
-// this file; what is needed of an engine comes through smmc_internal.h.  It keeps no state per engine: the two
+// this file; what is needed of an engine comes through smmc_host.h.  It keeps no state per engine: the two
 // records use the halves of the engine's partial array, the four counter arrays the engine's zeroed accumulator.
-// The launch is a wave walk, and its host side is the shared one: host_require_v3, host_wave_walk_grid,
-// host_timed_launch, host_outputs_to_host and SMMC_HIP (smmc_internal.h, defined in smmc_capi.cpp).
+// The launch is a wave walk, and its run is the shared one (smmc_host.h, host_wave_walk_run) with two records and two
+// count arrays.  What is this unit's own: the argument checks, the launch shape and LDS need, how the accumulator is
+// divided, the kernel arguments, and the keepdata divide rule asked before the device is touched.
 // The reference draws the MINIMUM and TARGET levels across its trajectory plot
 // (examples/visualize_returns_cpu_v2.cpp:397-411) and counts final values below the minimum (:125-138); what
 // happened along a path it can only read off the stored trajectories.
@@ -13,10 +14,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
@@ -57,14 +58,10 @@ int check_excursions(const smmc_engine *e, const smmc_sim *sim, const smmc_excur
 }
 
 int check_alignment(const smmc_excursion_outputs *o) {
-  const uintptr_t words = reinterpret_cast<uintptr_t>(o->final) | reinterpret_cast<uintptr_t>(o->peak) |
-                          reinterpret_cast<uintptr_t>(o->low) | reinterpret_cast<uintptr_t>(o->drawdown) |
-                          reinterpret_cast<uintptr_t>(o->drawdown_period) | reinterpret_cast<uintptr_t>(o->underwater) |
-                          reinterpret_cast<uintptr_t>(o->first_below) | reinterpret_cast<uintptr_t>(o->first_reach);
-  if (words & 3u) return host_fail(SMMC_ERR_INVALID, "the per-path output pointers must be 4-byte aligned");
-  const uintptr_t wide = reinterpret_cast<uintptr_t>(o->stats) | reinterpret_cast<uintptr_t>(o->drawdown_stats) |
-                         reinterpret_cast<uintptr_t>(o->first_below_at) | reinterpret_cast<uintptr_t>(o->first_reach_at);
-  if (wide & 7u) return host_fail(SMMC_ERR_INVALID, "the record and count-array pointers must be 8-byte aligned");
+  if (smmc::host_misaligned({o->final, o->peak, o->low, o->drawdown, o->drawdown_period, o->underwater, o->first_below, o->first_reach}, 4))
+    return host_fail(SMMC_ERR_INVALID, "the per-path output pointers must be 4-byte aligned");
+  if (smmc::host_misaligned({o->stats, o->drawdown_stats, o->first_below_at, o->first_reach_at}, 8))
+    return host_fail(SMMC_ERR_INVALID, "the record and count-array pointers must be 8-byte aligned");
   return SMMC_OK;
 }
 
@@ -109,9 +106,6 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
   // a value has to be right when it is looked at: the keepdata rule (never SMMC_DIV_CHECKED)
   const int div = smmc_engine_divide_kind(e, sim, 1);
   if (div < 0) return div;
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
   smmc::ExcursionArgs xa;
   std::memset(&xa, 0, sizeof xa);
   xa.lower = x->lower;
@@ -126,42 +120,15 @@ int smmc_engine_simulate_excursions(smmc_engine *e, const smmc_sim *sim, const s
   xa.d_first_below = out->first_below;
   xa.d_first_reach = out->first_reach;
   a.d_final = out->final;
-  smmc::ZeroLease lease;
-  if (((out->stats || out->drawdown_stats) && sim->n_bins) || out->first_below_at || out->first_reach_at) {
-    rc = smmc::engine_acc_lease(e, &lease);  // zero now, and zero again after the finalize launches below
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (out->stats) {
-    a.partials = view.d_partials;
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (out->drawdown_stats) {
-    xa.dd_partials = view.d_partials + half;
-    xa.d_dd_hist = sim->n_bins ? acc + kAccDrawdownHist : nullptr;
-  }
-  if (out->first_below_at) xa.d_below_at = acc + kAccBelowAt;
-  if (out->first_reach_at) xa.d_reach_at = acc + kAccReachAt;
-  if (grid) {
-    rc = smmc::host_timed_launch(e, "launch_excursions",
-                                 [&] { return smmc::launch_excursions(a, xa, div != SMMC_DIV_FAST, grid, view.stream); });
-    if (rc) return rc;
-  }
-  const uint32_t spread = sim->n_bins ? 1u : 0u;
-  if (out->stats)
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(out->stats), sim->n_bins, view.stream,
-                                      sim->n_bins ? acc : nullptr, spread));
-  if (out->drawdown_stats)
-    SMMC_HIP(smmc::launch_finalize(view.d_partials + half, grid, static_cast<smmc_stats *>(out->drawdown_stats), sim->n_bins,
-                                      view.stream, sim->n_bins ? acc + kAccDrawdownHist : nullptr, spread));
-  if (out->first_below_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kAccBelowAt, sim->n_periods + 1u,
-                                               reinterpret_cast<unsigned long long *>(out->first_below_at), view.stream));
-  if (out->first_reach_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kAccReachAt, sim->n_periods + 1u,
-                                               reinterpret_cast<unsigned long long *>(out->first_reach_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const uint32_t n_counts = sim->n_periods + 1u;
+  const smmc::WaveWalk walk = {"launch_excursions", grid, sim->n_bins,
+                               {{out->stats, 0, 0, &a.partials, &a.d_hist},
+                                {out->drawdown_stats, half, kAccDrawdownHist, &xa.dd_partials, &xa.d_dd_hist}},
+                               {{out->first_below_at, kAccBelowAt, n_counts, &xa.d_below_at},
+                                {out->first_reach_at, kAccReachAt, n_counts, &xa.d_reach_at}}};
+  return smmc::host_wave_walk_run(e, walk, smmc::FoldRecord(), [&](hipStream_t stream) {
+    return smmc::launch_excursions(a, xa, div != SMMC_DIV_FAST, grid, stream);
+  });
 }
 
 int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_excursions *x,
@@ -174,31 +141,17 @@ int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim,
   if (rc) return rc;
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  typedef smmc_excursion_outputs O;
   const size_t stats_bytes = static_cast<size_t>(smmc_stats_bytes(sim->n_bins));
   const size_t at_bytes = sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u);
   const size_t per_path = sizeof(float) * sim->n_paths;
-  const smmc::HostPiece pieces[12] = {
-      {out->stats, stats_bytes}, {out->drawdown_stats, stats_bytes}, {out->first_below_at, at_bytes}, {out->first_reach_at, at_bytes},
-      {out->final, per_path},    {out->peak, per_path},              {out->low, per_path},            {out->drawdown, per_path},
-      {out->drawdown_period, per_path}, {out->underwater, per_path}, {out->first_below, per_path},    {out->first_reach, per_path}};
-  return smmc::host_outputs_to_host(e, "simulate_excursions_to_host", pieces, 12, [&](void *const *dev) {
-    smmc_excursion_outputs o;
-    std::memset(&o, 0, sizeof o);
-    o.struct_size = sizeof o;
-    o.stats = dev[0];
-    o.drawdown_stats = dev[1];
-    o.first_below_at = static_cast<uint64_t *>(dev[2]);
-    o.first_reach_at = static_cast<uint64_t *>(dev[3]);
-    o.final = static_cast<float *>(dev[4]);
-    o.peak = static_cast<float *>(dev[5]);
-    o.low = static_cast<float *>(dev[6]);
-    o.drawdown = static_cast<float *>(dev[7]);
-    o.drawdown_period = static_cast<uint32_t *>(dev[8]);
-    o.underwater = static_cast<uint32_t *>(dev[9]);
-    o.first_below = static_cast<uint32_t *>(dev[10]);
-    o.first_reach = static_cast<uint32_t *>(dev[11]);
-    return smmc_engine_simulate_excursions(e, sim, x, &o);
-  });
+  const smmc::OutputField fields[12] = {
+      {offsetof(O, stats), stats_bytes},        {offsetof(O, drawdown_stats), stats_bytes}, {offsetof(O, first_below_at), at_bytes},
+      {offsetof(O, first_reach_at), at_bytes},  {offsetof(O, final), per_path},             {offsetof(O, peak), per_path},
+      {offsetof(O, low), per_path},             {offsetof(O, drawdown), per_path},          {offsetof(O, drawdown_period), per_path},
+      {offsetof(O, underwater), per_path},      {offsetof(O, first_below), per_path},       {offsetof(O, first_reach), per_path}};
+  return smmc::host_outputs_struct_to_host(e, "simulate_excursions_to_host", *out, fields,
+                                           [&](const O *d) { return smmc_engine_simulate_excursions(e, sim, x, d); });
 }
 
 }  // extern "C"

@@ -1,6 +1,11 @@
 // smmc_host.h -- what the library's host translation units share and no kernel translation unit sees: ONE statement
 // of the host-buffer pinning rules (engine smmc_capi.cpp, group smmc_group.cpp, C++ drop-in smmc_dropin.cpp), the
-// owner of device and page-locked memory, and the lease on an array that is zero between launches.  Not installed.
+// owner of device and page-locked memory, the lease on an array that is zero between launches, what smmc_capi.cpp
+// shares with the feature units (engine_view, host_fail, SMMC_HIP, host_timed_launch, host_outputs_to_host, ...), what
+// those units lend each other, and the ONE statement of a wave-walk entry's run (host_wave_walk_run).  Not installed.
+// smmc_internal.h holds what a kernel translation unit or a launch stub needs and is part of the kernels' source
+// digest (tools/isa_loop_count.py); this header is not, so a host-only change here leaves profiles/pmc_traffic.json
+// valid.
 //
 // Round 3 had three copies of these rules that had drifted apart: the group hard-coded the
 // threshold and tested only a buffer's first byte for "already pinned", the drop-in treated SMMC_PIN_HOST=chunk
@@ -10,9 +15,11 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <cstring>
+#include <initializer_list>
 #include <utility>
 
-struct smmc_engine;
+#include "smmc_internal.h"  // KernelArgs, CashflowArgs, PortfolioArgs, launch_finalize*
 
 namespace smmc {
 
@@ -98,5 +105,250 @@ struct ZeroLease {
 // A lease on the engine's accumulator (kHistSpread x SMMC_MAX_BINS counters, smmc_capi.cpp) for the library's other
 // host translation units; the device must be current.
 int engine_acc_lease(smmc_engine *e, ZeroLease *lease);
+// How the depletion entries divide it.  One scenario: the final-value histogram in copy 0, the depletion counters
+// from copy 1 on.  A sweep: [scenario][bucket] from 0, [scenario][period] from kSweepDepletedAt.
+constexpr size_t kDepletedAt = SMMC_MAX_BINS;
+static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(kHistSpread) * SMMC_MAX_BINS,
+              "the engine's accumulator holds the histogram and the depletion counters");
+constexpr size_t kSweepDepletedAt = SMMC_MAX_SWEEP_COUNTERS;
+static_assert(2u * SMMC_MAX_SWEEP_COUNTERS <= static_cast<size_t>(kHistSpread) * SMMC_MAX_BINS,
+              "the engine's accumulator holds a sweep's buckets and depletion counters");
+
+// ---- what smmc_capi.cpp shares with the library's other host translation units (smmc_cashflow.cpp, ...) -----
+// Defined in smmc_capi.cpp, which owns struct smmc_engine; a unit that adds an entry point goes through these and
+// keeps what it needs per engine in its own state (engine_ext), so that smmc_capi.cpp never calls into it.
+
+// Makes `device` current for the scope and restores the caller's device after.
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != device) ok = hipSetDevice(device) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+struct EngineView {  // what a launch needs to know of an engine
+  int device;
+  hipStream_t stream;
+  uint32_t compute_units, max_grid;
+  size_t max_lds;
+  BlockPartial *d_partials;  // max_grid entries
+  unsigned long long *clock_probe;  // KernelArgs::clock_probe of a launch now: null unless smmc_engine_timing is on
+};
+// One slot of state owned by another translation unit, keyed by `owner` (the address of an object of that unit):
+// smmc_engine_destroy calls release(state) for every slot taken.
+constexpr int kEngineExtSlots = 4;
+struct EngineExt {
+  const void *owner;  // null: free
+  void *state;
+  void (*release)(void *state);
+};
+int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));  // sets smmc_last_error()
+// Returns SMMC_ERR_HIP with the call's text and place out of the enclosing function when a HIP call fails.
+#define SMMC_HIP(call)                                                                                                   \
+  do {                                                                                                                   \
+    hipError_t err__ = (call);                                                                                           \
+    if (err__ != hipSuccess)                                                                                             \
+      return smmc::host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
+  } while (0)
+// "<feature> counter stream v3 only": the refusal of SMMC_FLAG_STREAM_REF and SMMC_FLAG_STREAM_V2; `feature` ends in
+// its verb ("cash flows support").
+int host_require_v3(const smmc_sim *s, const char *feature);
+// The grid of a wave-walk launch (wave_walk_group_paths): the chunks of group_paths, at most groups_per_cu workgroups
+// per CU and at most grid_cap.  Refuses a request that would give a workgroup 2^32 paths or more (u32 counters).
+int host_wave_walk_grid(const EngineView &v, uint64_t n_paths, uint32_t group_paths, uint32_t groups_per_cu, uint32_t grid_cap,
+                        uint32_t *grid);
+// The engine's timing pair around launch(ctx) -- begun before, closed on both paths; a failed launch is
+// "<name> failed: <HIP's text>".  The template takes any callable returning hipError_t.
+int host_timed_launch(smmc_engine *e, const char *name, hipError_t (*launch)(void *ctx), void *ctx);
+template <typename F>
+int host_timed_launch(smmc_engine *e, const char *name, F launch) {
+  return host_timed_launch(e, name, [](void *f) { return (*static_cast<F *>(f))(); }, &launch);
+}
+// The _to_host form of an entry: one device allocation for all pieces (host == null: left out; the 8-byte aligned
+// ones come first), run(dev, ctx) with the pieces' device pointers (null for one left out) enqueues on the engine
+// stream; the stream is synchronised also after a failure (nothing of the call may outlive the buffer), the pieces
+// are copied if all went well.  A HIP failure after a successful run is "<what>: <HIP's text>".  Device must be current.
+struct HostPiece {
+  void *host;
+  size_t bytes;
+};
+constexpr int kMaxHostPieces = 12;  // the most any entry has: the twelve outputs of smmc_excursion_outputs
+int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces,
+                         int (*run)(void *const *dev, void *ctx), void *ctx);
+template <typename F>  // any callable int(void *const *dev), as host_timed_launch
+int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces, F run) {
+  return host_outputs_to_host(e, what, pieces, n_pieces, [](void *const *dev, void *f) { return (*static_cast<F *>(f))(dev); }, &run);
+}
+int host_check_sim(const smmc_engine *e, const smmc_sim *s);
+// bounds on a = 100 + r of one period; false if there are none (smmc_capi.cpp, divide_kind)
+bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
+KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
+EngineView engine_view(const smmc_engine *e);
+// The slot of `owner`, claimed at the first ask; null when every slot belongs to somebody else.
+EngineExt *engine_ext(smmc_engine *e, const void *owner);
+// smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
+int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
+// smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around
+// another enqueue: `enqueue` is called with the device current, once per chunk, with that chunk's smmc_sim and
+// device buffers (any may be null), and enqueues on the engine stream as smmc_engine_simulate does.
+typedef int (*HostEnqueue)(smmc_engine *e, const smmc_sim *part, float *d_final, float *d_chunk_mean, float *d_chunk_var,
+                           void *d_stats, const void *ctx);
+int host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final, float *host_chunk_mean, float *host_chunk_var,
+                          volatile int64_t *progress, smmc_stats *stats, uint64_t *hist, HostEnqueue enqueue, const void *ctx);
+
+// ---- what smmc_portfolio.cpp and smmc_cashflow.cpp lend to smmc_portfolio_cashflow.cpp -----------------------------
+// Each rule is stated once, in the unit that owns it; neither unit refers to the borrower.
+// smmc_portfolio.cpp: every argument check of smmc_engine_simulate_portfolio on (e, sim, pf), the asset table included;
+int portfolio_check(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf);
+// bounds on asset k's multiplier a_k, false if there are none that keep it positive (the divide rule's);
+bool portfolio_asset_bounds(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, uint32_t k, double *lo_a, double *hi_a);
+// the KernelArgs and PortfolioArgs of a checked request (the asset table, the draw at scale 1, weights, s_k, L).
+void portfolio_launch_args(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, KernelArgs *a, PortfolioArgs *p);
+// smmc_cashflow.cpp: the checks of smmc_engine_simulate_cashflow on cf itself and on n_periods;
+int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf);
+inline bool cashflow_varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }  // per-period arrays
+// the arrays of a varying schedule staged and their upload enqueued: c->schedule, c->stride.  Device must be current.
+int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c);
+
+// ---- what the entries of the feature units share: the checks of their outputs, the run, the _to_host form ----------
+// An *_outputs structure of include/smmc.h that begins with struct_size and reserved; `type` is its name.
+template <typename Out>
+int host_check_outputs(const Out *out, const char *type) {
+  if (!out) return host_fail(SMMC_ERR_INVALID, "the %s argument is NULL", type);
+  if (out->struct_size != sizeof(Out))
+    return host_fail(SMMC_ERR_INVALID, "%s.struct_size is %u, this library expects %zu", type, out->struct_size, sizeof(Out));
+  if (out->reserved != 0) return host_fail(SMMC_ERR_INVALID, "%s.reserved is %u, it must be 0", type, out->reserved);
+  return SMMC_OK;
+}
+// Is one of the pointers no multiple of `align` (4 or 8)?  The refusal's text stays the entry's own.
+inline bool host_misaligned(std::initializer_list<const void *> ptrs, uintptr_t align) {
+  uintptr_t bits = 0;
+  for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & (align - 1u)) != 0;
+}
+// The entries with loose output pointers (smmc_cashflow.cpp, smmc_sweep.cpp);
+inline int cashflow_check_pointers(const void *fin, const void *paid, const void *ruin, const void *stats, const void *dep) {
+  if (host_misaligned({fin, paid, ruin}, 4))
+    return host_fail(SMMC_ERR_INVALID, "the final-value, paid and ruin-period pointers must be 4-byte aligned");
+  if (host_misaligned({stats, dep}, 8))
+    return host_fail(SMMC_ERR_INVALID, "the statistics and depletion-count pointers must be 8-byte aligned");
+  return SMMC_OK;
+}
+// those with an outputs structure of a portfolio's depletion; `more`: one of the structure's further per-path pointers
+// is misaligned, `words` then names them all.
+template <typename Out>
+int host_check_depletion_alignment(const Out *o, bool more = false,
+                                   const char *words = "d_final, d_holdings, d_paid and d_ruin_period must be 4-byte aligned") {
+  if (more || host_misaligned({o->d_final, o->d_holdings, o->d_paid, o->d_ruin_period}, 4)) return host_fail(SMMC_ERR_INVALID, "%s", words);
+  if (host_misaligned({o->d_stats, o->d_depleted_at}, 8)) return host_fail(SMMC_ERR_INVALID, "d_stats and d_depleted_at must be 8-byte aligned");
+  return SMMC_OK;
+}
+
+// The run of a wave-walk entry, stated ONCE (host_wave_walk_run).  The entry has made every check that needs no device
+// and built its kernel arguments; it says what differs between entries:
+struct WalkRecord {  // a statistics record of the launch; d_stats null: not asked for
+  void *d_stats;                  // device: where the fold writes it
+  uint32_t partials_at;           // its partials in the engine's partial array (EngineView::d_partials)
+  size_t hist_at;                 // its bucket counts in the engine's accumulator
+  BlockPartial **partials;        // the kernel arguments that get the two
+  unsigned long long **d_hist;
+};
+struct WalkCounts {  // a count array of the launch (depletion, first passage); d_out null: not asked for
+  uint64_t *d_out;                // device: where launch_finalize_depleted copies it
+  size_t acc_at;                  // its counters in the engine's accumulator
+  uint32_t n;
+  unsigned long long **d_counts;  // the kernel argument that gets them
+};
+struct WaveWalk {
+  const char *name;  // of the launch, as host_timed_launch reports its failure
+  uint32_t grid;     // workgroups; 0 (no paths): nothing is launched, the folds still write the empty outputs
+  uint32_t n_bins;   // smmc_sim::n_bins of the request
+  WalkRecord records[2];
+  WalkCounts counts[2];
+};
+// How a record is folded: one record (launch_finalize), or the packed records of n scenarios whose partials and
+// buckets lie [scenario][...] from the record's offsets (launch_finalize_sweep).  A type each, so that a unit refers to
+// the launch symbol of its own fold only.
+struct FoldRecord {
+  hipError_t operator()(const BlockPartial *partials, uint32_t grid, void *d_stats, uint32_t n_bins, unsigned long long *hist,
+                        hipStream_t stream) const {
+    return launch_finalize(partials, grid, static_cast<smmc_stats *>(d_stats), n_bins, stream, hist, n_bins ? 1u : 0u);
+  }
+};
+struct FoldScenarios {
+  uint32_t n;
+  hipError_t operator()(const BlockPartial *partials, uint32_t grid, void *d_stats, uint32_t n_bins, unsigned long long *hist,
+                        hipStream_t stream) const {
+    return launch_finalize_sweep(partials, grid, n, d_stats, n_bins, hist, stream);
+  }
+};
+struct NoPrepare {
+  int operator()() const { return SMMC_OK; }
+};
+// The protocol: the engine's device current; prepare() (what an entry enqueues before its kernel: a staged schedule); the
+// lease on the accumulator if a histogram or a count array will be counted -- zero now, and zero again after the folds;
+// the kernel arguments wired; launch(stream) unless the grid is empty; the records folded, then the count arrays; and
+// only with all folds in the queue the lease's mark comes off.  Any error return in between leaves the accumulator dirty.
+template <typename Fold, typename Launch, typename Prepare = NoPrepare>
+int host_wave_walk_run(smmc_engine *e, const WaveWalk &w, Fold fold, Launch launch, Prepare prepare = Prepare()) {
+  const EngineView view = engine_view(e);
+  DeviceGuard guard(view.device);
+  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  int rc = prepare();
+  if (rc) return rc;
+  bool counted = false;
+  for (const WalkRecord &r : w.records) counted = counted || (r.d_stats && w.n_bins);
+  for (const WalkCounts &c : w.counts) counted = counted || c.d_out;
+  ZeroLease lease;
+  if (counted) {
+    rc = engine_acc_lease(e, &lease);
+    if (rc) return rc;
+  }
+  unsigned long long *const acc = lease.acc();
+  for (const WalkRecord &r : w.records)
+    if (r.d_stats) {
+      *r.partials = view.d_partials + r.partials_at;
+      *r.d_hist = w.n_bins ? acc + r.hist_at : nullptr;
+    }
+  for (const WalkCounts &c : w.counts)
+    if (c.d_out) *c.d_counts = acc + c.acc_at;
+  if (w.grid) {
+    rc = host_timed_launch(e, w.name, [&] { return launch(view.stream); });
+    if (rc) return rc;
+  }
+  for (const WalkRecord &r : w.records)
+    if (r.d_stats)
+      SMMC_HIP(fold(view.d_partials + r.partials_at, w.grid, r.d_stats, w.n_bins, w.n_bins ? acc + r.hist_at : nullptr, view.stream));
+  for (const WalkCounts &c : w.counts)
+    if (c.d_out) SMMC_HIP(launch_finalize_depleted(acc + c.acc_at, c.n, reinterpret_cast<unsigned long long *>(c.d_out), view.stream));
+  lease.finalize_queued();
+  return SMMC_OK;
+}
+
+// host_outputs_to_host for an entry that takes an *_outputs structure: `fields` lists its pointer members (offsetof) with
+// the bytes behind each, the 8-byte aligned ones first; run(d) gets a copy of `out` with the device pointers in them.
+struct OutputField {
+  size_t offset, bytes;
+};
+template <typename Out, int N, typename F>
+int host_outputs_struct_to_host(smmc_engine *e, const char *what, const Out &out, const OutputField (&fields)[N], F run) {
+  static_assert(N <= kMaxHostPieces, "more pieces than host_outputs_to_host takes");
+  HostPiece pieces[N];
+  for (int i = 0; i < N; ++i) {
+    std::memcpy(&pieces[i].host, reinterpret_cast<const char *>(&out) + fields[i].offset, sizeof(void *));
+    pieces[i].bytes = fields[i].bytes;
+  }
+  return host_outputs_to_host(e, what, pieces, N, [&](void *const *dev) {
+    Out d = out;
+    for (int i = 0; i < N; ++i) std::memcpy(reinterpret_cast<char *>(&d) + fields[i].offset, &dev[i], sizeof(void *));
+    return run(&d);
+  });
+}
 
 }  // namespace smmc

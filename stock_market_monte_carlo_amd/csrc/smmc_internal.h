@@ -1,4 +1,6 @@
-// smmc_internal.h -- shared between the kernel TU and the C-ABI TU (not installed).
+// smmc_internal.h -- what a kernel translation unit or a launch stub needs, shared with the host units: the argument
+// structures, launch_*, *_lds_bytes and the constants (not installed).  Part of the kernels' source digest
+// (tools/isa_loop_count.py): what only host units share belongs in smmc_host.h, which is not.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -277,107 +279,5 @@ size_t allocation_sweep_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_asse
 size_t keepdata_lds_bytes(uint32_t table_len, int tile, int waves, int stream);
 size_t bm_tables_bytes(int stream);  // 2 | 3
 hipError_t static_lds_bytes(size_t *bytes);  // of the kernels that address the v3 tables absolutely: 0
-
-// ---- what smmc_capi.cpp shares with the library's other host translation units (smmc_cashflow.cpp, ...) -----
-// Defined in smmc_capi.cpp, which owns struct smmc_engine; a unit that adds an entry point goes through these and
-// keeps what it needs per engine in its own state (engine_ext), so that smmc_capi.cpp never calls into it.
-
-// Makes `device` current for the scope and restores the caller's device after.
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-struct EngineView {  // what a launch needs to know of an engine
-  int device;
-  hipStream_t stream;
-  uint32_t compute_units, max_grid;
-  size_t max_lds;
-  BlockPartial *d_partials;  // max_grid entries
-  unsigned long long *clock_probe;  // KernelArgs::clock_probe of a launch now: null unless smmc_engine_timing is on
-};
-// One slot of state owned by another translation unit, keyed by `owner` (the address of an object of that unit):
-// smmc_engine_destroy calls release(state) for every slot taken.
-constexpr int kEngineExtSlots = 4;
-struct EngineExt {
-  const void *owner;  // null: free
-  void *state;
-  void (*release)(void *state);
-};
-int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));  // sets smmc_last_error()
-// Returns SMMC_ERR_HIP with the call's text and place out of the enclosing function when a HIP call fails.
-#define SMMC_HIP(call)                                                                                                   \
-  do {                                                                                                                   \
-    hipError_t err__ = (call);                                                                                           \
-    if (err__ != hipSuccess)                                                                                             \
-      return smmc::host_fail(SMMC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-  } while (0)
-// "<feature> counter stream v3 only": the refusal of SMMC_FLAG_STREAM_REF and SMMC_FLAG_STREAM_V2; `feature` ends in
-// its verb ("cash flows support").
-int host_require_v3(const smmc_sim *s, const char *feature);
-// The grid of a wave-walk launch (wave_walk_group_paths): the chunks of group_paths, at most groups_per_cu workgroups
-// per CU and at most grid_cap.  Refuses a request that would give a workgroup 2^32 paths or more (u32 counters).
-int host_wave_walk_grid(const EngineView &v, uint64_t n_paths, uint32_t group_paths, uint32_t groups_per_cu, uint32_t grid_cap,
-                        uint32_t *grid);
-// The engine's timing pair around launch(ctx) -- begun before, closed on both paths; a failed launch is
-// "<name> failed: <HIP's text>".  The template takes any callable returning hipError_t.
-int host_timed_launch(smmc_engine *e, const char *name, hipError_t (*launch)(void *ctx), void *ctx);
-template <typename F>
-int host_timed_launch(smmc_engine *e, const char *name, F launch) {
-  return host_timed_launch(e, name, [](void *f) { return (*static_cast<F *>(f))(); }, &launch);
-}
-// The _to_host form of an entry: one device allocation for all pieces (host == null: left out; the 8-byte aligned
-// ones come first), run(dev, ctx) with the pieces' device pointers (null for one left out) enqueues on the engine
-// stream; the stream is synchronised also after a failure (nothing of the call may outlive the buffer), the pieces
-// are copied if all went well.  A HIP failure after a successful run is "<what>: <HIP's text>".  Device must be current.
-struct HostPiece {
-  void *host;
-  size_t bytes;
-};
-constexpr int kMaxHostPieces = 12;  // the most any entry has: the twelve outputs of smmc_excursion_outputs
-int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces,
-                         int (*run)(void *const *dev, void *ctx), void *ctx);
-template <typename F>  // any callable int(void *const *dev), as host_timed_launch
-int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *pieces, int n_pieces, F run) {
-  return host_outputs_to_host(e, what, pieces, n_pieces, [](void *const *dev, void *f) { return (*static_cast<F *>(f))(dev); }, &run);
-}
-int host_check_sim(const smmc_engine *e, const smmc_sim *s);
-// bounds on a = 100 + r of one period; false if there are none (smmc_capi.cpp, divide_kind)
-bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
-KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
-EngineView engine_view(const smmc_engine *e);
-// The slot of `owner`, claimed at the first ask; null when every slot belongs to somebody else.
-EngineExt *engine_ext(smmc_engine *e, const void *owner);
-// (the engine's zeroed accumulator is leased through smmc_host.h: ZeroLease, engine_acc_lease)
-// smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
-int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
-// smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around
-// another enqueue: `enqueue` is called with the device current, once per chunk, with that chunk's smmc_sim and
-// device buffers (any may be null), and enqueues on the engine stream as smmc_engine_simulate does.
-typedef int (*HostEnqueue)(smmc_engine *e, const smmc_sim *part, float *d_final, float *d_chunk_mean, float *d_chunk_var,
-                           void *d_stats, const void *ctx);
-int host_simulate_to_host(smmc_engine *e, const smmc_sim *sim, float *host_final, float *host_chunk_mean, float *host_chunk_var,
-                          volatile int64_t *progress, smmc_stats *stats, uint64_t *hist, HostEnqueue enqueue, const void *ctx);
-
-// ---- what smmc_portfolio.cpp and smmc_cashflow.cpp lend to smmc_portfolio_cashflow.cpp -----------------------------
-// Each rule is stated once, in the unit that owns it; neither unit refers to the borrower.
-// smmc_portfolio.cpp: every argument check of smmc_engine_simulate_portfolio on (e, sim, pf), the asset table included;
-int portfolio_check(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf);
-// bounds on asset k's multiplier a_k, false if there are none that keep it positive (the divide rule's);
-bool portfolio_asset_bounds(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, uint32_t k, double *lo_a, double *hi_a);
-// the KernelArgs and PortfolioArgs of a checked request (the asset table, the draw at scale 1, weights, s_k, L).
-void portfolio_launch_args(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, KernelArgs *a, PortfolioArgs *p);
-// smmc_cashflow.cpp: the checks of smmc_engine_simulate_cashflow on cf itself and on n_periods;
-int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf);
-// the arrays of a varying schedule staged and their upload enqueued: c->schedule, c->stride.  Device must be current.
-int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c);
 
 }  // namespace smmc

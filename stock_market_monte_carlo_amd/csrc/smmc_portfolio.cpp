@@ -3,22 +3,23 @@
 // rebalanced every R periods.
 //
 // A translation unit of its own, as smmc_cashflow.cpp and smmc_blocks.cpp: smmc_capi.cpp owns struct smmc_engine and
-// never calls into this file; what is needed of an engine comes through smmc_internal.h and smmc_host.h.  What this
-// file keeps per engine -- the joint table and its columns' extremes -- hangs in this unit's extension slot of the
-// engine (engine_ext), released by smmc_engine_destroy.  The launch is a wave walk and its host side the shared one:
-// host_require_v3, host_wave_walk_grid, engine_acc_lease, host_timed_launch, host_outputs_to_host and SMMC_HIP.  The
-// reference simulates one return series per path; it has no portfolio.
+// never calls into this file; what is needed of an engine comes through smmc_host.h.  What this file keeps per engine
+// -- the joint table and its columns' extremes -- hangs in this unit's extension slot of the engine (engine_ext),
+// released by smmc_engine_destroy.  The launch is a wave walk and its run the shared one (smmc_host.h,
+// host_wave_walk_run) with one record and no count array.  What is this unit's own: the asset table, the portfolio's
+// checks, the divide rule, the LDS need and the kernel arguments.  The reference simulates one return series per path;
+// it has no portfolio.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <limits>
 #include <new>
 #include <vector>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
@@ -154,15 +155,6 @@ int portfolio_divide(const smmc_engine *e, const smmc_sim *sim, const smmc_portf
   return SMMC_DIV_FAST;
 }
 
-int check_outputs(const smmc_portfolio_outputs *out) {
-  if (!out) return host_fail(SMMC_ERR_INVALID, "the smmc_portfolio_outputs argument is NULL");
-  if (out->struct_size != sizeof(smmc_portfolio_outputs))
-    return host_fail(SMMC_ERR_INVALID, "smmc_portfolio_outputs.struct_size is %u, this library expects %zu", out->struct_size,
-                     sizeof(smmc_portfolio_outputs));
-  if (out->reserved != 0) return host_fail(SMMC_ERR_INVALID, "smmc_portfolio_outputs.reserved is %u, it must be 0", out->reserved);
-  return SMMC_OK;
-}
-
 // The launch's arguments and LDS need, and the refusals that follow from them; asked before any device work.
 struct Plan {
   smmc::KernelArgs a;
@@ -209,7 +201,7 @@ int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, bo
 
 }  // namespace
 
-namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_internal.h)
+namespace smmc {  // what smmc_portfolio_cashflow.cpp takes of this unit (smmc_host.h)
 int portfolio_check(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf) { return check_portfolio(e, sim, pf); }
 bool portfolio_asset_bounds(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, uint32_t k, double *lo_a, double *hi_a) {
   return asset_bounds(e, sim, pf, k, lo_a, hi_a);
@@ -274,48 +266,27 @@ int smmc_engine_portfolio_divide_kind(smmc_engine *e, const smmc_sim *sim, const
 int smmc_engine_simulate_portfolio(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_portfolio_outputs *out) {
   int rc = check_portfolio(e, sim, pf);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_portfolio_outputs");
   if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(out->d_final) | reinterpret_cast<uintptr_t>(out->d_holdings)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "d_final and d_holdings must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(out->d_stats) & 7u) return host_fail(SMMC_ERR_INVALID, "d_stats must be 8-byte aligned");
+  if (smmc::host_misaligned({out->d_final, out->d_holdings}, 4)) return host_fail(SMMC_ERR_INVALID, "d_final and d_holdings must be 4-byte aligned");
+  if (smmc::host_misaligned({out->d_stats}, 8)) return host_fail(SMMC_ERR_INVALID, "d_stats must be 8-byte aligned");
   Plan pl;
   rc = plan(e, sim, pf, out->d_stats != nullptr, &pl);
   if (rc) return rc;
-  const smmc::EngineView view = smmc::engine_view(e);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
-  smmc::KernelArgs &a = pl.a;
-  a.d_final = out->d_final;
+  pl.a.d_final = out->d_final;
   pl.p.d_holdings = out->d_holdings;
-  smmc::ZeroLease lease;
-  if (out->d_stats) {  // no memset: finalize_kernel writes the whole record and leaves the accumulator zero again
-    a.partials = view.d_partials;
-    if (sim->n_bins) {
-      rc = smmc::engine_acc_lease(e, &lease);
-      if (rc) return rc;
-      a.d_hist = lease.acc();
-    }
-  }
-  if (pl.grid) {
-    const bool exact_div = portfolio_divide(e, sim, pf) != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_portfolio", [&] { return smmc::launch_portfolio(a, pl.p, exact_div, pl.grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (out->d_stats) {
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, pl.grid, static_cast<smmc_stats *>(out->d_stats), sim->n_bins, view.stream, lease.acc(),
-                                   sim->n_bins ? 1u : 0u));
-    lease.finalize_queued();
-  }
-  return SMMC_OK;
+  const bool exact_div = pl.grid && portfolio_divide(e, sim, pf) != SMMC_DIV_FAST;
+  // no count array: the accumulator is leased only for a histogram
+  const smmc::WaveWalk walk = {"launch_portfolio", pl.grid, sim->n_bins, {{out->d_stats, 0, 0, &pl.a.partials, &pl.a.d_hist}}, {}};
+  return smmc::host_wave_walk_run(e, walk, smmc::FoldRecord(),
+                                  [&](hipStream_t stream) { return smmc::launch_portfolio(pl.a, pl.p, exact_div, pl.grid, stream); });
 }
 
 int smmc_engine_simulate_portfolio_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                            const smmc_portfolio_outputs *out) {
   int rc = check_portfolio(e, sim, pf);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_portfolio_outputs");
   if (rc) return rc;
   Plan pl;  // refuse before anything is allocated
   rc = plan(e, sim, pf, out->d_stats != nullptr, &pl);
@@ -323,17 +294,13 @@ int smmc_engine_simulate_portfolio_to_host(smmc_engine *e, const smmc_sim *sim, 
   const smmc::EngineView view = smmc::engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  typedef smmc_portfolio_outputs O;
   const size_t per_path = sizeof(float) * sim->n_paths;
-  const smmc::HostPiece pieces[3] = {{out->d_stats, static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
-                                     {out->d_final, per_path},
-                                     {out->d_holdings, per_path * pf->n_assets}};
-  return smmc::host_outputs_to_host(e, "simulate_portfolio_to_host", pieces, 3, [&](void *const *dev) {
-    smmc_portfolio_outputs d = *out;
-    d.d_stats = dev[0];
-    d.d_final = static_cast<float *>(dev[1]);
-    d.d_holdings = static_cast<float *>(dev[2]);
-    return smmc_engine_simulate_portfolio(e, sim, pf, &d);
-  });
+  const smmc::OutputField fields[3] = {{offsetof(O, d_stats), static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
+                                       {offsetof(O, d_final), per_path},
+                                       {offsetof(O, d_holdings), per_path * pf->n_assets}};
+  return smmc::host_outputs_struct_to_host(e, "simulate_portfolio_to_host", *out, fields,
+                                           [&](const O *d) { return smmc_engine_simulate_portfolio(e, sim, pf, d); });
 }
 
 }  // extern "C"

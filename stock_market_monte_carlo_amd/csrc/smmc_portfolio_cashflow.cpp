@@ -4,46 +4,31 @@
 //
 // A translation unit of its own, as its two parents: smmc_capi.cpp owns struct smmc_engine and never calls into this
 // file.  The portfolio's argument checks, asset table and launch arguments are smmc_portfolio.cpp's, the schedule's
-// checks and staging smmc_cashflow.cpp's (smmc_internal.h, "lend"): this unit states neither again and keeps no state
-// of its own.  What is its own: the output structure's checks, the LDS need, the divide rule ("Portfolio
-// cash flows", has the proof) and the launch.  The launch is a wave walk and its host side the shared one:
-// host_wave_walk_grid, engine_acc_lease, host_timed_launch, host_outputs_to_host and SMMC_HIP.
+// checks and staging smmc_cashflow.cpp's (smmc_host.h, "lend"): this unit states neither again and keeps no state
+// of its own.  What is its own: the LDS need, the divide rule ("Portfolio cash flows", has the proof), the
+// kernel arguments, and which record and count array the launch leaves.  The launch is a wave walk and its run the
+// shared one (smmc_host.h, host_wave_walk_run), as are the output structure's checks.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
+using smmc::cashflow_varying;
 using smmc::DeviceGuard;
 using smmc::host_fail;
 
 // Workgroups per CU, as cashflow_kernel: a workgroup flushes n_periods + 1 + n_bins counters.
 constexpr uint32_t kGroupsPerCU = 32;
-// The depletion counters take the engine's accumulator from copy 1 on (copy 0 holds the final-value histogram).
-constexpr size_t kDepletedAt = SMMC_MAX_BINS;
-static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
-              "the engine's accumulator holds the histogram and the depletion counters");
-
-bool varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }
 
 int check_request(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf) {
   const int rc = smmc::portfolio_check(e, sim, pf);
   return rc ? rc : smmc::cashflow_check_schedule(sim, cf);
-}
-
-int check_outputs(const smmc_portfolio_cashflow_outputs *out) {
-  if (!out) return host_fail(SMMC_ERR_INVALID, "the smmc_portfolio_cashflow_outputs argument is NULL");
-  if (out->struct_size != sizeof(smmc_portfolio_cashflow_outputs))
-    return host_fail(SMMC_ERR_INVALID, "smmc_portfolio_cashflow_outputs.struct_size is %u, this library expects %zu", out->struct_size,
-                     sizeof(smmc_portfolio_cashflow_outputs));
-  if (out->reserved != 0)
-    return host_fail(SMMC_ERR_INVALID, "smmc_portfolio_cashflow_outputs.reserved is %u, it must be 0", out->reserved);
-  return SMMC_OK;
 }
 
 // The rule of include/smmc.h (smmc_engine_portfolio_cashflow_divide_kind); DESIGN.md, "Portfolio cash flows", has the
@@ -77,11 +62,11 @@ int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio 
   // the flows: all of them paid in (every amount <= 0, every fraction 0), or one constant amount and fraction 0
   bool no_fraction = true, all_in = true;
   double paid_in = 0.0;
-  for (uint32_t t = 0; t < (varying(cf) ? P : 1u); ++t) {
+  for (uint32_t t = 0; t < (cashflow_varying(cf) ? P : 1u); ++t) {
     const double am = cf->amounts ? cf->amounts[t] : cf->amount, fr = cf->fractions ? cf->fractions[t] : cf->fraction;
     no_fraction = no_fraction && fr == 0.0;
     all_in = all_in && am <= 0.0;
-    paid_in += std::fabs(am) * (varying(cf) ? 1.0 : p);
+    paid_in += std::fabs(am) * (cashflow_varying(cf) ? 1.0 : p);
   }
   if (!no_fraction) return SMMC_DIV_EXACT;
   // above, both shapes: the sum of the holdings' magnitudes grows by the best asset's factor and by |amount| per period
@@ -94,7 +79,7 @@ int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio 
     const double start = std::min(std::log2(h_min), std::log2(w_min) + std::log2(cap));
     if (start - p * shrink + std::min(0.0, std::log2(lo_min)) - slack > -89.0) return SMMC_DIV_FAST;
   }
-  if (!varying(cf) && cf->amount != 0.0f) {
+  if (!cashflow_varying(cf) && cf->amount != 0.0f) {
     // below: a holding that enters a product is the initial one, a rebalanced share of a value above the floor, or a
     // binary32 difference with the flow's share s_k = fl(amount * w_k), which is 0 or at least 2^-25 |s_k|
     const bool rebalances = pf->rebalance_every != 0 && pf->rebalance_every < P;
@@ -149,62 +134,31 @@ int smmc_engine_simulate_portfolio_cashflow(smmc_engine *e, const smmc_sim *sim,
                                             const smmc_portfolio_cashflow_outputs *out) {
   int rc = check_request(e, sim, pf, cf);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_portfolio_cashflow_outputs");
   if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(out->d_final) | reinterpret_cast<uintptr_t>(out->d_holdings) | reinterpret_cast<uintptr_t>(out->d_paid) |
-       reinterpret_cast<uintptr_t>(out->d_ruin_period)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "d_final, d_holdings, d_paid and d_ruin_period must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->d_stats) | reinterpret_cast<uintptr_t>(out->d_depleted_at)) & 7u)
-    return host_fail(SMMC_ERR_INVALID, "d_stats and d_depleted_at must be 8-byte aligned");
+  rc = smmc::host_check_depletion_alignment(out);
+  if (rc) return rc;
   Plan pl;
   rc = plan(e, sim, pf, cf, out->d_stats != nullptr, &pl);
   if (rc) return rc;
-  const smmc::EngineView view = smmc::engine_view(e);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
-  smmc::KernelArgs &a = pl.a;
   smmc::CashflowArgs &c = pl.x.c;
-  a.d_final = out->d_final;
+  pl.a.d_final = out->d_final;
   pl.x.p.d_holdings = out->d_holdings;
   c.d_paid = out->d_paid;
   c.d_ruin_period = out->d_ruin_period;
-  if (varying(cf) && pl.grid) {
-    rc = smmc::cashflow_stage_schedule(e, sim, cf, &c);
-    if (rc) return rc;
-  }
-  smmc::ZeroLease lease;
-  if ((out->d_stats && sim->n_bins) || out->d_depleted_at) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_lease(e, &lease);
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (out->d_stats) {
-    a.partials = view.d_partials;
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (out->d_depleted_at) c.d_depleted = acc + kDepletedAt;
-  if (pl.grid) {
-    const bool exact_div = divide_rule(e, sim, pf, cf) != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_portfolio_cashflow",
-                                 [&] { return smmc::launch_portfolio_cashflow(a, pl.x, exact_div, pl.grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (out->d_stats)
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, pl.grid, static_cast<smmc_stats *>(out->d_stats), sim->n_bins, view.stream,
-                                   sim->n_bins ? acc : nullptr, sim->n_bins ? 1u : 0u));
-  if (out->d_depleted_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
-                                            reinterpret_cast<unsigned long long *>(out->d_depleted_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const bool exact_div = pl.grid && divide_rule(e, sim, pf, cf) != SMMC_DIV_FAST;
+  const smmc::WaveWalk walk = {"launch_portfolio_cashflow", pl.grid, sim->n_bins, {{out->d_stats, 0, 0, &pl.a.partials, &pl.a.d_hist}},
+                               {{out->d_depleted_at, smmc::kDepletedAt, sim->n_periods + 1u, &c.d_depleted}}};
+  return smmc::host_wave_walk_run(
+      e, walk, smmc::FoldRecord(), [&](hipStream_t stream) { return smmc::launch_portfolio_cashflow(pl.a, pl.x, exact_div, pl.grid, stream); },
+      [&] { return cashflow_varying(cf) && pl.grid ? smmc::cashflow_stage_schedule(e, sim, cf, &c) : SMMC_OK; });
 }
 
 int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                     const smmc_cashflow *cf, const smmc_portfolio_cashflow_outputs *out) {
   int rc = check_request(e, sim, pf, cf);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_portfolio_cashflow_outputs");
   if (rc) return rc;
   Plan pl;  // refuse before anything is allocated
   rc = plan(e, sim, pf, cf, out->d_stats != nullptr, &pl);
@@ -212,23 +166,16 @@ int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_s
   const smmc::EngineView view = smmc::engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  typedef smmc_portfolio_cashflow_outputs O;
   const size_t per_path = sizeof(float) * sim->n_paths;
-  const smmc::HostPiece pieces[6] = {{out->d_stats, static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
-                                     {out->d_depleted_at, sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u)},
-                                     {out->d_final, per_path},
-                                     {out->d_holdings, per_path * pf->n_assets},
-                                     {out->d_paid, per_path},
-                                     {out->d_ruin_period, per_path}};
-  return smmc::host_outputs_to_host(e, "simulate_portfolio_cashflow_to_host", pieces, 6, [&](void *const *dev) {
-    smmc_portfolio_cashflow_outputs d = *out;
-    d.d_stats = dev[0];
-    d.d_depleted_at = static_cast<uint64_t *>(dev[1]);
-    d.d_final = static_cast<float *>(dev[2]);
-    d.d_holdings = static_cast<float *>(dev[3]);
-    d.d_paid = static_cast<float *>(dev[4]);
-    d.d_ruin_period = static_cast<uint32_t *>(dev[5]);
-    return smmc_engine_simulate_portfolio_cashflow(e, sim, pf, cf, &d);
-  });
+  const smmc::OutputField fields[6] = {{offsetof(O, d_stats), static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
+                                       {offsetof(O, d_depleted_at), sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u)},
+                                       {offsetof(O, d_final), per_path},
+                                       {offsetof(O, d_holdings), per_path * pf->n_assets},
+                                       {offsetof(O, d_paid), per_path},
+                                       {offsetof(O, d_ruin_period), per_path}};
+  return smmc::host_outputs_struct_to_host(e, "simulate_portfolio_cashflow_to_host", *out, fields,
+                                           [&](const O *d) { return smmc_engine_simulate_portfolio_cashflow(e, sim, pf, cf, d); });
 }
 
 }  // extern "C"

@@ -6,32 +6,27 @@
 // into this file, and no other unit refers to it.  The joint law is K + 1 series wide, so the portfolio's argument
 // checks, asset table, multiplier bounds and launch arguments are smmc_portfolio.cpp's put to a copy of the request
 // with n_assets = K + 1 (`law` below: the lent helpers take the width from the structure and need no parameter for
-// it); the schedule's checks and staging are smmc_cashflow.cpp's (smmc_internal.h, "lend").  What is this unit's own:
-// the two checks the wider law cannot make (K = SMMC_MAX_ASSETS, weights[K] != 0), the output structure's checks, the
-// divide rule ("Real cash flows", has the proof) and the launch.  The launch is a wave walk and its host
-// side the shared one: host_wave_walk_grid, engine_acc_lease, host_timed_launch, host_outputs_to_host and SMMC_HIP.
+// it); the schedule's checks and staging are smmc_cashflow.cpp's (smmc_host.h, "lend").  What is this unit's own:
+// the two checks the wider law cannot make (K = SMMC_MAX_ASSETS, weights[K] != 0), the wording of its alignment
+// refusal, the divide rule ("Real cash flows", has the proof), the LDS need and the kernel arguments.  The
+// launch is a wave walk and its run the shared one (smmc_host.h, host_wave_walk_run), as are the output structure's checks.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
+using smmc::cashflow_varying;
 using smmc::DeviceGuard;
 using smmc::host_fail;
 
 // Workgroups per CU, as portfolio_cashflow_kernel: a workgroup flushes n_periods + 1 + n_bins counters.
 constexpr uint32_t kGroupsPerCU = 32;
-// The depletion counters take the engine's accumulator from copy 1 on (copy 0 holds the histogram of the real values).
-constexpr size_t kDepletedAt = SMMC_MAX_BINS;
-static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
-              "the engine's accumulator holds the histogram and the depletion counters");
-
-bool varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }
 
 // Every check on (e, sim, pf, cf); on success *law is pf at the joint law's width, n_assets = K + 1.
 int check_request(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf, smmc_portfolio *law) {
@@ -52,15 +47,6 @@ int check_request(const smmc_engine *e, const smmc_sim *sim, const smmc_portfoli
     return host_fail(SMMC_ERR_INVALID, "weights[%u] is %g: series %u is inflation and is not held, its weight must be 0", K,
                      static_cast<double>(pf->weights[K]), K);
   return smmc::cashflow_check_schedule(sim, cf);
-}
-
-int check_outputs(const smmc_real_cashflow_outputs *out) {
-  if (!out) return host_fail(SMMC_ERR_INVALID, "the smmc_real_cashflow_outputs argument is NULL");
-  if (out->struct_size != sizeof(smmc_real_cashflow_outputs))
-    return host_fail(SMMC_ERR_INVALID, "smmc_real_cashflow_outputs.struct_size is %u, this library expects %zu", out->struct_size,
-                     sizeof(smmc_real_cashflow_outputs));
-  if (out->reserved != 0) return host_fail(SMMC_ERR_INVALID, "smmc_real_cashflow_outputs.reserved is %u, it must be 0", out->reserved);
-  return SMMC_OK;
 }
 
 // The rule of include/smmc.h (smmc_engine_real_cashflow_divide_kind); DESIGN.md, "Real cash flows", has the proof.
@@ -103,10 +89,10 @@ int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio 
 
   // the flows: contributions only -- every real amount <= 0, so every nominal one fl(amount * I) <= 0 -- and no fraction
   double paid_in = 0.0;
-  for (uint32_t t = 0; t < (varying(cf) ? P : 1u); ++t) {
+  for (uint32_t t = 0; t < (cashflow_varying(cf) ? P : 1u); ++t) {
     const double am = cf->amounts ? cf->amounts[t] : cf->amount, fr = cf->fractions ? cf->fractions[t] : cf->fraction;
     if (fr != 0.0 || !(am <= 0.0)) return SMMC_DIV_EXACT;
-    paid_in += std::fabs(am) * (varying(cf) ? 1.0 : p);
+    paid_in += std::fabs(am) * (cashflow_varying(cf) ? 1.0 : p);
   }
   paid_in *= std::pow(std::max(1.0, hi_i / 100.0), p);  // no nominal amount exceeds |amount| max(1, hi_I)^P
   // above: the sum of the holdings grows by the best asset's factor and by the nominal amount per period
@@ -159,58 +145,27 @@ int smmc_engine_simulate_real_cashflow(smmc_engine *e, const smmc_sim *sim, cons
   smmc_portfolio law;
   int rc = check_request(e, sim, pf, cf, &law);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_real_cashflow_outputs");
   if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(out->d_final) | reinterpret_cast<uintptr_t>(out->d_final_real) | reinterpret_cast<uintptr_t>(out->d_index) |
-       reinterpret_cast<uintptr_t>(out->d_holdings) | reinterpret_cast<uintptr_t>(out->d_paid) |
-       reinterpret_cast<uintptr_t>(out->d_ruin_period)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "d_final, d_final_real, d_index, d_holdings, d_paid and d_ruin_period must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->d_stats) | reinterpret_cast<uintptr_t>(out->d_depleted_at)) & 7u)
-    return host_fail(SMMC_ERR_INVALID, "d_stats and d_depleted_at must be 8-byte aligned");
+  rc = smmc::host_check_depletion_alignment(out, smmc::host_misaligned({out->d_final_real, out->d_index}, 4),
+                                            "d_final, d_final_real, d_index, d_holdings, d_paid and d_ruin_period must be 4-byte aligned");
+  if (rc) return rc;
   Plan pl;
   rc = plan(e, sim, &law, cf, out->d_stats != nullptr, &pl);
   if (rc) return rc;
-  const smmc::EngineView view = smmc::engine_view(e);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
-  smmc::KernelArgs &a = pl.a;
   smmc::CashflowArgs &c = pl.x.c;
-  a.d_final = out->d_final;
+  pl.a.d_final = out->d_final;
   pl.x.d_final_real = out->d_final_real;
   pl.x.d_index = out->d_index;
   pl.x.p.d_holdings = out->d_holdings;
   c.d_paid = out->d_paid;
   c.d_ruin_period = out->d_ruin_period;
-  if (varying(cf) && pl.grid) {
-    rc = smmc::cashflow_stage_schedule(e, sim, cf, &c);
-    if (rc) return rc;
-  }
-  smmc::ZeroLease lease;
-  if ((out->d_stats && sim->n_bins) || out->d_depleted_at) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_lease(e, &lease);
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (out->d_stats) {
-    a.partials = view.d_partials;
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (out->d_depleted_at) c.d_depleted = acc + kDepletedAt;
-  if (pl.grid) {
-    const bool exact_div = divide_rule(e, sim, &law, cf) != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_real_cashflow",
-                                 [&] { return smmc::launch_real_cashflow(a, pl.x, exact_div, pl.grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (out->d_stats)
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, pl.grid, static_cast<smmc_stats *>(out->d_stats), sim->n_bins, view.stream,
-                                   sim->n_bins ? acc : nullptr, sim->n_bins ? 1u : 0u));
-  if (out->d_depleted_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, sim->n_periods + 1u,
-                                            reinterpret_cast<unsigned long long *>(out->d_depleted_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const bool exact_div = pl.grid && divide_rule(e, sim, &law, cf) != SMMC_DIV_FAST;
+  const smmc::WaveWalk walk = {"launch_real_cashflow", pl.grid, sim->n_bins, {{out->d_stats, 0, 0, &pl.a.partials, &pl.a.d_hist}},
+                               {{out->d_depleted_at, smmc::kDepletedAt, sim->n_periods + 1u, &c.d_depleted}}};
+  return smmc::host_wave_walk_run(
+      e, walk, smmc::FoldRecord(), [&](hipStream_t stream) { return smmc::launch_real_cashflow(pl.a, pl.x, exact_div, pl.grid, stream); },
+      [&] { return cashflow_varying(cf) && pl.grid ? smmc::cashflow_stage_schedule(e, sim, cf, &c) : SMMC_OK; });
 }
 
 int smmc_engine_simulate_real_cashflow_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf,
@@ -218,7 +173,7 @@ int smmc_engine_simulate_real_cashflow_to_host(smmc_engine *e, const smmc_sim *s
   smmc_portfolio law;
   int rc = check_request(e, sim, pf, cf, &law);
   if (rc) return rc;
-  rc = check_outputs(out);
+  rc = smmc::host_check_outputs(out, "smmc_real_cashflow_outputs");
   if (rc) return rc;
   Plan pl;  // refuse before anything is allocated
   rc = plan(e, sim, &law, cf, out->d_stats != nullptr, &pl);
@@ -226,27 +181,18 @@ int smmc_engine_simulate_real_cashflow_to_host(smmc_engine *e, const smmc_sim *s
   const smmc::EngineView view = smmc::engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
+  typedef smmc_real_cashflow_outputs O;
   const size_t per_path = sizeof(float) * sim->n_paths;
-  const smmc::HostPiece pieces[8] = {{out->d_stats, static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
-                                     {out->d_depleted_at, sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u)},
-                                     {out->d_final, per_path},
-                                     {out->d_final_real, per_path},
-                                     {out->d_index, per_path},
-                                     {out->d_holdings, per_path * pf->n_assets},
-                                     {out->d_paid, per_path},
-                                     {out->d_ruin_period, per_path}};
-  return smmc::host_outputs_to_host(e, "simulate_real_cashflow_to_host", pieces, 8, [&](void *const *dev) {
-    smmc_real_cashflow_outputs d = *out;
-    d.d_stats = dev[0];
-    d.d_depleted_at = static_cast<uint64_t *>(dev[1]);
-    d.d_final = static_cast<float *>(dev[2]);
-    d.d_final_real = static_cast<float *>(dev[3]);
-    d.d_index = static_cast<float *>(dev[4]);
-    d.d_holdings = static_cast<float *>(dev[5]);
-    d.d_paid = static_cast<float *>(dev[6]);
-    d.d_ruin_period = static_cast<uint32_t *>(dev[7]);
-    return smmc_engine_simulate_real_cashflow(e, sim, pf, cf, &d);
-  });
+  const smmc::OutputField fields[8] = {{offsetof(O, d_stats), static_cast<size_t>(smmc_stats_bytes(sim->n_bins))},
+                                       {offsetof(O, d_depleted_at), sizeof(uint64_t) * (static_cast<size_t>(sim->n_periods) + 1u)},
+                                       {offsetof(O, d_final), per_path},
+                                       {offsetof(O, d_final_real), per_path},
+                                       {offsetof(O, d_index), per_path},
+                                       {offsetof(O, d_holdings), per_path * pf->n_assets},
+                                       {offsetof(O, d_paid), per_path},
+                                       {offsetof(O, d_ruin_period), per_path}};
+  return smmc::host_outputs_struct_to_host(e, "simulate_real_cashflow_to_host", *out, fields,
+                                           [&](const O *d) { return smmc_engine_simulate_real_cashflow(e, sim, pf, cf, d); });
 }
 
 }  // extern "C"

@@ -3,8 +3,9 @@
 //
 // A translation unit of its own, like smmc_cashflow.cpp: smmc_capi.cpp and smmc_cashflow.cpp never call into this
 // file.  A scenario's argument checks and its divide are smmc_engine_cashflow_divide_kind's -- the rule is stated
-// once, in smmc_cashflow.cpp -- and the launch is a wave walk on the shared host side (host_wave_walk_grid,
-// host_make_args, engine_acc_lease, host_timed_launch, host_outputs_to_host).  The scenarios travel as kernel
+// once, in smmc_cashflow.cpp -- and the launch is a wave walk whose run is the shared one (smmc_host.h,
+// host_wave_walk_run, with the per-scenario fold).  What is this unit's own: the checks across scenarios, the counter
+// cap, the padding to the kernel's widths, the LDS need and the kernel arguments.  The scenarios travel as kernel
 // arguments: nothing is staged, the unit keeps no state per engine.
 #include <hip/hip_runtime_api.h>
 
@@ -12,7 +13,6 @@
 #include <cstring>
 
 #include "smmc_host.h"
-#include "smmc_internal.h"
 
 namespace {
 
@@ -22,11 +22,6 @@ using smmc::host_fail;
 // Workgroups per CU, as cashflow_kernel; a workgroup leaves one partial per scenario in the engine's max_grid
 // partials, so the grid is capped at max_grid / sweep_width as well.
 constexpr uint32_t kSweepGroupsPerCU = 32;
-// The engine's accumulator: [scenario][bucket] from 0, [scenario][period] from kDepletedAt.
-constexpr size_t kDepletedAt = SMMC_MAX_SWEEP_COUNTERS;
-static_assert(2u * SMMC_MAX_SWEEP_COUNTERS <= static_cast<size_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
-              "the engine's accumulator holds a sweep's buckets and depletion counters");
-
 // The checks that need no output pointer; *kind: SMMC_DIV_FAST iff every scenario's own rule says so.
 int check_sweep(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenarios, uint32_t n_scenarios, int *kind) {
   int rc = smmc::host_check_sim(e, sim);
@@ -44,14 +39,6 @@ int check_sweep(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenar
     if (one < 0) return one;
     if (one != SMMC_DIV_FAST) *kind = SMMC_DIV_EXACT;
   }
-  return SMMC_OK;
-}
-
-int check_outputs(const void *fin, const void *paid, const void *ruin, const void *stats, const void *dep) {
-  if ((reinterpret_cast<uintptr_t>(fin) | reinterpret_cast<uintptr_t>(paid) | reinterpret_cast<uintptr_t>(ruin)) & 3u)
-    return host_fail(SMMC_ERR_INVALID, "the final-value, paid and ruin-period pointers must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(dep)) & 7u)
-    return host_fail(SMMC_ERR_INVALID, "the statistics and depletion-count pointers must be 8-byte aligned");
   return SMMC_OK;
 }
 
@@ -81,7 +68,7 @@ int smmc_engine_simulate_cashflow_sweep(smmc_engine *e, const smmc_sim *sim, con
   if (rc) return rc;
   rc = check_counters(sim, n_scenarios, d_stats != nullptr);
   if (rc) return rc;
-  rc = check_outputs(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
+  rc = smmc::cashflow_check_pointers(d_final, d_paid, d_ruin_period, d_stats, d_depleted_at);
   if (rc) return rc;
   const smmc::EngineView view = smmc::engine_view(e);
   const uint32_t width = smmc::sweep_width(n_scenarios);
@@ -95,9 +82,6 @@ int smmc_engine_simulate_cashflow_sweep(smmc_engine *e, const smmc_sim *sim, con
   if (lds + 2048 > view.max_lds)
     return host_fail(SMMC_ERR_INVALID, "table, the scenarios' depletion counters and histograms need %zu bytes of LDS, device allows %zu",
                      lds, view.max_lds);
-  DeviceGuard guard(view.device);
-  if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
-
   smmc::SweepArgs c;
   std::memset(&c, 0, sizeof c);
   c.n = n_scenarios;
@@ -110,29 +94,12 @@ int smmc_engine_simulate_cashflow_sweep(smmc_engine *e, const smmc_sim *sim, con
   c.d_paid = d_paid;
   c.d_ruin_period = d_ruin_period;
   a.d_final = d_final;
-  smmc::ZeroLease lease;
-  if ((d_stats && sim->n_bins) || d_depleted_at) {  // zero now, and zero again after the finalize launches below
-    rc = smmc::engine_acc_lease(e, &lease);
-    if (rc) return rc;
-  }
-  unsigned long long *const acc = lease.acc();
-  if (d_stats) {
-    a.partials = view.d_partials;  // [scenario][grid]
-    a.d_hist = sim->n_bins ? acc : nullptr;
-  }
-  if (d_depleted_at) c.d_depleted = acc + kDepletedAt;
-  if (grid) {
-    const bool exact_div = kind != SMMC_DIV_FAST;
-    rc = smmc::host_timed_launch(e, "launch_cashflow_sweep", [&] { return smmc::launch_cashflow_sweep(a, c, exact_div, grid, view.stream); });
-    if (rc) return rc;
-  }
-  if (d_stats)
-    SMMC_HIP(smmc::launch_finalize_sweep(view.d_partials, grid, n_scenarios, d_stats, sim->n_bins, sim->n_bins ? acc : nullptr, view.stream));
-  if (d_depleted_at)
-    SMMC_HIP(smmc::launch_finalize_depleted(acc + kDepletedAt, n_scenarios * (sim->n_periods + 1u),
-                                            reinterpret_cast<unsigned long long *>(d_depleted_at), view.stream));
-  lease.finalize_queued();
-  return SMMC_OK;
+  const bool exact_div = kind != SMMC_DIV_FAST;
+  // a.partials: [scenario][grid]
+  const smmc::WaveWalk walk = {"launch_cashflow_sweep", grid, sim->n_bins, {{d_stats, 0, 0, &a.partials, &a.d_hist}},
+                               {{d_depleted_at, smmc::kSweepDepletedAt, n_scenarios * (sim->n_periods + 1u), &c.d_depleted}}};
+  return smmc::host_wave_walk_run(e, walk, smmc::FoldScenarios{n_scenarios},
+                                  [&](hipStream_t stream) { return smmc::launch_cashflow_sweep(a, c, exact_div, grid, stream); });
 }
 
 int smmc_engine_simulate_cashflow_sweep_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *scenarios,
