@@ -591,6 +591,43 @@ int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_s
 int smmc_engine_portfolio_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                const smmc_cashflow *cf);
 
+/* ---- portfolio cash-flow checkpoints: the value distribution along a plan ----------------------- */
+
+/* "What does my wealth look like in year 5, 10, 15 ... under this plan": smmc_engine_simulate_portfolio_cashflow with
+ * the paths' values reduced also after n_checkpoints chosen periods, one launch (the fan chart of a plan).  Neither
+ * keepdata (no cash flows; 4 (n_periods + 1) bytes per path) nor two separate calls can give this.
+ * The path: exactly the path of smmc_engine_simulate_portfolio_cashflow for the same (sim, pf, cf) -- recurrence,
+ * draws, masks and roundings are that contract's.  The value of a path at period p is v after period p's step: vn
+ * while the path is live, 0 from the period of its depletion on.
+ * periods[0 .. n_checkpoints): HOST array, strictly increasing, 1 <= periods[k] <= sim->n_periods, 1 <= n_checkpoints <=
+ * SMMC_MAX_CHECKPOINTS; may be reused on return.
+ * d_records (required, DEVICE, 8-byte aligned): n_checkpoints packed records back to back, smmc_stats_bytes(sim->n_bins)
+ * bytes each; record k is what smmc_engine_values_stats would write for the paths' values at periods[k] with sim's
+ * below_threshold, n_bins, hist_lo and hist_hi: integer fields, min, max and bucket counts exactly, sum and sumsq as
+ * double sums in a fixed order (two identical calls give the same bytes; no floating-point atomics).  Depleted paths are
+ * in every record, as the value 0.  n_bins == 0 is allowed (records without buckets).
+ * out: every member keeps the meaning it has in smmc_engine_simulate_portfolio_cashflow, may be NULL, and is
+ * bit-identical to what that call writes for the same request; of d_stats the integer fields, min, max and bucket counts
+ * are identical and sum and sumsq agree within relative 1e-12.
+ * Divide: smmc_engine_portfolio_cashflow_divide_kind(e, sim, pf, cf) answers for this call too -- a value already has to
+ * be right whenever it meets the floor, so a checkpoint asks nothing more, and SMMC_DIV_CHECKED never applies.
+ * Shards merge with smmc_stats_merge per record and by adding d_depleted_at.  n_paths == 0 launches nothing and yields
+ * empty records, the empty final record and zero counts.
+ * SMMC_ERR_INVALID with a text and without a launch: everything smmc_engine_simulate_portfolio_cashflow refuses;
+ * n_checkpoints == 0 or > SMMC_MAX_CHECKPOINTS; a period that is 0, above n_periods or not above the one before it; NULL
+ * periods or d_records; a d_records that is not 8-byte aligned; n_checkpoints * n_bins > SMMC_MAX_CHECKPOINT_BINS; asset
+ * table (or draw tables), n_periods + 1 depletion counters, n_bins final buckets, n_checkpoints * n_bins checkpoint
+ * buckets and the waves' partials beyond the device's LDS less 2048 bytes (the text names both numbers).
+ * Asynchronous on the engine stream. */
+int smmc_engine_simulate_portfolio_cashflow_checkpoints(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                        const smmc_cashflow *cf, const uint32_t *periods, uint32_t n_checkpoints,
+                                                        const smmc_portfolio_cashflow_outputs *out, void *d_records);
+/* Synchronous convenience: the same with HOST pointers in out and for the records (no alignment asked of them). */
+int smmc_engine_simulate_portfolio_cashflow_checkpoints_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                                const smmc_cashflow *cf, const uint32_t *periods,
+                                                                uint32_t n_checkpoints,
+                                                                const smmc_portfolio_cashflow_outputs *out, void *host_records);
+
 /* ---- allocation sweeps: up to eight portfolio strategies on one set of draws, one launch ------- */
 
 /* "Which mix, rebalanced how often, still carries this withdrawal?": n_scenarios (1 .. SMMC_MAX_SWEEP) strategies

@@ -834,10 +834,12 @@ constexpr uint32_t kCheckpointGroupsPerCU = 32;
 static_assert(static_cast<uint64_t>(SMMC_MAX_CHECKPOINT_BINS) <= static_cast<uint64_t>(smmc::kHistSpread) * SMMC_MAX_BINS,
               "the engine's bucket accumulator holds a checkpoint launch's counters");
 
-static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints,
-                             const void *final_ptr, const void *records) {
-  int rc = check_sim(e, sim);
-  if (rc) return rc;
+}  // extern "C"
+
+// smmc_host.h: lent to the units whose entries take checkpoints too
+int smmc::host_check_checkpoint_args(const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints, const void *final_ptr,
+                                     const void *records) {
+  int rc;
   if (!periods) return fail(SMMC_ERR_INVALID, "periods is NULL");
   if (!records) return fail(SMMC_ERR_INVALID, "the records pointer is NULL");
   if (n_checkpoints == 0) return fail(SMMC_ERR_INVALID, "n_checkpoints is 0");
@@ -858,6 +860,17 @@ static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const ui
                 sim->n_bins, SMMC_MAX_CHECKPOINT_BINS);
   if (reinterpret_cast<uintptr_t>(final_ptr) & 3u) return fail(SMMC_ERR_INVALID, "the final-value pointer must be 4-byte aligned");
   if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(SMMC_ERR_INVALID, "the records pointer must be 8-byte aligned");
+  return SMMC_OK;
+}
+
+extern "C" {
+
+static int check_checkpoints(const smmc_engine *e, const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints,
+                             const void *final_ptr, const void *records) {
+  int rc = check_sim(e, sim);
+  if (rc) return rc;
+  rc = smmc::host_check_checkpoint_args(sim, periods, n_checkpoints, final_ptr, records);
+  if (rc) return rc;
   if (!smmc::launch_checkpoints || !smmc::launch_finalize_checkpoints || !smmc::checkpoints_lds_bytes)
     return fail(SMMC_ERR_HIP, "this build carries no checkpoint kernel");
   return SMMC_OK;

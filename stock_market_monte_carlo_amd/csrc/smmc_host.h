@@ -110,6 +110,12 @@ int engine_acc_lease(smmc_engine *e, ZeroLease *lease);
 constexpr size_t kDepletedAt = SMMC_MAX_BINS;
 static_assert(kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= static_cast<size_t>(kHistSpread) * SMMC_MAX_BINS,
               "the engine's accumulator holds the histogram and the depletion counters");
+// One scenario with checkpoints (smmc_portfolio_cashflow_checkpoints.cpp): a third region behind those two, the
+// checkpoints' buckets [checkpoint][bucket].
+constexpr size_t kCheckpointBucketsAt = kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1;
+static_assert(SMMC_MAX_BINS <= kDepletedAt && kDepletedAt + SMMC_MAX_CASHFLOW_PERIODS + 1 <= kCheckpointBucketsAt &&
+                  kCheckpointBucketsAt + SMMC_MAX_CHECKPOINT_BINS <= static_cast<size_t>(kHistSpread) * SMMC_MAX_BINS,
+              "the engine's accumulator holds the final buckets, the depletion counters and the checkpoints' buckets side by side");
 constexpr size_t kSweepDepletedAt = SMMC_MAX_SWEEP_COUNTERS;
 static_assert(2u * SMMC_MAX_SWEEP_COUNTERS <= static_cast<size_t>(kHistSpread) * SMMC_MAX_BINS,
               "the engine's accumulator holds a sweep's buckets and depletion counters");
@@ -186,6 +192,10 @@ int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *piec
   return host_outputs_to_host(e, what, pieces, n_pieces, [](void *const *dev, void *f) { return (*static_cast<F *>(f))(dev); }, &run);
 }
 int host_check_sim(const smmc_engine *e, const smmc_sim *s);
+// What smmc_engine_simulate_checkpoints refuses about periods, n_checkpoints, the records pointer, the stream flags and
+// n_checkpoints * n_bins, with its texts, for a checked sim; final_ptr (may be null): its 4-byte alignment.
+int host_check_checkpoint_args(const smmc_sim *sim, const uint32_t *periods, uint32_t n_checkpoints, const void *final_ptr,
+                               const void *records);
 // bounds on a = 100 + r of one period; false if there are none (smmc_capi.cpp, divide_kind)
 bool host_multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, double *hi_a);
 KernelArgs host_make_args(const smmc_engine *e, const smmc_sim *s);
@@ -265,12 +275,21 @@ struct WalkCounts {  // a count array of the launch (depletion, first passage); 
   uint32_t n;
   unsigned long long **d_counts;  // the kernel argument that gets them
 };
+struct WalkRecordSet {  // n packed records that the launch leaves beside `records`, folded by a fold of their own (checkpoints);
+  void *d_records;                // d_records null: none.  device: where that fold writes them
+  uint32_t n;
+  BlockPartial *partials_mem;     // their partials [record][workgroup], n x grid entries in an array of the ENTRY's own
+  size_t hist_at;                 // their bucket counts [record][bucket] in the engine's accumulator
+  BlockPartial **partials;        // the kernel arguments that get the two
+  unsigned long long **d_hist;
+};
 struct WaveWalk {
   const char *name;  // of the launch, as host_timed_launch reports its failure
   uint32_t grid;     // workgroups; 0 (no paths): nothing is launched, the folds still write the empty outputs
   uint32_t n_bins;   // smmc_sim::n_bins of the request
   WalkRecord records[2];
   WalkCounts counts[2];
+  WalkRecordSet set = {};  // most entries leave none
 };
 // How a record is folded: one record (launch_finalize), or the packed records of n scenarios whose partials and
 // buckets lie [scenario][...] from the record's offsets (launch_finalize_sweep).  A type each, so that a unit refers to
@@ -288,6 +307,15 @@ struct FoldScenarios {
     return launch_finalize_sweep(partials, grid, n, d_stats, n_bins, hist, stream);
   }
 };
+// How WaveWalk::set is folded: not at all (an entry without one), or as checkpoints (launch_finalize_checkpoints).
+struct NoRecordSet {
+  hipError_t operator()(const WalkRecordSet &, uint32_t, uint32_t, unsigned long long *, hipStream_t) const { return hipSuccess; }
+};
+struct FoldCheckpointSet {
+  hipError_t operator()(const WalkRecordSet &s, uint32_t grid, uint32_t n_bins, unsigned long long *hist, hipStream_t stream) const {
+    return launch_finalize_checkpoints(s.partials_mem, grid, s.n, s.d_records, n_bins, hist, stream);
+  }
+};
 struct NoPrepare {
   int operator()() const { return SMMC_OK; }
 };
@@ -295,14 +323,14 @@ struct NoPrepare {
 // lease on the accumulator if a histogram or a count array will be counted -- zero now, and zero again after the folds;
 // the kernel arguments wired; launch(stream) unless the grid is empty; the records folded, then the count arrays; and
 // only with all folds in the queue the lease's mark comes off.  Any error return in between leaves the accumulator dirty.
-template <typename Fold, typename Launch, typename Prepare = NoPrepare>
-int host_wave_walk_run(smmc_engine *e, const WaveWalk &w, Fold fold, Launch launch, Prepare prepare = Prepare()) {
+template <typename Fold, typename Launch, typename Prepare = NoPrepare, typename FoldSet = NoRecordSet>
+int host_wave_walk_run(smmc_engine *e, const WaveWalk &w, Fold fold, Launch launch, Prepare prepare = Prepare(), FoldSet fold_set = FoldSet()) {
   const EngineView view = engine_view(e);
   DeviceGuard guard(view.device);
   if (!guard.ok) return host_fail(SMMC_ERR_HIP, "hipSetDevice(%d) failed", view.device);
   int rc = prepare();
   if (rc) return rc;
-  bool counted = false;
+  bool counted = w.set.d_records && w.n_bins;
   for (const WalkRecord &r : w.records) counted = counted || (r.d_stats && w.n_bins);
   for (const WalkCounts &c : w.counts) counted = counted || c.d_out;
   ZeroLease lease;
@@ -318,6 +346,10 @@ int host_wave_walk_run(smmc_engine *e, const WaveWalk &w, Fold fold, Launch laun
     }
   for (const WalkCounts &c : w.counts)
     if (c.d_out) *c.d_counts = acc + c.acc_at;
+  if (w.set.d_records) {
+    *w.set.partials = w.set.partials_mem;
+    *w.set.d_hist = w.n_bins ? acc + w.set.hist_at : nullptr;
+  }
   if (w.grid) {
     rc = host_timed_launch(e, w.name, [&] { return launch(view.stream); });
     if (rc) return rc;
@@ -325,6 +357,7 @@ int host_wave_walk_run(smmc_engine *e, const WaveWalk &w, Fold fold, Launch laun
   for (const WalkRecord &r : w.records)
     if (r.d_stats)
       SMMC_HIP(fold(view.d_partials + r.partials_at, w.grid, r.d_stats, w.n_bins, w.n_bins ? acc + r.hist_at : nullptr, view.stream));
+  if (w.set.d_records) SMMC_HIP(fold_set(w.set, w.grid, w.n_bins, w.n_bins ? acc + w.set.hist_at : nullptr, view.stream));
   for (const WalkCounts &c : w.counts)
     if (c.d_out) SMMC_HIP(launch_finalize_depleted(acc + c.acc_at, c.n, reinterpret_cast<unsigned long long *>(c.d_out), view.stream));
   lease.finalize_queued();

@@ -243,6 +243,25 @@ struct PortfolioCashflowArgs {
 hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
                                      hipStream_t stream);
 size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// portfolio_cashflow_checkpoints_kernel (smmc_engine_simulate_portfolio_cashflow_checkpoints,
+// csrc/smmc_portfolio_cashflow_checkpoints.cpp; counter stream v3 only): portfolio_cashflow_kernel's paths, with the
+// record of their values after each of n chosen periods ("Portfolio cash-flow checkpoints").  p, c, a.partials,
+// a.d_hist and c.d_depleted as launch_portfolio_cashflow; a.n_bins applies to the final record and to every checkpoint's.
+struct PortfolioCashflowCheckpointsArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  uint32_t n;                              // 1 .. SMMC_MAX_CHECKPOINTS
+  uint32_t periods[SMMC_MAX_CHECKPOINTS];  // strictly increasing, 1 .. n_periods; entries from n on: 0xffffffff
+  BlockPartial *ck_partials;               // n x grid entries, [checkpoint][workgroup]
+  unsigned long long *d_ck_hist;           // n x a.n_bins counters, zero before the launch; nullable when a.n_bins == 0
+};
+// launch_finalize_checkpoints folds x.ck_partials and x.d_ck_hist into the n packed records, launch_finalize the final one.
+hipError_t launch_portfolio_cashflow_checkpoints(const KernelArgs &a, const PortfolioCashflowCheckpointsArgs &x, bool exact_div,
+                                                 uint32_t grid, hipStream_t stream);
+// [front: the padded rows or the draw tables, later the waves' checkpoint partials][n_periods + 1 depletion counters]
+// [n_bins final buckets][n_checkpoints x n_bins checkpoint buckets][pad][the waves' partials of the final record]
+size_t portfolio_cashflow_checkpoints_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins,
+                                                uint32_t n_checkpoints);
 // real_cashflow_kernel (smmc_engine_simulate_real_cashflow, csrc/smmc_real_cashflow.cpp; counter stream v3 only):
 // portfolio_cashflow_kernel's step with the schedule's amounts and floor in money of period 0, indexed by a price index
 // that the LAST series of the joint law compounds ("Real cash flows").  p is the law as launch_portfolio

@@ -2645,6 +2645,133 @@ void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods ---------------
+//
+// smmc_engine_simulate_portfolio_cashflow_checkpoints (csrc/smmc_portfolio_cashflow_checkpoints.cpp; include/smmc.h and
+// DESIGN.md, "Portfolio cash-flow checkpoints", state the contract): portfolio_cashflow_kernel's path -- the same draws,
+// the same portfolio_cashflow_step, called, not restated -- with checkpoints_kernel's records of `v` after chosen
+// periods.  A family of its own: portfolio_cashflow_kernel compiles to what it compiled to before.
+//
+// Where the checkpoint test sits.  The sorted periods are kernel arguments read with scalar loads, `next_p`, the next
+// one, lives in an SGPR, and the period index t is wave-uniform, so the test is ONE scalar compare and branch per
+// period behind the step (checkpoints_kernel tests once per Philox block and pays with a second copy of the block that
+// keeps the prefix values; here v is in its register after every step anyway, and a second copy of the unrolled steps
+// would double the loop's code).  A period that is no checkpoint runs the parent's vector instructions and no other.
+// A record (checkpoint_record) is taken for every lane of the chunk with `active` as its mask; a depleted lane
+// contributes its 0.
+//
+// What persists over a wave's trips: lane k's CheckpointAcc, the LaneRecord of the final values, the LDS counters.
+// Per path: `until`, `ck` and `next_p` start again, and the schedule is read from its first entry (blk = 0).
+//
+// LDS, stated once more on the host side (portfolio_cashflow_checkpoints_lds_bytes):
+//   [front: the asset table or the v3 draw tables at address 0; after the walk and a barrier the waves' checkpoint
+//           partials [kW][x.n] -- checkpoint_front_words() reserves the larger of the two]
+//   [n_periods + 1 depletion counters][n_bins final buckets][x.n][n_bins] checkpoint buckets]   (u32, zeroed by walk_setup)
+//   [pad to 8 bytes][kW BlockPartial: the waves' LaneRecord partials]
+template <int kMode, bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void portfolio_cashflow_checkpoints_kernel(const KernelArgs k, const PortfolioCashflowCheckpointsArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const uint32_t n_at = k.n_periods + 1u, ck_words = x.n * k.n_bins;
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, checkpoint_front_words(walk_table_words<kMode>(staged), kW, x.n),
+                                      n_at + k.n_bins + ck_words);
+  uint32_t *lds_dep = s.counters;          // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + n_at;     // [n_bins]
+  uint32_t *lds_ck = lds_hist + k.n_bins;  // [x.n][n_bins]
+  const uint32_t lane = s.lane, wave = s.wave;
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  CheckpointAcc acc;
+  acc.sum = acc.sumsq = 0.0;
+  acc.count = acc.below = acc.under = acc.over = 0u;
+  acc.min = __builtin_inff();
+  acc.max = -__builtin_inff();
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    uint32_t ck = 0u, next_p = x.periods[0];  // uniform: the next checkpoint and its period
+    float a[kDraws][K];
+    float am[kDraws], fr[kDraws];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) {
+#pragma unroll
+          for (int j = 0; j < kDraws; ++j) {  // the block's schedule entries (padded to whole blocks)
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+          portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a);
+        },
+        [&](int j, uint32_t t) {
+          portfolio_cashflow_step<kExactDiv, K>(a[j], p.weights, am[j], fr[j], c.floor, every, k.n_periods, t, h, v, paid, ruin, alive,
+                                                until);
+          if (t == next_p) {  // uniform; ck < x.n here: next_p is 0xffffffff once none is left
+            checkpoint_record(k, ck, v, active, lane, lds_ck, acc);
+            ++ck;
+            next_p = ck < x.n ? x.periods[ck] : 0xffffffffu;
+          }
+        });
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // every wave is through with the draw tables; the waves' partials are written, their LDS adds complete
+  BlockPartial *part = reinterpret_cast<BlockPartial *>(lds_raw);  // [kW][x.n], over the tables
+  if (lane < x.n) {
+    BlockPartial q;
+    q.sum = acc.sum;
+    q.sumsq = acc.sumsq;
+    q.count = acc.count;
+    q.below = acc.below;
+    q.underflow = acc.under;
+    q.overflow = acc.over;
+    q.min = acc.min;
+    q.max = acc.max;
+    part[wave * x.n + lane] = q;
+  }
+  __syncthreads();
+  if (threadIdx.x < x.n) {  // thread k: checkpoint k's partials in wave order
+    BlockPartial t = part[threadIdx.x];
+    for (uint32_t w = 1; w < kW; ++w) partial_add(t, part[w * x.n + threadIdx.x]);
+    x.ck_partials[static_cast<size_t>(threadIdx.x) * gridDim.x + blockIdx.x] = t;
+  }
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, n_at, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+  if (ck_words) flush_counters<kGroup>(lds_ck, ck_words, x.d_ck_hist);
+}
+
 // ---- real cash flows: the schedule in money of period 0, indexed by a jointly drawn inflation series ----
 //
 // smmc_engine_simulate_real_cashflow (csrc/smmc_real_cashflow.cpp; include/smmc.h and DESIGN.md, "Real cash flows",
@@ -2942,7 +3069,19 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_KERNELS
-#define SMMC_REAL_CASHFLOW_KERNELS(K, V)                                                                                     \
+#define SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(K, V)                                                                   \
+  reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),             \
+      reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),          \
+      reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_TABLE, false, true, K, V>),             \
+      reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_TABLE, true, true, K, V>),              \
+      reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_TABLE, false, false, K, V>),            \
+      reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_TABLE, true, false, K, V>)
+      SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(1, false), SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(2, false),
+      SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(3, false), SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(4, false),
+      SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(2, true),
+      SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(4, true),
+#undef SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS
+#define SMMC_REAL_CASHFLOW_KERNELS(K, V)                                                                                    \
   reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),                              \
       reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),                           \
       reinterpret_cast<const void *>(real_cashflow_kernel<SMMC_MODE_TABLE, false, true, K, V>),                              \
@@ -3379,6 +3518,51 @@ hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflo
   if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
   return launch_wave_walk<PortfolioCashflowFamily>(
       a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
+}
+
+// ---- portfolio cash-flow checkpoints ----
+
+size_t portfolio_cashflow_checkpoints_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins,
+                                                uint32_t n_checkpoints) {
+  // the kernel's layout: [front: the padded rows or the draw tables, later the checkpoint partials [waves][n_checkpoints]]
+  // [depletion [n_periods + 1]][final buckets [n_bins]][checkpoint buckets [n_checkpoints][n_bins]][pad to 8 bytes]
+  // [one LaneRecord partial per wave]
+  const bool table = mode == SMMC_MODE_TABLE;
+  const uint32_t waves = walk_waves(table ? SMMC_MODE_TABLE : SMMC_MODE_GAUSSIAN);
+  const uint32_t front = checkpoint_front_words(table ? n_rows * portfolio_row_words(n_assets) : bm_lds_words(SMMC_MODE_GAUSSIAN), waves, n_checkpoints);
+  const size_t counters = static_cast<size_t>(n_periods) + 1u + n_bins + static_cast<size_t>(n_checkpoints) * n_bins;
+  return ((front + counters + 1u) & ~static_cast<size_t>(1)) * 4u + waves * sizeof(BlockPartial);
+}
+
+struct PortfolioCashflowCheckpointsFamily {
+  template <int kMode, bool kExactDiv, bool kDense, int K>
+  static WalkKernel<PortfolioCashflowCheckpointsArgs> schedule(const PortfolioCashflowCheckpointsArgs &x) {
+    return x.c.schedule ? portfolio_cashflow_checkpoints_kernel<kMode, kExactDiv, kDense, K, true>
+                        : portfolio_cashflow_checkpoints_kernel<kMode, kExactDiv, kDense, K, false>;
+  }
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<PortfolioCashflowCheckpointsArgs> get(const PortfolioCashflowCheckpointsArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return schedule<kMode, kExactDiv, kDense, 1>(x);
+      case 2: return schedule<kMode, kExactDiv, kDense, 2>(x);
+      case 3: return schedule<kMode, kExactDiv, kDense, 3>(x);
+      default: return schedule<kMode, kExactDiv, kDense, 4>(x);
+    }
+  }
+};
+// The entries of x.periods from x.n on must be 0xffffffff.
+hipError_t launch_portfolio_cashflow_checkpoints(const KernelArgs &a, const PortfolioCashflowCheckpointsArgs &x, bool exact_div, uint32_t grid,
+                                                 hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
+  if (x.n < 1 || x.n > SMMC_MAX_CHECKPOINTS || !x.ck_partials) return hipErrorInvalidValue;
+  if (static_cast<uint64_t>(x.n) * a.n_bins > SMMC_MAX_CHECKPOINT_BINS || (a.n_bins && !x.d_ck_hist)) return hipErrorInvalidValue;
+  for (uint32_t i = 0; i < x.n; ++i)  // every record is of a period the walk reaches, in the order it reaches them
+    if (x.periods[i] < 1 || x.periods[i] > a.n_periods || (i && x.periods[i] <= x.periods[i - 1])) return hipErrorInvalidValue;
+  return launch_wave_walk<PortfolioCashflowCheckpointsFamily>(
+      a, x, exact_div, grid, portfolio_cashflow_checkpoints_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins, x.n), stream);
 }
 
 // ---- real cash flows ----

@@ -261,6 +261,29 @@ class PortfolioCashflowResult(CashflowResult):
 
 
 @dataclasses.dataclass
+class PortfolioCashflowCheckpointsResult(PortfolioCashflowResult):
+    """What Engine.simulate_portfolio_cashflow_checkpoints returns: PortfolioCashflowResult's outputs and the record of
+    the paths' values after each chosen period (0 for a path depleted by then)."""
+    periods: np.ndarray = None  # uint32 [n_checkpoints]
+    checkpoints: list = None    # [Stats per checkpoint], hist_lo / hist_hi filled
+
+    def fan(self, quantiles):
+        """The fan chart: fan(self.checkpoints, quantiles) -- [n_checkpoints, len(quantiles)] values."""
+        return fan(self.checkpoints, quantiles)
+
+    def depleted_by(self):
+        """Share of paths depleted at or before each checkpoint's period: float64 [n_checkpoints]."""
+        if self.depleted_at is None:
+            raise ValueError("depleted_by() needs depleted_at (want_depleted_at=True)")
+        d = np.asarray(self.depleted_at, dtype=np.float64)
+        n = d.sum()
+        if n == 0:
+            return np.full(len(self.periods), np.nan)
+        gone = np.cumsum(d) - d[0]  # [0] counts the paths that were never depleted
+        return gone[np.asarray(self.periods, dtype=np.int64)] / n
+
+
+@dataclasses.dataclass
 class RealCashflowResult(PortfolioCashflowResult):
     """What Engine.simulate_real_cashflow returns: PortfolioCashflowResult's nominal outputs (survival() included), the
     final values in money of period 0 and the price index they were divided by; stats is the record of final_real."""
@@ -1033,6 +1056,105 @@ class Engine:
         if rc < 0:
             _lib.check(rc)
         return rc
+
+    # -- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods
+    #    (smmc_engine_simulate_portfolio_cashflow_checkpoints) ---------------------------------------------------------
+    @staticmethod
+    def _checkpoint_periods(periods):
+        per = np.ascontiguousarray([int(p) for p in periods], dtype=np.int64)
+        if per.size and (per.min() < 0 or per.max() > 0xFFFFFFFF):
+            raise ValueError("periods must be non-negative 32-bit integers")
+        return per.astype(np.uint32)
+
+    def simulate_portfolio_cashflow_checkpoints(self, sim, weights, periods, rebalance_every=0, amount=0.0, fraction=0.0,
+                                                floor=0.0, amounts=None, fractions=None, means=None, factor=None,
+                                                want_final=True, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                                want_stats=False, want_depleted_at=True):
+        """simulate_portfolio_cashflow with the record of the paths' values after each of `periods` (strictly increasing
+        integers in 1 .. n_periods, at most _lib.MAX_CHECKPOINTS; a depleted path counts as 0), in one launch.  Returns a
+        PortfolioCashflowCheckpointsResult: its checkpoints carry sim's bucket range, fan(quantiles) draws the fan chart
+        of the plan.  Per-path outputs stay on the device; the records are read back (that waits)."""
+        raw = self.simulate_portfolio_cashflow_checkpoints_raw(sim, weights, periods, rebalance_every, amount, fraction, floor,
+                                                               amounts, fractions, means, factor, want_final, want_holdings,
+                                                               want_paid, want_ruin_period, want_stats, want_depleted_at)
+        per = raw["periods"]
+        res = PortfolioCashflowCheckpointsResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                                 n_assets=raw["n_assets"], holdings=raw["holdings"], periods=per)
+        self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        host, rec = raw["records_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
+        res.checkpoints = []
+        for k in range(per.size):
+            st = stats_from_bytes(host[k * rec:(k + 1) * rec])
+            st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+            res.checkpoints.append(st)
+        return res
+
+    def simulate_portfolio_cashflow_checkpoints_raw(self, sim, weights, periods, rebalance_every=0, amount=0.0, fraction=0.0,
+                                                    floor=0.0, amounts=None, fractions=None, means=None, factor=None,
+                                                    want_final=True, want_holdings=False, want_paid=False,
+                                                    want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict with
+        records_raw (uint8, n_checkpoints packed records) and periods (numpy uint32)."""
+        torch = self._torch
+        per = self._checkpoint_periods(periods)
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        rec = int(self._L.smmc_stats_bytes(sim.n_bins))
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "periods": per, "final": new(want_final, n, torch.float32),
+               "holdings": new(want_holdings, (K, n), torch.float32), "paid": new(want_paid, n, torch.float32),
+               "ruin_period": new(want_ruin_period, n, torch.int32), "stats_raw": new(want_stats, rec, torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64),
+               "records_raw": torch.empty(max(per.size, 1) * rec, dtype=torch.uint8, device=self.tdevice)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints(
+            self._h, C.byref(sim), C.byref(pf), C.byref(cf), per.ctypes.data_as(C.c_void_p), per.size, C.byref(o),
+            C.c_void_p(res["records_raw"].data_ptr())))
+        self._leave(cur, res["records_raw"], *[res[key] for _, key in self._PFCF_OUTPUTS])
+        del keep
+        res["records_raw"] = res["records_raw"][: per.size * rec]
+        return res
+
+    def simulate_portfolio_cashflow_checkpoints_to_host(self, sim, weights, periods, rebalance_every=0, amount=0.0, fraction=0.0,
+                                                        floor=0.0, amounts=None, fractions=None, means=None, factor=None,
+                                                        want_final=True, want_holdings=False, want_paid=False,
+                                                        want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_portfolio_cashflow_checkpoints_to_host: a dict of numpy arrays (stats_raw
+        and records_raw: bytes)."""
+        per = self._checkpoint_periods(periods)
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        rec = int(self._L.smmc_stats_bytes(sim.n_bins))
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "periods": per, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, rec // 8, np.uint64), "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        records = np.zeros(max(per.size, 1) * rec // 8, dtype=np.uint64)
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints_to_host(
+            self._h, C.byref(sim), C.byref(pf), C.byref(cf), per.ctypes.data_as(C.c_void_p), per.size, C.byref(o),
+            records.ctypes.data_as(C.c_void_p)))
+        del keep
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        res["records_raw"] = records.tobytes()[: per.size * rec]
+        return res
 
     # -- real cash flows: the schedule in money of period 0, inflation drawn jointly (smmc_engine_simulate_real_cashflow) --
     _REAL_OUTPUTS = (("final", "final"), ("final_real", "final_real"), ("index", "index"), ("holdings", "holdings"), ("paid", "paid"),
