@@ -760,6 +760,89 @@ int smmc_engine_simulate_real_cashflow_to_host(smmc_engine *e, const smmc_sim *s
 int smmc_engine_real_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                           const smmc_cashflow *cf);
 
+/* ---- guardrails: a withdrawal that a review rule adjusts per path ------------------------------------ */
+
+/* "Take 4 %, index it every year, cut spending by 10 % if the withdrawal rate drifts above 5 %, raise it by 10 % if it
+ * falls below 3 %" (Guyton-Klinger style guardrails; with cut = raise = 1 and the clamps, a floor-and-ceiling rule):
+ * smmc_engine_simulate_portfolio_cashflow with a constant starting amount that a review after every E-th period
+ * adjusts PER PATH.  Every other cash-flow call takes its schedule as fixed before the first draw; here the amount in
+ * force is state of the path that feeds back into its value.  pf keeps smmc_portfolio's meaning: weights,
+ * rebalance_every = R, the asset table or means and factor, the draws and the checks are exactly as in
+ * smmc_engine_simulate_portfolio_cashflow.  Counter stream v3 only. */
+typedef struct smmc_guardrails {
+  uint32_t struct_size;    /* = sizeof(smmc_guardrails) */
+  uint32_t review_every;   /* E: a review after every E-th period; 0 = never */
+  float amount;            /* A0 > 0, taken after every period until a review changes it */
+  float index;             /* > 0, finite: multiplies the amount at every review (1 = none; 1.02 = +2 % a review) */
+  float upper, lower;      /* withdrawal-rate bands per period as fractions of the value; 0 <= lower <= upper; upper may be +inf */
+  float cut, raise;        /* 0 < cut <= 1; 1 <= raise, finite */
+  float amount_min, amount_max; /* 0 <= amount_min <= A0 <= amount_max; amount_max may be +inf */
+  float floor;             /* depleted when !(value > floor); >= 0, finite */
+} smmc_guardrails;
+
+/* Per path, every operation ONE binary32 rounding, nothing fused, every comparison false for NaN; a_k(t) are the
+ * portfolio contract's multipliers, P = n_periods, 1 <= P <= SMMC_MAX_CASHFLOW_PERIODS:
+ *   start      h_k = fl(capital * w_k);  paid = 0;  ruin = 0;  alive;  cur = A0;  lowest = A0;  cuts = raises = 0
+ *   t = 1..P   h_k = fl(fl(h_k * a_k(t)) / 100.0f)               IEEE divide, always
+ *              g   = ((h_0 + h_1) + h_2) + h_3                    left to right over K
+ *              w   = cur;  vn = fl(g - w)
+ *     live, vn > floor:    paid = fl(paid + w);  v = vn
+ *                          rebalance (R > 0, t mod R == 0, t != P):  h_k = fl(vn * w_k)
+ *                          else:                                     h_k = fl(h_k - fl(w * w_k))
+ *                          review (E > 0, t mod E == 0, t != P):
+ *                            c = fl(cur * index)
+ *                            if      c > fl(vn * upper):  c = fl(c * cut);    cuts   += 1;  counted in cuts_at[t]
+ *                            else if c < fl(vn * lower):  c = fl(c * raise);  raises += 1;  counted in raises_at[t]
+ *                            cur = fminf(fmaxf(c, amount_min), amount_max);  lowest = fminf(lowest, cur)
+ *     live, !(vn > floor): depleted at t exactly as the parent: h_k = 0, v = 0, paid = fl(paid + fmaxf(g, 0)), ruin = t;
+ *                          no review
+ *     depleted:            nothing changes, cur / lowest / counts included; its draws are still consumed
+ *   final value = v after period P;  final holdings = h_k after period P (no rebalance and no review at P)
+ * What follows from it:
+ *   - The bands compare the amount of the NEXT periods with the value AFTER this period's withdrawal.
+ *   - E = 0 or E >= P (no review ever happens), or cut = raise = index = 1 with amount_min = 0 and amount_max = +inf,
+ *     give smmc_engine_simulate_portfolio_cashflow with the constant amount A0 bit for bit, amount_last ==
+ *     amount_lowest == A0 and all counts 0.
+ *   - upper = +inf, lower = 0, amount_min = 0 and amount_max = +inf: the amount in force is A0 multiplied by index once
+ *     per passed review, the same for every path; the call is the parent with that amounts[] bit for bit.
+ *   - Table mode with K = 1, w_0 = 1 is the same rule on smmc_engine_simulate_cashflow's paths.
+ *   - The divide by 100 is always the IEEE one: the amount varies per path, the case for which the proof of
+ *     smmc_engine_portfolio_cashflow_divide_kind has no fast form.  SMMC_FLAG_EXACT_DIV is accepted and changes
+ *     nothing; there is no divide_kind entry.
+ *   - A path depends only on (seed, global path id, table or means and factor, weights, R, the smmc_guardrails), never
+ *     on first_path, the shard or the launch geometry. */
+typedef struct smmc_guardrails_outputs {
+  uint32_t struct_size, reserved; /* = sizeof(smmc_guardrails_outputs), 0 */
+  float *d_final;          /* n_paths final values, 0 for a depleted path */
+  float *d_holdings;       /* final holdings, asset-major K x n_paths */
+  float *d_paid;           /* n_paths totals paid out */
+  uint32_t *d_ruin_period; /* n_paths periods of depletion, 0 = never */
+  void *d_stats;           /* packed record of the final values, smmc_stats_bytes(n_bins) */
+  uint64_t *d_depleted_at; /* n_periods + 1 counts: [0] never depleted, [t] depleted at period t; their sum is n_paths */
+  float *d_amount_last;    /* n_paths amounts in force after the last review (a depleted path: when it was depleted) */
+  float *d_amount_lowest;  /* n_paths lowest amounts ever in force */
+  uint32_t *d_cuts;        /* n_paths numbers of cuts */
+  uint32_t *d_raises;      /* n_paths numbers of raises */
+  uint64_t *d_cuts_at;     /* n_periods + 1 counts: [t] paths cut at the review after period t; [0] is unused and stays 0 */
+  uint64_t *d_raises_at;   /* n_periods + 1 counts, likewise */
+} smmc_guardrails_outputs;
+
+/* Enqueues one such simulation on the engine stream and returns without waiting.  out holds DEVICE pointers (4-byte
+ * aligned; d_stats, d_depleted_at, d_cuts_at and d_raises_at 8-byte), any may be NULL; they are written, not
+ * accumulated into.  Integer outputs, min, max and bucket counts are exact; sum and sumsq are double sums in a fixed
+ * order, so two identical calls give the same bytes.  Shards merge by smmc_stats_merge and by adding the three count
+ * arrays.  n_paths == 0 launches nothing and yields the empty record and zero counts.
+ * SMMC_ERR_INVALID with a text: everything smmc_engine_simulate_portfolio refuses for sim and pf (the v2 and ref stream
+ * flags among it); a NULL or wrongly sized gr; a field of gr outside the bounds its comment states, or not finite
+ * where it must be; n_periods == 0 or above SMMC_MAX_CASHFLOW_PERIODS; a NULL or wrongly sized out, or reserved != 0;
+ * asset table, the three counter arrays and histogram beyond the device's LDS; 2^32 or more paths per workgroup (shard
+ * the request). */
+int smmc_engine_simulate_guardrails(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_guardrails *gr,
+                                    const smmc_guardrails_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_guardrails_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                            const smmc_guardrails *gr, const smmc_guardrails_outputs *out);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

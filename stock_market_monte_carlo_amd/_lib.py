@@ -161,6 +161,33 @@ class RealCashflowOutputs(C.Structure):
     ]
 
 
+class Guardrails(C.Structure):
+    """smmc_guardrails"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("review_every", C.c_uint32),
+        ("amount", C.c_float),
+        ("index", C.c_float),
+        ("upper", C.c_float),
+        ("lower", C.c_float),
+        ("cut", C.c_float),
+        ("raise_", C.c_float),
+        ("amount_min", C.c_float),
+        ("amount_max", C.c_float),
+        ("floor", C.c_float),
+    ]
+
+
+# the pointer fields of smmc_guardrails_outputs, in the order of the structure
+GUARDRAILS_OUTPUTS = ("final", "holdings", "paid", "ruin_period", "stats", "depleted_at", "amount_last", "amount_lowest",
+                      "cuts", "raises", "cuts_at", "raises_at")
+
+
+class GuardrailsOutputs(C.Structure):
+    """smmc_guardrails_outputs"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(name, C.c_void_p) for name in GUARDRAILS_OUTPUTS]
+
+
 class AllocationSweepOutputs(C.Structure):
     """smmc_allocation_sweep_outputs"""
     _fields_ = PortfolioCashflowOutputs._fields_  # the same pointers, scenario-major
@@ -254,6 +281,10 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(RealCashflowOutputs)]),
     ("smmc_engine_real_cashflow_divide_kind", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow)]),
+    ("smmc_engine_simulate_guardrails", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Guardrails), C.POINTER(GuardrailsOutputs)]),
+    ("smmc_engine_simulate_guardrails_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Guardrails), C.POINTER(GuardrailsOutputs)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

@@ -288,7 +288,7 @@ struct WaveWalk {
   uint32_t grid;     // workgroups; 0 (no paths): nothing is launched, the folds still write the empty outputs
   uint32_t n_bins;   // smmc_sim::n_bins of the request
   WalkRecord records[2];
-  WalkCounts counts[2];
+  WalkCounts counts[3];  // the most any entry has: depletion, cuts and raises (smmc_guardrails.cpp)
   WalkRecordSet set = {};  // most entries leave none
 };
 // How a record is folded: one record (launch_finalize), or the packed records of n scenarios whose partials and

@@ -275,6 +275,30 @@ struct RealCashflowArgs {
   float *d_index;       // nullable: n_paths price indices after the last period
 };
 hipError_t launch_real_cashflow(const KernelArgs &a, const RealCashflowArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
+// guardrails_kernel (smmc_engine_simulate_guardrails, csrc/smmc_guardrails.cpp; counter stream v3 only):
+// portfolio_cashflow_kernel's paths with a constant starting amount that a review after every review_every-th period
+// adjusts per path ("Guardrails").  p as launch_portfolio takes it; a.partials and a.d_hist as
+// launch_cashflow.  Always the IEEE divide: the amount varies per path.
+struct GuardrailsArgs {
+  PortfolioArgs p;
+  uint32_t review_every;  // E; 0: never
+  float amount;           // A0: the amount in force until a review changes it
+  float index;            // multiplies the amount at every review
+  float upper, lower;     // the bands, fractions of the value after the withdrawal
+  float cut, raise;       // the factors of a cut and of a raise
+  float amount_min, amount_max;
+  float floor;            // a path is depleted when !(value > floor)
+  float *d_paid;            // nullable: n_paths totals paid out
+  uint32_t *d_ruin_period;  // nullable: n_paths periods of depletion, 0 = never
+  float *d_amount_last, *d_amount_lowest;  // nullable: n_paths each
+  uint32_t *d_cuts, *d_raises;             // nullable: n_paths each
+  unsigned long long *d_depleted;               // nullable: n_periods + 1 counters, zero before the launch ([0]: never depleted)
+  unsigned long long *d_cuts_at, *d_raises_at;  // nullable: n_periods + 1 counters each, zero before the launch ([0] stays 0)
+};
+hipError_t launch_guardrails(const KernelArgs &a, const GuardrailsArgs &x, uint32_t grid, hipStream_t stream);
+// [the padded rows or the draw tables][three arrays of n_periods + 1 counters: depleted, cuts, raises][n_bins buckets]
+// [pad][the waves' partials]
+size_t guardrails_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
 // allocation_sweep_kernel (smmc_engine_simulate_allocation_sweep, csrc/smmc_allocation_sweep.cpp; counter stream v3
 // only): n constant-schedule strategies (weights, rebalance_every, amount, fraction, floor) stepped on ONE joint draw
 // per period ("Allocation sweeps").  p: the law as launch_portfolio takes it (n_assets, shift100, factor;

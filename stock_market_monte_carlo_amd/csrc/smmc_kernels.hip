@@ -2896,6 +2896,147 @@ void real_cashflow_kernel(const KernelArgs k, const RealCashflowArgs x) {
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- guardrails: a withdrawal that a review rule adjusts per path -----------------------------------
+//
+// smmc_engine_simulate_guardrails (csrc/smmc_guardrails.cpp; include/smmc.h and DESIGN.md, "Guardrails", state the
+// contract): portfolio_cashflow_kernel's holdings, draws and depletion with the amount in force `cur` as per-lane state.
+// Every period takes w = cur (no fraction); after every E-th period a live lane that goes on reviews it:
+//   c = cur * index;  c > vn * upper: c *= cut, a cut;  else c < vn * lower: c *= raise, a raise
+//   cur = min(max(c, amount_min), amount_max);  lowest = min(lowest, cur)
+// The amount differs per path, which is the case the parent's divide proof sends to the IEEE divide: the chains are
+// compound<true> always, there is no fast form.  The step is a SIBLING of portfolio_cashflow_step: the parent's, the
+// checkpoint kernel's and the sweep's instruction sequences stay what they are.  The review sits behind a second scalar
+// countdown beside the rebalance countdown (`until_review`; E = 0: it never ends), a wave-uniform branch: a period
+// without a review is the parent's step less the two instructions of w = amount + g * fraction.  By source, on top of
+// the K compounding chains: 4 K + 6 VALU in an ordinary period; a review adds 16 (three multiplies and two compares of
+// the bands, two selects of the factor and its multiply, max, min, select (cur), min (lowest), two selects and two adds
+// of the per-path counts); the per-period counts are two ballots and population counts on the scalar unit and one LDS
+// add each from lane 0.  `counts`: the lane's path is below n_paths (a lane beyond it runs a path and counts nothing).
+struct GuardrailsLane {  // a lane's state beside the holdings
+  float v, paid, cur, lowest;
+  uint32_t ruin, cuts, raises;
+  bool alive;
+};
+template <int K>
+__device__ __forceinline__ void guardrails_step(const float (&a)[K], const GuardrailsArgs &x, uint32_t n_periods, uint32_t t, bool counts,
+                                                uint32_t lane, uint32_t *lds_cuts, uint32_t *lds_raises, float (&h)[K],
+                                                GuardrailsLane &s, uint32_t &until, uint32_t &until_review) {
+  const float (&weights)[SMMC_MAX_ASSETS] = x.p.weights;
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = compound<true>(h[y], a[y]);
+  const float g = portfolio_value<K>(h);
+  const float w = s.cur;
+  const float vn = __fsub_rn(g, w);
+  const bool goes_on = s.alive && vn > x.floor;  // false for NaN
+  const bool dies = s.alive && !goes_on;
+  float hn[K];
+  bool rebalance = false;
+  if (--until == 0u) {  // uniform: t mod R == 0
+    until = x.p.rebalance_every;
+    rebalance = t != n_periods;  // the final holdings are formed before any rebalance at P
+  }
+  if (rebalance) {
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fmul_rn(vn, weights[y]);
+  } else {  // the flow settles at the target weights
+#pragma unroll
+    for (int y = 0; y < K; ++y) hn[y] = __fsub_rn(h[y], __fmul_rn(w, weights[y]));
+  }
+#pragma unroll
+  for (int y = 0; y < K; ++y) h[y] = goes_on ? hn[y] : 0.0f;
+  s.v = goes_on ? vn : 0.0f;
+  // a depleted lane: g = 0 (or NaN from 0 * inf: fmaxf gives 0), and paid + 0 is paid (paid is never -0)
+  s.paid = __fadd_rn(s.paid, goes_on ? w : fmaxf(g, 0.0f));
+  s.ruin = dies ? t : s.ruin;
+  s.alive = goes_on;
+  if (--until_review == 0u) {  // uniform: t mod E == 0
+    until_review = x.review_every;
+    if (t != n_periods) {  // no review after the last period: nothing would be taken at the new amount
+      float c = __fmul_rn(s.cur, x.index);
+      const bool cut = goes_on && c > __fmul_rn(vn, x.upper);            // false for NaN
+      const bool raise = goes_on && !cut && c < __fmul_rn(vn, x.lower);  // false for NaN
+      c = __fmul_rn(c, cut ? x.cut : raise ? x.raise : 1.0f);            // c * 1.0f is c
+      c = fminf(fmaxf(c, x.amount_min), x.amount_max);
+      s.cur = goes_on ? c : s.cur;
+      s.lowest = fminf(s.lowest, s.cur);
+      s.cuts += cut ? 1u : 0u;
+      s.raises += raise ? 1u : 0u;
+      const uint32_t n_cut = ballot_count(cut && counts), n_raise = ballot_count(raise && counts);  // wave-uniform
+      if (lds_cuts && n_cut && lane == 0u) atomicAdd(&lds_cuts[t], n_cut);
+      if (lds_raises && n_raise && lane == 0u) atomicAdd(&lds_raises[t], n_raise);
+    }
+  }
+}
+
+template <int kMode, bool kDense, int K>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void guardrails_kernel(const KernelArgs k, const GuardrailsArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const uint32_t n_at = k.n_periods + 1u;
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), 3u * n_at + k.n_bins);
+  uint32_t *lds_dep = s.counters;          // [n_periods + 1]
+  uint32_t *lds_cuts = lds_dep + n_at;     // [n_periods + 1], [0] stays 0
+  uint32_t *lds_raises = lds_cuts + n_at;  // [n_periods + 1], [0] stays 0
+  uint32_t *lds_hist = lds_raises + n_at;  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = x.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    GuardrailsLane st;
+    st.v = 0.0f;  // set by the first period (n_periods >= 1)
+    st.paid = 0.0f;
+    st.cur = st.lowest = x.amount;
+    st.ruin = st.cuts = st.raises = 0u;
+    st.alive = true;
+    uint32_t until = p.rebalance_every;  // periods until the next rebalance; with R == 0 the countdown never ends
+    uint32_t until_review = x.review_every;  // and until the next review, likewise
+    float a[kDraws][K];
+    walk_blocks<kDraws>(
+        k.n_periods, [&](uint32_t blk) { portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a); },
+        [&](int j, uint32_t t) {
+          guardrails_step<K>(a[j], x, k.n_periods, t, active, s.lane, x.d_cuts_at ? lds_cuts : nullptr,
+                             x.d_raises_at ? lds_raises : nullptr, h, st, until, until_review);
+        });
+    if (active) {
+      if (k.d_final) k.d_final[i] = st.v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (x.d_paid) x.d_paid[i] = st.paid;
+      if (x.d_ruin_period) x.d_ruin_period[i] = st.ruin;
+      if (x.d_amount_last) x.d_amount_last[i] = st.cur;
+      if (x.d_amount_lowest) x.d_amount_lowest[i] = st.lowest;
+      if (x.d_cuts) x.d_cuts[i] = st.cuts;
+      if (x.d_raises) x.d_raises[i] = st.raises;
+      if (want_dep) atomicAdd(&lds_dep[st.ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, st.v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, n_at, x.d_depleted);
+  if (x.d_cuts_at) flush_counters<kGroup>(lds_cuts, n_at, x.d_cuts_at);
+  if (x.d_raises_at) flush_counters<kGroup>(lds_raises, n_at, x.d_raises_at);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 // ---- allocation sweeps: up to eight portfolio strategies on one set of draws ------------------------
 //
 // smmc_engine_simulate_allocation_sweep (csrc/smmc_allocation_sweep.cpp; include/smmc.h and DESIGN.md, "Allocation
@@ -3091,7 +3232,13 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_REAL_CASHFLOW_KERNELS(1, false), SMMC_REAL_CASHFLOW_KERNELS(2, false), SMMC_REAL_CASHFLOW_KERNELS(3, false),
       SMMC_REAL_CASHFLOW_KERNELS(1, true), SMMC_REAL_CASHFLOW_KERNELS(2, true), SMMC_REAL_CASHFLOW_KERNELS(3, true),
 #undef SMMC_REAL_CASHFLOW_KERNELS
-#define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                                 \
+#define SMMC_GUARDRAILS_KERNELS(K)                                                                                          \
+  reinterpret_cast<const void *>(guardrails_kernel<SMMC_MODE_GAUSSIAN, false, K>),                                           \
+      reinterpret_cast<const void *>(guardrails_kernel<SMMC_MODE_TABLE, true, K>),                                           \
+      reinterpret_cast<const void *>(guardrails_kernel<SMMC_MODE_TABLE, false, K>)
+      SMMC_GUARDRAILS_KERNELS(1), SMMC_GUARDRAILS_KERNELS(2), SMMC_GUARDRAILS_KERNELS(3), SMMC_GUARDRAILS_KERNELS(4),
+#undef SMMC_GUARDRAILS_KERNELS
+#define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                                \
   reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, false, false, K, S>),                           \
       reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, true, false, K, S>),                        \
       reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, false, true, K, S>),                           \
@@ -3589,6 +3736,33 @@ hipError_t launch_real_cashflow(const KernelArgs &a, const RealCashflowArgs &x, 
   // LDS: the parent's layout with rows of the law's width
   return launch_wave_walk<RealCashflowFamily>(
       a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
+}
+
+// ---- guardrails ----
+
+size_t guardrails_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins) {
+  // the padded rows in the table's place; counters: depletion, cuts and raises [n_periods + 1] each, histogram [n_bins];
+  // one partial per wave
+  return wave_walk_lds_bytes(mode, n_rows * portfolio_row_words(n_assets), 3u * (static_cast<size_t>(n_periods) + 1u) + n_bins, 1u);
+}
+
+struct GuardrailsFamily {  // one divide, the IEEE one: both rungs of the ladder's divide are the same kernel
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<GuardrailsArgs> get(const GuardrailsArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return guardrails_kernel<kMode, kDense, 1>;
+      case 2: return guardrails_kernel<kMode, kDense, 2>;
+      case 3: return guardrails_kernel<kMode, kDense, 3>;
+      default: return guardrails_kernel<kMode, kDense, 4>;
+    }
+  }
+};
+hipError_t launch_guardrails(const KernelArgs &a, const GuardrailsArgs &x, uint32_t grid, hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  return launch_wave_walk<GuardrailsFamily>(a, x, true, grid, guardrails_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins),
+                                            stream);
 }
 
 // ---- allocation sweeps ----

@@ -291,6 +291,37 @@ class RealCashflowResult(PortfolioCashflowResult):
     index: object = None       # torch.float32 [n_paths]: the price index after the last period (1.0 at the start)
 
 
+@dataclasses.dataclass
+class GuardrailsResult(PortfolioCashflowResult):
+    """What Engine.simulate_guardrails returns: PortfolioCashflowResult's outputs (survival() included), the amounts in
+    force per path and the counts of cuts and raises, per path and per review."""
+    amount_last: object = None    # torch.float32 [n_paths]: the amount in force after the last review
+    amount_lowest: object = None  # torch.float32 [n_paths]: the lowest amount ever in force
+    cuts: object = None           # torch.int32 [n_paths] holding uint32 values: the path's cuts
+    raises: object = None         # torch.int32 [n_paths] holding uint32 values: the path's raises
+    cuts_at: np.ndarray = None    # uint64 [n_periods + 1]: [t] paths cut at the review after period t; [0] stays 0
+    raises_at: np.ndarray = None  # uint64 [n_periods + 1], likewise
+
+    def ever_cut(self):
+        """Share of paths with at least one cut."""
+        if self.cuts is None:
+            raise ValueError("ever_cut() needs cuts (want_cuts=True)")
+        if self.n_paths == 0:
+            return float("nan")
+        return float((self.cuts > 0).sum().item()) / self.n_paths
+
+    def cut_by(self):
+        """Cuts made by period t per path, cumulative, length n_periods + 1: cumsum(cuts_at) / n_paths.  Where no path is
+        cut more than once (cuts.max() <= 1) this is the share of paths first cut by period t; cuts_at counts EVERY cut,
+        and the contract has no per-path period of the first one, so with repeated cuts it is an upper bound of that
+        share (ever_cut() is its exact last value)."""
+        if self.cuts_at is None:
+            raise ValueError("cut_by() needs cuts_at (want_cuts_at=True)")
+        if self.n_paths == 0:
+            return np.full(len(self.cuts_at), np.nan)
+        return np.cumsum(np.asarray(self.cuts_at, dtype=np.float64)) / self.n_paths
+
+
 def cholesky_factor(stds, corr):
     """The lower-triangular factor L (float32 [K, K], percent) of diag(stds) corr diag(stds), for
     Engine.simulate_portfolio(factor=...): numpy's float64 Cholesky, cast once.  Raises ValueError for a matrix that
@@ -1056,6 +1087,114 @@ class Engine:
         if rc < 0:
             _lib.check(rc)
         return rc
+
+    # -- guardrails: a withdrawal that a review rule adjusts per path (smmc_engine_simulate_guardrails) --------------
+    _GUARDRAILS_WANTS = ("final", "holdings", "paid", "ruin_period", "stats", "depleted_at", "amount_last", "amount_lowest",
+                         "cuts", "raises", "cuts_at", "raises_at")  # _lib.GUARDRAILS_OUTPUTS; the result key of stats is stats_raw
+
+    @staticmethod
+    def make_guardrails(amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1, index=1.0, amount_min=0.0,
+                        amount_max=float("inf"), floor=0.0):
+        """smmc_guardrails; the library checks the bounds."""
+        gr = _lib.Guardrails()
+        gr.struct_size = C.sizeof(_lib.Guardrails)
+        gr.review_every = int(review_every)
+        gr.amount, gr.index, gr.upper, gr.lower = float(amount), float(index), float(upper), float(lower)
+        gr.cut, gr.raise_, gr.amount_min, gr.amount_max, gr.floor = float(cut), float(raise_), float(amount_min), float(amount_max), float(floor)
+        return gr
+
+    @staticmethod
+    def _guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at, want_amount_last,
+                          want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at):
+        return dict(zip(Engine._GUARDRAILS_WANTS, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
+                                                    want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at,
+                                                    want_raises_at)))
+
+    def simulate_guardrails(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1, index=1.0,
+                            amount_min=0.0, amount_max=float("inf"), floor=0.0, rebalance_every=0, means=None, factor=None,
+                            want_final=True, want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                            want_depleted_at=True, want_amount_last=True, want_amount_lowest=True, want_cuts=True, want_raises=True,
+                            want_cuts_at=True, want_raises_at=True):
+        """simulate_portfolio_cashflow with the constant amount `amount` that a review after every `review_every`-th
+        period adjusts per path: multiplied by `index`, then by `cut` if it exceeds `upper` times the value left, else
+        by `raise_` if it is below `lower` times it, and clamped to [amount_min, amount_max].  Returns a
+        GuardrailsResult; per-path outputs stay on the device, stats and the three count arrays are read back (that
+        waits).  include/smmc.h states the arithmetic."""
+        raw = self.simulate_guardrails_raw(sim, weights, amount, review_every, upper, lower, cut, raise_, index, amount_min, amount_max,
+                                           floor, rebalance_every, means, factor, want_final, want_holdings, want_paid,
+                                           want_ruin_period, want_stats, want_depleted_at, want_amount_last, want_amount_lowest,
+                                           want_cuts, want_raises, want_cuts_at, want_raises_at)
+        res = GuardrailsResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                               n_assets=raw["n_assets"], holdings=raw["holdings"], amount_last=raw["amount_last"],
+                               amount_lowest=raw["amount_lowest"], cuts=raw["cuts"], raises=raw["raises"])
+        if want_stats or want_depleted_at or want_cuts_at or want_raises_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        for key in ("depleted_at", "cuts_at", "raises_at"):
+            if raw[key] is not None:
+                setattr(res, key, raw[key].cpu().numpy().view(np.uint64).copy())
+        return res
+
+    def simulate_guardrails_raw(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1,
+                                index=1.0, amount_min=0.0, amount_max=float("inf"), floor=0.0, rebalance_every=0, means=None,
+                                factor=None, want_final=True, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                want_stats=False, want_depleted_at=True, want_amount_last=True, want_amount_lowest=True,
+                                want_cuts=True, want_raises=True, want_cuts_at=True, want_raises_at=True):
+        """Enqueues the call and returns its device tensors without waiting: a dict with final, holdings, paid,
+        amount_last, amount_lowest (float32), ruin_period, cuts, raises (int32 holding uint32 values), stats_raw (uint8,
+        the packed record) and depleted_at, cuts_at, raises_at (int64 holding uint64 counts, n_periods + 1); None for
+        what was not asked for."""
+        torch = self._torch
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        gr = self.make_guardrails(amount, review_every, upper, lower, cut, raise_, index, amount_min, amount_max, floor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        want = self._guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
+                                      want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
+        shapes = {"final": (n, torch.float32), "holdings": ((K, n), torch.float32), "paid": (n, torch.float32),
+                  "ruin_period": (n, torch.int32), "stats": (int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+                  "depleted_at": (p + 1, torch.int64), "amount_last": (n, torch.float32), "amount_lowest": (n, torch.float32),
+                  "cuts": (n, torch.int32), "raises": (n, torch.int32), "cuts_at": (p + 1, torch.int64), "raises_at": (p + 1, torch.int64)}
+        res = {"n_assets": K}
+        o = _lib.GuardrailsOutputs()
+        o.struct_size = C.sizeof(_lib.GuardrailsOutputs)
+        for name in self._GUARDRAILS_WANTS:
+            t = torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.tdevice) if want[name] else None
+            res["stats_raw" if name == "stats" else name] = t
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_guardrails(self._h, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o)))
+        self._leave(cur, *[res["stats_raw" if name == "stats" else name] for name in self._GUARDRAILS_WANTS])
+        return res
+
+    def simulate_guardrails_to_host(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1,
+                                    index=1.0, amount_min=0.0, amount_max=float("inf"), floor=0.0, rebalance_every=0, means=None,
+                                    factor=None, want_final=True, want_holdings=False, want_paid=False, want_ruin_period=False,
+                                    want_stats=False, want_depleted_at=True, want_amount_last=True, want_amount_lowest=True,
+                                    want_cuts=True, want_raises=True, want_cuts_at=True, want_raises_at=True):
+        """The same through smmc_engine_simulate_guardrails_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        gr = self.make_guardrails(amount, review_every, upper, lower, cut, raise_, index, amount_min, amount_max, floor)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        want = self._guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
+                                      want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
+        shapes = {"final": (n, np.float32), "holdings": ((K, n), np.float32), "paid": (n, np.float32), "ruin_period": (n, np.uint32),
+                  "stats": (int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64), "depleted_at": (p + 1, np.uint64),
+                  "amount_last": (n, np.float32), "amount_lowest": (n, np.float32), "cuts": (n, np.uint32), "raises": (n, np.uint32),
+                  "cuts_at": (p + 1, np.uint64), "raises_at": (p + 1, np.uint64)}
+        res = {"n_assets": K}
+        o = _lib.GuardrailsOutputs()
+        o.struct_size = C.sizeof(_lib.GuardrailsOutputs)
+        for name in self._GUARDRAILS_WANTS:
+            t = np.zeros(shapes[name][0], dtype=shapes[name][1]) if want[name] else None
+            res["stats_raw" if name == "stats" else name] = t
+            setattr(o, name, t.ctypes.data if t is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_guardrails_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o)))
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
 
     # -- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods
     #    (smmc_engine_simulate_portfolio_cashflow_checkpoints) ---------------------------------------------------------
