@@ -591,6 +591,52 @@ int smmc_engine_simulate_portfolio_cashflow_to_host(smmc_engine *e, const smmc_s
 int smmc_engine_portfolio_cashflow_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                const smmc_cashflow *cf);
 
+/* ---- block-bootstrap plans: portfolio cash flows on runs of consecutive months ------------------- */
+
+/* smmc_engine_simulate_portfolio_cashflow on paths built as smmc_engine_simulate_blocks builds them: independent rows keep
+ * the correlation between assets and destroy what lies between neighbouring months -- volatility clusters, the shape of a
+ * crash and of its recovery, runs of bad years --, which is what sequence-of-returns risk and the depletion statistics are
+ * made of.  A path is a sequence of runs of L = blocks->block_len consecutive rows of the asset table.
+ * Scope: SMMC_MODE_TABLE and counter stream v3 only; the table is the one given by smmc_engine_set_asset_table, T = n_rows.
+ * Block starts: block b = 0, 1, ... of a path starts at row s_b, exactly the row smmc_engine_simulate_portfolio's table
+ *     stream draws for that path at 0-based period b: the same key, counter (b / D, id lo, id hi, 0) and digits, D = 8
+ *     for n_rows <= 2048 and 4 above.
+ * Row of a period: period t = 1 .. P uses row (s_{(t-1) div L} + (t-1) mod L) mod n_rows, for every asset.  L may exceed
+ *     n_rows or P.
+ * No new random numbers: the starts of a path over P periods are the parent's rows over ceil(P / L) periods.
+ * Recurrence: everything after the row is smmc_engine_simulate_portfolio_cashflow's, word for word -- the holdings, the
+ *     left-to-right value, the flow, settling at the target weights, the rebalance at t mod R == 0 && t != P, depletion,
+ *     the lane mask of a depleted path (whose draws are still consumed), the outputs, the exactness of the record and the
+ *     counts, byte-identical repeat calls, shards merged by smmc_stats_merge and by adding d_depleted_at, n_paths == 0.
+ * A path depends only on (seed, global path id, table, weights, R, schedule, floor, L).
+ * Identities:
+ *   1. block_len == 1 is smmc_engine_simulate_portfolio_cashflow bit for bit: final, holdings, paid, ruin_period,
+ *      depleted_at, the record's integer fields, min, max and bucket counts; sum and sumsq within relative 1e-12 (another
+ *      summation order is allowed).
+ *   2. K = 1, w_0 = 1, zero flows and floor 0 give smmc_engine_simulate_blocks' final values bit for bit for the same
+ *      column (also given to smmc_engine_set_table) and the same L, while every value stays finite and above 0, whatever
+ *      divide either call takes.
+ *   3. Zero flows with any K are the block bootstrap of smmc_engine_simulate_portfolio.
+ *   4. block_len >= n_periods: every path is ONE run of consecutive rows from s_0, the parent's first row.
+ * SMMC_ERR_INVALID with a text, before any device work: everything smmc_engine_simulate_portfolio_cashflow refuses;
+ * mode != SMMC_MODE_TABLE; everything smmc_engine_simulate_blocks refuses for blocks (NULL, a wrong struct_size, block_len
+ * == 0, kind != SMMC_BLOCKS_CIRCULAR, reserved != 0); the asset table with its circular extension of 7 rows, the n_periods
+ * + 1 depletion counters, the n_bins buckets and the waves' partials beyond the device's LDS less 2048 bytes (the text
+ * names both numbers).  out holds DEVICE pointers as in the parent.  Asynchronous on the engine stream. */
+int smmc_engine_simulate_portfolio_cashflow_blocks(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                   const smmc_cashflow *cf, const smmc_blocks *blocks,
+                                                   const smmc_portfolio_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_portfolio_cashflow_blocks_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                           const smmc_cashflow *cf, const smmc_blocks *blocks,
+                                                           const smmc_portfolio_cashflow_outputs *out);
+/* After the call's argument checks, blocks included: what smmc_engine_portfolio_cashflow_divide_kind(e, sim, pf, cf)
+ * returns.  That rule's bounds come from the columns' extremes, the capital, P, the weights and the schedule, never from
+ * the order of the rows, and a block path is the parent's recurrence on another order of the same rows (DESIGN.md,
+ * "Block-bootstrap plans").  Results never depend on the form. */
+int smmc_engine_portfolio_cashflow_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                      const smmc_cashflow *cf, const smmc_blocks *blocks);
+
 /* ---- portfolio cash-flow checkpoints: the value distribution along a plan ----------------------- */
 
 /* "What does my wealth look like in year 5, 10, 15 ... under this plan": smmc_engine_simulate_portfolio_cashflow with

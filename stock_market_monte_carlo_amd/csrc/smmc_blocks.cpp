@@ -21,20 +21,8 @@ using smmc::DeviceGuard;
 using smmc::host_fail;
 
 int check_blocks(const smmc_engine *e, const smmc_sim *sim, const smmc_blocks *b) {
-  int rc = smmc::host_check_sim(e, sim);
-  if (rc) return rc;
-  if (!b) return host_fail(SMMC_ERR_INVALID, "the smmc_blocks argument is NULL");
-  if (b->struct_size != sizeof(smmc_blocks))
-    return host_fail(SMMC_ERR_INVALID, "smmc_blocks.struct_size is %u, this library expects %zu", b->struct_size, sizeof(smmc_blocks));
-  if (sim->mode != SMMC_MODE_TABLE)
-    return host_fail(SMMC_ERR_INVALID, "the block bootstrap resamples the returns table: mode must be SMMC_MODE_TABLE (got %d)", sim->mode);
-  rc = smmc::host_require_v3(sim, "the block bootstrap supports");
-  if (rc) return rc;
-  if (b->block_len == 0) return host_fail(SMMC_ERR_INVALID, "block_len is 0: a block holds at least one period");
-  if (b->kind != SMMC_BLOCKS_CIRCULAR)
-    return host_fail(SMMC_ERR_INVALID, "smmc_blocks.kind is %u: SMMC_BLOCKS_CIRCULAR (0) is the only kind", b->kind);
-  if (b->reserved != 0) return host_fail(SMMC_ERR_INVALID, "smmc_blocks.reserved is %u, it must be 0", b->reserved);
-  return SMMC_OK;
+  const int rc = smmc::host_check_sim(e, sim);
+  return rc ? rc : smmc::blocks_check(sim, b);
 }
 
 constexpr size_t kLdsPerCU = 160u * 1024u;  // CDNA4
@@ -99,6 +87,22 @@ int enqueue_blocks(smmc_engine *e, const smmc_sim *s, const smmc_blocks *b, floa
 }
 
 }  // namespace
+
+// What this unit refuses about `blocks`, the mode and the stream of a checked sim (smmc_host.h, "lend").
+int smmc::blocks_check(const smmc_sim *sim, const smmc_blocks *b) {
+  if (!b) return host_fail(SMMC_ERR_INVALID, "the smmc_blocks argument is NULL");
+  if (b->struct_size != sizeof(smmc_blocks))
+    return host_fail(SMMC_ERR_INVALID, "smmc_blocks.struct_size is %u, this library expects %zu", b->struct_size, sizeof(smmc_blocks));
+  if (sim->mode != SMMC_MODE_TABLE)
+    return host_fail(SMMC_ERR_INVALID, "the block bootstrap resamples the returns table: mode must be SMMC_MODE_TABLE (got %d)", sim->mode);
+  const int rc = smmc::host_require_v3(sim, "the block bootstrap supports");
+  if (rc) return rc;
+  if (b->block_len == 0) return host_fail(SMMC_ERR_INVALID, "block_len is 0: a block holds at least one period");
+  if (b->kind != SMMC_BLOCKS_CIRCULAR)
+    return host_fail(SMMC_ERR_INVALID, "smmc_blocks.kind is %u: SMMC_BLOCKS_CIRCULAR (0) is the only kind", b->kind);
+  if (b->reserved != 0) return host_fail(SMMC_ERR_INVALID, "smmc_blocks.reserved is %u, it must be 0", b->reserved);
+  return SMMC_OK;
+}
 
 extern "C" {
 

@@ -225,6 +225,9 @@ int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf);
 inline bool cashflow_varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }  // per-period arrays
 // the arrays of a varying schedule staged and their upload enqueued: c->schedule, c->stride.  Device must be current.
 int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c);
+// smmc_blocks.cpp, to smmc_portfolio_cashflow_blocks.cpp: what smmc_engine_simulate_blocks refuses about `blocks`, the mode
+// and the stream of a checked sim, with its texts.
+int blocks_check(const smmc_sim *sim, const smmc_blocks *b);
 
 // ---- what the entries of the feature units share: the checks of their outputs, the run, the _to_host form ----------
 // An *_outputs structure of include/smmc.h that begins with struct_size and reserved; `type` is its name.

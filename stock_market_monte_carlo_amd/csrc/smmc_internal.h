@@ -243,6 +243,22 @@ struct PortfolioCashflowArgs {
 hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflowArgs &x, bool exact_div, uint32_t grid,
                                      hipStream_t stream);
 size_t portfolio_cashflow_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// portfolio_cashflow_blocks_kernel (smmc_engine_simulate_portfolio_cashflow_blocks, csrc/smmc_portfolio_cashflow_blocks.cpp;
+// counter stream v3, table mode): portfolio_cashflow_kernel's recurrence on runs of block_len consecutive rows of the asset
+// table, each run starting at the row the portfolio's table stream draws ("Block-bootstrap plans").  p, c,
+// a.partials, a.d_hist and c.d_depleted as launch_portfolio_cashflow; c.stride >= a.n_periods.
+struct PortfolioCashflowBlocksArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  uint32_t block_len;  // L >= 1
+};
+// Rows as staged: row i holds table row i mod n_rows, so that a segment of 8 consecutive periods that begins at any row
+// below n_rows reads on without a wrap.
+constexpr uint32_t portfolio_cashflow_blocks_rows(uint32_t n_rows) { return n_rows + 7u; }
+hipError_t launch_portfolio_cashflow_blocks(const KernelArgs &a, const PortfolioCashflowBlocksArgs &x, bool exact_div, uint32_t grid,
+                                            hipStream_t stream);
+// [portfolio_cashflow_blocks_rows(n_rows) padded rows][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
+size_t portfolio_cashflow_blocks_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
 // portfolio_cashflow_checkpoints_kernel (smmc_engine_simulate_portfolio_cashflow_checkpoints,
 // csrc/smmc_portfolio_cashflow_checkpoints.cpp; counter stream v3 only): portfolio_cashflow_kernel's paths, with the
 // record of their values after each of n chosen periods ("Portfolio cash-flow checkpoints").  p, c, a.partials,

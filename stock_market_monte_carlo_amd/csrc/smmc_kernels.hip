@@ -2400,22 +2400,27 @@ void cashflow_sweep_kernel(const KernelArgs k, const SweepArgs c) {
 // multipliers_of_words_multi then yields STANDARD normals, and the multiplier is the contract's chain of fused
 // multiply-adds over L's row, j = 0 upwards from s_k.  The additions of V_t are __fadd_rn, the weight products
 // __fmul_rn: nothing may be re-associated or contracted.
+// The row at LDS byte address `at`, a multiple of the row's 4, 8 or 16 bytes.
 template <int K>
-__device__ __forceinline__ void load_asset_row(uint32_t row, float (&a)[K]) {
+__device__ __forceinline__ void load_asset_row_at(uint32_t at, float (&a)[K]) {
   static_assert(K >= 1 && K <= SMMC_MAX_ASSETS, "1 .. 4 assets");
   if constexpr (K == 1) {
-    a[0] = lds_load_at<float>(row << 2);
+    a[0] = lds_load_at<float>(at);
   } else if constexpr (K == 2) {
-    const f32x2_t r = lds_load_at<f32x2_t>(row << 3);
+    const f32x2_t r = lds_load_at<f32x2_t>(at);
     a[0] = r.x;
     a[1] = r.y;
   } else {
-    const f32x4_t r = lds_load_at<f32x4_t>(row << 4);
+    const f32x4_t r = lds_load_at<f32x4_t>(at);
     a[0] = r.x;
     a[1] = r.y;
     a[2] = r.z;
     if constexpr (K == 4) a[3] = r.w;
   }
+}
+template <int K>
+__device__ __forceinline__ void load_asset_row(uint32_t row, float (&a)[K]) {
+  load_asset_row_at<K>(row << (K == 1 ? 2 : K == 2 ? 3 : 4), a);
 }
 
 // The multipliers a[j][k] of asset k at draw j of Philox block `blk` (wave-uniform) of a path.
@@ -2625,6 +2630,131 @@ void portfolio_cashflow_kernel(const KernelArgs k, const PortfolioCashflowArgs x
           portfolio_cashflow_step<kExactDiv, K>(a[j], p.weights, am[j], fr[j], c.floor, every, k.n_periods, t, h, v, paid, ruin, alive,
                                                 until);
         });
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
+// ---- block-bootstrap plans: portfolio cash flows on runs of consecutive months ---------------------
+//
+// smmc_engine_simulate_portfolio_cashflow_blocks (csrc/smmc_portfolio_cashflow_blocks.cpp; include/smmc.h and DESIGN.md,
+// "Block-bootstrap plans", state the contract): portfolio_cashflow_kernel's recurrence -- the same
+// portfolio_cashflow_step, called, not restated -- on rows drawn as blocks_kernel draws its entries.  Block b of a path
+// starts at the row block_starts draws for it at period b (one Philox block per kDraws blocks, that is per kDraws L
+// periods), and period t reads row (s_{(t-1) div L} + (t-1) mod L) mod n_rows.  Table mode only; a family of its own:
+// portfolio_cashflow_kernel and blocks_kernel compile to what they compiled to before.
+//
+// Rows.  The asset table is staged with portfolio_cashflow_blocks_rows(n_rows) = n_rows + 7 rows, staged row i holding
+// table row i mod n_rows, so that a run walks in segments of up to kBlockSeg = 8 periods from ONE per-lane byte address
+// with the period in the instruction's offset field: one ds_read_b32 / b64 / b128 per period (K = 1, 2, 3 .. 4), no
+// address arithmetic and no wrap test per period.  A segment that begins at row s < n_rows reads rows s .. s + 7 at the
+// most, all below n_rows + 7.  Between segments the address advances by (8 mod n_rows) rows and wraps once (it stays below
+// 2 n_rows rows), as block_run does.  The block's last 1 .. 7 periods and the last block, cut by P, read only the rows of
+// their own periods (a uniform test per period of the tail).
+//
+// Control flow is wave-uniform: the period t, the block's and the segment's ends and the rebalance countdown are scalars,
+// only the start row differs per lane.  The kDraws starts of a Philox block stay in registers; block b takes start
+// b mod kDraws through a chain of selects on a scalar condition (no indexed register file access, no scratch), so the
+// step is instantiated for the eight periods of a segment and the seven of a tail, not once more per draw.
+//
+// Schedule (kVarying): entry t - 1 is read for period t with the wave-uniform index through the constant address space,
+// only for periods that exist (t <= P <= stride): a segment that begins off a multiple of 8 reads nothing past what
+// cashflow_stage_schedule staged.
+//
+// LDS: [n_rows + 7 padded rows][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
+// (portfolio_cashflow_blocks_lds_bytes).
+template <bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(SMMC_MODE_TABLE))
+void portfolio_cashflow_blocks_kernel(const KernelArgs k, const PortfolioCashflowBlocksArgs x) {
+  constexpr int kMode = SMMC_MODE_TABLE;
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  constexpr uint32_t kRowWords = portfolio_row_words(K), kRowBytes = 4u * kRowWords;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  const uint32_t n_rows = k.table_len;
+  const uint32_t staged_words = portfolio_cashflow_blocks_rows(n_rows) * kRowWords;
+  {  // the circular extension: staged rows n_rows .. n_rows + 6 (walk_setup stages the n_rows before them, and ends with the barrier)
+    float *lds = reinterpret_cast<float *>(lds_raw);
+    for (uint32_t i = n_rows * kRowWords + threadIdx.x; i < staged_words; i += kGroup)
+      lds[i] = k.table_a[((i / kRowWords) % n_rows) * kRowWords + i % kRowWords];
+  }
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  staged.table_len = n_rows * kRowWords;
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, staged_words, k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+  const uint32_t P = k.n_periods, L = x.block_len;
+  const uint32_t table_bytes = n_rows * kRowBytes;
+  const uint32_t step_bytes = (static_cast<uint32_t>(kBlockSeg) % n_rows) * kRowBytes;  // what an address advances by between segments
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    uint32_t start[kDraws];
+    uint32_t t = 0u;  // periods done; the block in hand covers periods t + 1 .. t + len
+    // period t + j + 1 of the run in hand, on the row at `at` + j rows
+    auto period = [&](uint32_t at, int j) {
+      float a[K];
+      load_asset_row_at<K>(at + static_cast<uint32_t>(j) * kRowBytes, a);
+      const float am = kVarying ? amounts[t + j] : c.amount;
+      const float fr = kVarying ? fractions[t + j] : c.fraction;
+      portfolio_cashflow_step<kExactDiv, K>(a, p.weights, am, fr, c.floor, every, P, t + j + 1u, h, v, paid, ruin, alive, until);
+    };
+    for (uint32_t b = 0; t < P; ++b) {  // block b; everything but `at` is wave-uniform
+      const uint32_t d = b % kDraws;
+      if (d == 0u) block_starts<kDense>(k, dr, path_lo, path_hi, b / kDraws, start);
+      uint32_t row = start[0];
+#pragma unroll
+      for (int j = 1; j < kDraws; ++j) row = d == static_cast<uint32_t>(j) ? start[j] : row;
+      uint32_t at = row * kRowBytes;  // < table_bytes
+      const uint32_t left = P - t;
+      uint32_t rem = left < L ? left : L;  // the last block is cut by P
+      for (; rem >= static_cast<uint32_t>(kBlockSeg); rem -= kBlockSeg) {
+#pragma unroll
+        for (int j = 0; j < kBlockSeg; ++j) period(at, j);
+        t += kBlockSeg;
+        at += step_bytes;  // < 2 table_bytes
+        at = at >= table_bytes ? at - table_bytes : at;
+      }
+      if (rem) {  // the block's last 1 .. 7 periods
+#pragma unroll
+        for (int j = 0; j < kBlockSeg - 1; ++j)
+          if (static_cast<uint32_t>(j) < rem) period(at, j);
+        t += rem;
+      }
+    }
     if (active) {
       if (k.d_final) k.d_final[i] = v;
       if (p.d_holdings) {
@@ -3210,7 +3340,17 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_KERNELS
-#define SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(K, V)                                                                   \
+#define SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(K, V) /* table mode only */                                                  \
+  reinterpret_cast<const void *>(portfolio_cashflow_blocks_kernel<false, true, K, V>),                                       \
+      reinterpret_cast<const void *>(portfolio_cashflow_blocks_kernel<true, true, K, V>),                                    \
+      reinterpret_cast<const void *>(portfolio_cashflow_blocks_kernel<false, false, K, V>),                                  \
+      reinterpret_cast<const void *>(portfolio_cashflow_blocks_kernel<true, false, K, V>)
+      SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(1, false), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(2, false),
+      SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(3, false), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(4, false),
+      SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(2, true),
+      SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(4, true),
+#undef SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS
+#define SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(K, V)                                                                  \
   reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),             \
       reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),          \
       reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_TABLE, false, true, K, V>),             \
@@ -3665,6 +3805,48 @@ hipError_t launch_portfolio_cashflow(const KernelArgs &a, const PortfolioCashflo
   if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
   return launch_wave_walk<PortfolioCashflowFamily>(
       a, x, exact_div, grid, portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
+}
+
+// ---- block-bootstrap plans ----
+
+size_t portfolio_cashflow_blocks_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins) {
+  // the parent's layout with the circularly extended rows in the table's place
+  return wave_walk_lds_bytes(SMMC_MODE_TABLE, portfolio_cashflow_blocks_rows(n_rows) * portfolio_row_words(n_assets),
+                             static_cast<size_t>(n_periods) + 1u + n_bins, 1u);
+}
+
+struct PortfolioCashflowBlocksFamily {  // table mode only: its own ladder, dense | four-draw table times exact | fast divide
+  template <bool kExactDiv, bool kDense, int K>
+  static WalkKernel<PortfolioCashflowBlocksArgs> schedule(const PortfolioCashflowBlocksArgs &x) {
+    return x.c.schedule ? portfolio_cashflow_blocks_kernel<kExactDiv, kDense, K, true>
+                        : portfolio_cashflow_blocks_kernel<kExactDiv, kDense, K, false>;
+  }
+  template <bool kExactDiv, bool kDense>
+  static WalkKernel<PortfolioCashflowBlocksArgs> assets(const PortfolioCashflowBlocksArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return schedule<kExactDiv, kDense, 1>(x);
+      case 2: return schedule<kExactDiv, kDense, 2>(x);
+      case 3: return schedule<kExactDiv, kDense, 3>(x);
+      default: return schedule<kExactDiv, kDense, 4>(x);
+    }
+  }
+  static WalkKernel<PortfolioCashflowBlocksArgs> get(const KernelArgs &a, const PortfolioCashflowBlocksArgs &x, bool exact_div) {
+    if (table_is_dense(a.table_len)) return exact_div ? assets<true, true>(x) : assets<false, true>(x);
+    return exact_div ? assets<true, false>(x) : assets<false, false>(x);
+  }
+};
+hipError_t launch_portfolio_cashflow_blocks(const KernelArgs &a, const PortfolioCashflowBlocksArgs &x, bool exact_div, uint32_t grid,
+                                            hipStream_t stream) {
+  if (a.stream != 3 || a.mode != SMMC_MODE_TABLE || !a.table_len || !a.table_a || !x.block_len) return hipErrorInvalidValue;
+  if (x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && x.c.stride < a.n_periods) return hipErrorInvalidValue;
+  const size_t lds = portfolio_cashflow_blocks_lds_bytes(a.table_len, x.p.n_assets, a.n_periods, a.n_bins);
+  const WalkKernel<PortfolioCashflowBlocksArgs> kernel = PortfolioCashflowBlocksFamily::get(a, x, exact_div);
+  const hipError_t err = allow_lds(kernel, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(SMMC_MODE_TABLE)), lds, stream, a, x);
+  return hipGetLastError();
 }
 
 // ---- portfolio cash-flow checkpoints ----

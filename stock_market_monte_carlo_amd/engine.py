@@ -1088,6 +1088,91 @@ class Engine:
             _lib.check(rc)
         return rc
 
+    # -- block-bootstrap plans: portfolio cash flows on runs of consecutive months (smmc_engine_simulate_portfolio_cashflow_blocks) --
+    def simulate_portfolio_cashflow_blocks(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
+                                           amounts=None, fractions=None, want_final=True, want_holdings=False, want_paid=False,
+                                           want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """simulate_portfolio_cashflow on paths built from runs of block_len consecutive rows of set_asset_table's table, each
+        run starting where the portfolio's table stream would have drawn a single row (table mode, counter stream v3): the
+        circular block bootstrap, which keeps what lies between neighbouring months.  block_len = 1 is
+        simulate_portfolio_cashflow bit for bit.  Returns the same PortfolioCashflowResult, so survival() works as there."""
+        raw = self.simulate_portfolio_cashflow_blocks_raw(sim, weights, block_len, rebalance_every, amount, fraction, floor, amounts,
+                                                          fractions, want_final, want_holdings, want_paid, want_ruin_period,
+                                                          want_stats, want_depleted_at)
+        res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                      n_assets=raw["n_assets"], holdings=raw["holdings"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_portfolio_cashflow_blocks_raw(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0,
+                                               floor=0.0, amounts=None, fractions=None, want_final=True, want_holdings=False,
+                                               want_paid=False, want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict."""
+        torch = self._torch
+        pf = self.make_portfolio(weights, rebalance_every)
+        blocks = self.make_blocks(block_len)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
+               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_blocks(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(blocks),
+                                                                          C.byref(o)))
+        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        del keep
+        return res
+
+    def simulate_portfolio_cashflow_blocks_to_host(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0,
+                                                   floor=0.0, amounts=None, fractions=None, want_final=True, want_holdings=False,
+                                                   want_paid=False, want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_portfolio_cashflow_blocks_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_portfolio(weights, rebalance_every)
+        blocks = self.make_blocks(block_len)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_blocks_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf),
+                                                                                  C.byref(blocks), C.byref(o)))
+        del keep
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def portfolio_cashflow_blocks_divide_kind(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
+                                              amounts=None, fractions=None):
+        """_lib.DIV_FAST or DIV_EXACT: what portfolio_cashflow_divide_kind says of the same plan (results never depend on it)."""
+        pf = self.make_portfolio(weights, rebalance_every)
+        blocks = self.make_blocks(block_len)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        rc = self._L.smmc_engine_portfolio_cashflow_blocks_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(blocks))
+        del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
     # -- guardrails: a withdrawal that a review rule adjusts per path (smmc_engine_simulate_guardrails) --------------
     _GUARDRAILS_WANTS = ("final", "holdings", "paid", "ruin_period", "stats", "depleted_at", "amount_last", "amount_lowest",
                          "cuts", "raises", "cuts_at", "raises_at")  # _lib.GUARDRAILS_OUTPUTS; the result key of stats is stats_raw
