@@ -1024,6 +1024,17 @@ int smmc_engine_selftest_draws(smmc_engine *e, const smmc_sim *sim, const uint32
 #define SMMC_DIV_EXACT 1
 #define SMMC_DIV_CHECKED 2
 int smmc_engine_divide_kind(smmc_engine *e, const smmc_sim *sim, int keepdata);
+/* Which kernel a smmc_engine_simulate launch of `sim` gets (the result never depends on it): 1, the form that holds
+ * the path id's bits 63..32 in a scalar register, for counter stream v3 in Gaussian mode or with a table of at most
+ * 2048 entries when first_path and first_path + n_paths - 1 share those bits (and their sum does not wrap) and
+ * smmc_set_uniform_hi has not switched it off; otherwise 0.  smmc_engine_simulate_to_host decides per chunk.
+ * Returns the form (>= 0) or an error. */
+int smmc_engine_paths_form(smmc_engine *e, const smmc_sim *sim);
+/* Process-wide switch for that form: 0 gives every later launch the generic kernel, 1 (the default) lets the rule
+ * above decide.  For A/B runs and for profiles of the generic kernel; results never depend on it.  The library reads
+ * no environment variable for it: the Python wrapper maps SMMC_UNIFORM_HI (0 | 1) onto this call before every
+ * launch.  SMMC_ERR_INVALID for another value. */
+int smmc_set_uniform_hi(int on);
 
 /* Launch geometry the engine will use (workgroups x threads), for reports. */
 int smmc_engine_geometry(smmc_engine *e, uint32_t *grid, uint32_t *block, uint32_t *compute_units);

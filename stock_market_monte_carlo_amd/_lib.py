@@ -318,6 +318,8 @@ SYMBOLS = [
     ("smmc_engine_geometry", C.c_int,
      [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("smmc_engine_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.c_int]),
+    ("smmc_engine_paths_form", C.c_int, [C.c_void_p, C.POINTER(Sim)]),
+    ("smmc_set_uniform_hi", C.c_int, [C.c_int]),
     ("smmc_group_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("smmc_group_destroy", None, [C.c_void_p]),
     ("smmc_group_size", C.c_int, [C.c_void_p]),

@@ -1567,6 +1567,19 @@ int smmc_engine_divide_kind(smmc_engine *e, const smmc_sim *sim, int keepdata) {
   return divide_kind(e, sim, keepdata == 0, &lo, &hi);
 }
 
+int smmc_set_uniform_hi(int on) {
+  if (on != 0 && on != 1) return fail(SMMC_ERR_INVALID, "smmc_set_uniform_hi takes 0 or 1, not %d", on);
+  smmc::paths_uniform_hi().store(on, std::memory_order_relaxed);
+  return SMMC_OK;
+}
+
+int smmc_engine_paths_form(smmc_engine *e, const smmc_sim *sim) {
+  const int rc = check_sim(e, sim);
+  if (rc) return rc;
+  if (sim->flags & SMMC_FLAG_STREAM_REF) return 0;  // the reference's stream has kernels of its own
+  return smmc::paths_form(make_args(e, sim));
+}
+
 uint64_t smmc_stats_bytes(uint32_t n_bins) { return sizeof(smmc_stats) + sizeof(uint64_t) * n_bins; }
 
 int smmc_stats_merge(void *dst_packed, const void *src_packed) {

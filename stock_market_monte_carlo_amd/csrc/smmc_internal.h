@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "smmc.h"
 
 namespace smmc {
@@ -123,6 +125,24 @@ hipError_t launch_radix_pick(int pass, uint32_t n_ranks, SelectState *st, unsign
 // `div`: SMMC_DIV_* of smmc.h (how a launch divides by 100: simulate_path in smmc_kernels.hip)
 hipError_t launch_paths(const KernelArgs &a, int div, uint32_t grid, size_t lds_bytes,
                         hipStream_t stream);
+constexpr uint32_t kDenseMaxTable = 2048u;  // largest table drawn eight-per-block
+// The process-wide switch of smmc_set_uniform_hi (default 1): read by every launch_paths, so a caller may change it
+// between the launches of one process.
+inline std::atomic<int> &paths_uniform_hi() {
+  static std::atomic<int> on{1};
+  return on;
+}
+// Which kernel launch_paths gives a launch (smmc_engine_paths_form): 1 = paths_hi_kernel, whose period loop takes the
+// path id's bits 63..32 from a scalar register (smmc_kernels.hip, kPhiloxUniformHi), 0 = paths_kernel.  1 needs
+// counter stream v3, Gaussian draws or a dense table, a range [first_path, first_path + n_paths) inside one multiple
+// of 2^32 -- a range that wraps past 2^64 is not -- and the switch above not 0.  The outputs do not depend on it.
+inline int paths_form(const KernelArgs &a) {
+  if (a.stream == 2 || !a.n_paths) return 0;
+  if (a.mode == SMMC_MODE_TABLE && a.table_len > kDenseMaxTable) return 0;
+  const uint64_t last = a.first_path + (a.n_paths - 1);
+  if (last < a.first_path || (last >> 32) != (a.first_path >> 32)) return 0;
+  return paths_uniform_hi().load(std::memory_order_relaxed) ? 1 : 0;
+}
 // hist_acc: `spread` copies of n_bins bucket counts accumulated by the launch before; folded into the record and zeroed
 // again (the engine keeps the array zero between launches: smmc_host.h, ZeroLease)
 hipError_t launch_finalize(const BlockPartial *partials, uint32_t n_partials, smmc_stats *d_stats,

@@ -26,12 +26,11 @@ constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
 constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
 constexpr uint32_t kWeyl0 = 0x9E3779B9u;
 constexpr uint32_t kWeyl1 = 0xBB67AE85u;
-constexpr uint32_t kDenseMaxTable = 2048u;  // largest table drawn eight-per-block
 
 // Philox4x32-10 (Salmon et al., SC'11).  The key schedule is wave-uniform and
 // lives in SGPRs; per round the lanes pay two 32x32->64 multiplies
 // (v_mad_u64_u32) and two three-input XORs (v_bitop3_b32).
-// kUniformFirst: the caller's c0 (counter stream v3: the block index) is wave-uniform and c1, c2 (the
+// kPhiloxUniformBlock: the caller's c0 (counter stream v3: the block index) is wave-uniform and c1, c2 (the
 // path) do not change along the caller's loop.  Rounds 0 and 1 then cost two VALU instructions:
 //   round 0: M0 c0 is a scalar product, M1 c2 per-path constant; n0 = hi(M1 c2) ^ c1 ^ k0 is
 //            per-path constant (hoisted out of the period loop), n2 = hi(M0 c0) ^ c3 ^ k1 scalar;
@@ -69,16 +68,44 @@ __device__ __forceinline__ DrawRegs make_draw_regs(const KernelArgs &k) {
   return d;
 }
 
-template <bool kUniformFirst = false>
+// kPhiloxUniformHi (paths_hi_kernel): c2 (the path's id bits 63..32) is wave-uniform as well -- every path of a
+// launch that does not reach across a multiple of 2^32 has the same.  Then
+//   round 0: M1 c2 is a scalar loop invariant too; n0 = hi(M1 c2) ^ c1 ^ k0 stays per-path constant, n2 scalar;
+//   round 1: (H, L) = M0 n0 per-path constant (hoisted); M1 n2 a scalar product; n0 is ALL scalar, n2 = H ^ pair;
+//   round 2: M0 n0 is a scalar product, M1 n2 one v_mad_u64_u32; n0 = hi(M1 n2) ^ pair, n2 = L ^ pair;
+//   round 3: four VALU instructions like the later rounds, n2's pair c3 ^ k1 scalar (c3 = lo of round 2's scalar product).
+// Five VALU instructions for rounds 1 .. 2 instead of six, one multiply fewer among them, and two hoisted
+// registers per path (H, L) instead of three.  A scalar pair handed a per-lane value would silently read lane 0's:
+// the form is only for callers whose c0 and c2 come from scalar registers.
+enum PhiloxForm { kPhiloxGeneric = 0, kPhiloxUniformBlock = 1, kPhiloxUniformHi = 2 };
+
+template <PhiloxForm kForm = kPhiloxGeneric>
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, const DrawRegs &dr, uint32_t (&out)[4]) {
+  constexpr bool kUniformFirst = kForm == kPhiloxUniformBlock;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     const uint64_t p0 = static_cast<uint64_t>(kPhiloxM0) * c0;
     const uint64_t p1 = static_cast<uint64_t>(kPhiloxM1) * c2;
     const uint32_t h0 = static_cast<uint32_t>(p0 >> 32), h1 = static_cast<uint32_t>(p1 >> 32);
     uint32_t n0, n2;
-    if (r == 1 && kUniformFirst) {
+    if (r == 1 && kForm == kPhiloxUniformHi) {
+      n0 = (h1 ^ k0) ^ c1;  // scalar throughout
+      uint32_t pair2 = c3 ^ k1;
+      asm("" : "+s"(pair2));
+      n2 = pair2 ^ h0;  // h0 = H
+    } else if (r == 2 && kForm == kPhiloxUniformHi) {
+      uint32_t pair0 = c1 ^ k0, pair2 = h0 ^ k1;
+      asm("" : "+s"(pair0));
+      asm("" : "+s"(pair2));
+      n0 = pair0 ^ h1;
+      n2 = pair2 ^ c3;  // c3 = L
+    } else if (r == 3 && kForm == kPhiloxUniformHi) {
+      uint32_t pair2 = c3 ^ k1;
+      asm("" : "+s"(pair2));
+      n0 = xor3(h1, c1, dr.k0[r]);
+      n2 = pair2 ^ h0;
+    } else if (r == 1 && kUniformFirst) {
       uint32_t pair0 = h1 ^ k0, pair2 = c3 ^ k1;  // scalar ^ scalar
       asm("" : "+s"(pair0));
       asm("" : "+s"(pair2));
@@ -382,15 +409,16 @@ __device__ __forceinline__ void multipliers_of_words(const KernelArgs &k, const 
 }
 
 // The per-period multipliers a = 100.0f + r of Philox block `blk` of a path.
-template <int kMode, bool kDense, bool kUniformBlock = false>
+template <int kMode, bool kDense, PhiloxForm kForm = kPhiloxGeneric>
 __device__ __forceinline__ void block_multipliers(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
                                                   uint32_t path_lo, uint32_t path_hi, uint32_t blk,
                                                   float (&a)[Draws<kMode, kDense>::value]) {
+  static_assert(kForm != kPhiloxUniformHi || counter_v3(kMode), "stream v2 counts blocks in the third word");
   uint32_t u[4];
   if constexpr (counter_v3(kMode))
-    philox4x32_10<kUniformBlock>(blk, path_lo, path_hi, mode_tag(kMode), k.key0, k.key1, dr, u);
+    philox4x32_10<kForm>(blk, path_lo, path_hi, mode_tag(kMode), k.key0, k.key1, dr, u);
   else
-    philox4x32_10<false>(path_lo, path_hi, blk, mode_tag(kMode), k.key0, k.key1, dr, u);
+    philox4x32_10<kPhiloxGeneric>(path_lo, path_hi, blk, mode_tag(kMode), k.key0, k.key1, dr, u);
   multipliers_of_words<kMode, kDense>(k, dr, lds_table, u, a);
 }
 
@@ -470,7 +498,8 @@ __device__ __forceinline__ void block_multipliers_multi(const KernelArgs &k, con
   multipliers_of_words_multi<kMode, kDense, N>(k, dr, lds_table, u, a);
 }
 
-template <int kMode, int kDiv, bool kDense>
+// kForm == kPhiloxUniformHi: the caller joins `path` from a per-lane low word and a SCALAR high word (philox4x32_10).
+template <int kMode, int kDiv, bool kDense, PhiloxForm kForm = kPhiloxUniformBlock>
 __device__ __forceinline__ float simulate_path(const KernelArgs &k, const DrawRegs &dr, const float *lds_table,
                                                uint64_t path) {
   constexpr int kDraws = Draws<kMode, kDense>::value;
@@ -487,7 +516,7 @@ __device__ __forceinline__ float simulate_path(const KernelArgs &k, const DrawRe
   // front of this block's chain.)
   for (uint32_t blk = 0; blk < full; ++blk) {
     float a[kDraws];
-    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+    block_multipliers<kMode, kDense, kForm>(k, dr, lds_table, path_lo, path_hi, blk, a);
 #pragma unroll
     for (int j = 0; j < kDraws; ++j) total = compound<kExactDiv>(total, a[j]);
     if constexpr (kDiv == kDivChecked) left_window |= !(total > k.chk_lo && total < k.chk_hi);  // NaN leaves too
@@ -495,13 +524,13 @@ __device__ __forceinline__ float simulate_path(const KernelArgs &k, const DrawRe
   const uint32_t rem = k.n_periods - full * kDraws;
   if (rem) {  // wave-uniform
     float a[kDraws];
-    block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, full, a);
+    block_multipliers<kMode, kDense, kForm>(k, dr, lds_table, path_lo, path_hi, full, a);
 #pragma unroll
     for (int j = 0; j < kDraws - 1; ++j)
       if (static_cast<uint32_t>(j) < rem) total = compound<kExactDiv>(total, a[j]);
   }
   if constexpr (kDiv == kDivChecked) {
-    if (left_window) total = simulate_path<kMode, kDivExact, kDense>(k, dr, lds_table, path);
+    if (left_window) total = simulate_path<kMode, kDivExact, kDense, kForm>(k, dr, lds_table, path);
   }
   return total;
 }
@@ -740,6 +769,162 @@ void paths_kernel(const KernelArgs k, const uint32_t vgrid) {
   }
 }
 
+// paths_kernel for a launch whose paths all have the same id bits 63..32 (launch_paths decides: paths_form in
+// smmc_internal.h): the high word is a kernel argument in a scalar register, not the carry of a per-lane 64-bit add,
+// and the period loop runs philox4x32_10<kPhiloxUniformHi> -- 68 VALU instructions per Philox block instead of 70 in
+// Gaussian mode, 82 instead of 84 in dense table mode, one of the two a half-rate multiply.  The draws, and with
+// them every output, are paths_kernel's bit for bit (tests/test_uniform_hi_gpu.py).
+//
+// The chunk walk, the outputs, the epilogue, the LDS layout, the halves and the occupancy request are paths_kernel's
+// statements, here a second time for the reason given above blocks_body: paths_kernel has to stay the instruction
+// sequence its counters were taken on, and every way of sharing code with it that was built moved that sequence.
+// A change to one copy belongs in the other.
+template <int kMode, int kDiv, bool kDense>
+__global__ __launch_bounds__(kBlock * paths_halves(kMode)) __attribute__((amdgpu_waves_per_eu(paths_min_waves(kMode))))
+void paths_hi_kernel(const KernelArgs k, const uint32_t vgrid) {
+  static_assert(counter_v3(kMode), "stream v2 has no uniform-high-word form");
+  constexpr uint32_t kHalves = paths_halves(kMode);
+  constexpr uint32_t kGroup = kBlock * kHalves;  // threads per workgroup
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *lds_table = reinterpret_cast<float *>(lds_raw);  // returns table, or the Box-Muller tables
+  const uint32_t table_words = is_table(kMode) ? k.table_len : bm_lds_words(kMode);
+  uint32_t *lds_hist = reinterpret_cast<uint32_t *>(lds_raw) + table_words;
+  const uint32_t scratch_words = (table_words + ((k.partials != nullptr) ? k.n_bins : 0u) + 1u) & ~1u;  // 8-byte aligned
+  double *red_scratch = reinterpret_cast<double *>(reinterpret_cast<uint32_t *>(lds_raw) + scratch_words);  // [kHalves][4 * kWaves]
+  BlockPartial *wave_part = reinterpret_cast<BlockPartial *>(red_scratch + 4 * kWaves * kHalves);          // [kHalves][kWaves]
+
+  const uint32_t half = kHalves > 1 ? threadIdx.x / kBlock : 0u;  // wave-uniform
+  const uint32_t tid = kHalves > 1 ? threadIdx.x % kBlock : threadIdx.x;
+  const uint32_t vb = blockIdx.x * kHalves + half;  // the virtual block: <= vgrid, == vgrid only for the idle half of an odd grid
+  red_scratch += half * (4 * kWaves);
+  wave_part += half * kWaves;
+  bool parity = false;
+  unsigned long long clk0 = 0, real0 = 0;
+  if (k.clock_probe) {  // uniform; timing instrumentation only
+    clk0 = __builtin_amdgcn_s_memtime();
+    real0 = __builtin_amdgcn_s_memrealtime();
+  }
+  stage_tables<kMode>(k, lds_table, kGroup);
+  const bool want_stats = k.partials != nullptr;
+  const bool want_hist = want_stats && k.n_bins != 0;
+  if (want_hist) {
+    for (uint32_t i = threadIdx.x; i < k.n_bins; i += kGroup) lds_hist[i] = 0u;
+  }
+  __syncthreads();
+
+  double sum = 0.0, sumsq = 0.0;
+  uint32_t n_count = 0, n_below = 0, n_under = 0, n_over = 0;
+  float vmin = __builtin_inff(), vmax = -__builtin_inff();
+  const DrawRegs dr = make_draw_regs(k);
+  // the launch's share of every path id: the low word wraps with the lane's index, the high word never moves
+  const uint32_t first_lo = static_cast<uint32_t>(k.first_path);
+  const uint64_t first_hi = k.first_path & 0xFFFFFFFF00000000ull;  // scalar
+
+  const uint64_t n_chunks = (k.n_paths + kBlock - 1) / kBlock;
+  for (uint64_t chunk0 = static_cast<uint64_t>(blockIdx.x) * kHalves; chunk0 < n_chunks; chunk0 += vgrid) {
+    const uint64_t chunk = chunk0 + half;
+    const bool live = kHalves == 1 || (vb < vgrid && chunk < n_chunks);  // wave-uniform
+    const uint64_t i = chunk * kBlock + tid;
+    const bool active = live && i < k.n_paths;
+    float v = 0.0f;
+    if (active) {
+      const uint32_t path_lo = first_lo + static_cast<uint32_t>(i);
+      v = simulate_path<kMode, kDiv, kDense, kPhiloxUniformHi>(k, dr, lds_table, first_hi | path_lo);
+      if (k.d_final) k.d_final[i] = v;
+    }
+    if (want_stats && active) {
+      const double dv = static_cast<double>(v);
+      sum += dv;
+      sumsq += dv * dv;
+      n_count += 1;
+      n_below += (v < k.below_threshold) ? 1u : 0u;
+      vmin = fminf(vmin, v);
+      vmax = fmaxf(vmax, v);
+      if (want_hist) {
+        if (v < k.hist_lo) {
+          n_under += 1;
+        } else if (v < k.hist_hi) {
+          int32_t b = static_cast<int32_t>((dv - static_cast<double>(k.hist_lo)) * k.hist_inv);
+          b = b < static_cast<int32_t>(k.n_bins) - 1 ? b : static_cast<int32_t>(k.n_bins) - 1;
+          atomicAdd(&lds_hist[b], 1u);
+        } else {
+          n_over += 1;
+        }
+      }
+    }
+    if (k.d_chunk_mean || k.d_chunk_var) {  // uniform over the workgroup
+      const double dv = active ? static_cast<double>(v) : 0.0;
+      const double s12 = wave_sum_pair(dv, dv * dv);  // lane 0: the wave's sum, lane 32: its sum of squares
+      double *slot = red_scratch + (parity ? 2 * kWaves : 0);
+      parity = !parity;
+      const int lane = tid & 63, wave = tid >> 6;
+      if ((lane & 31) == 0) slot[(lane ? kWaves : 0) + wave] = s12;
+      __syncthreads();
+      if (tid == 0 && live) {
+        double t1 = slot[0], t2 = slot[kWaves];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) {
+          t1 += slot[w];
+          t2 += slot[kWaves + w];
+        }
+        double mean, var;  // a full chunk needs no divide: see paths_kernel
+        if (chunk + 1 < n_chunks) {
+          static_assert(kBlock == 256, "the full chunk's reciprocal is 2^-8");
+          mean = t1 * 0x1p-8;
+          var = t2 * 0x1p-8 - mean * mean;
+        } else {
+          const double n_in = static_cast<double>(k.n_paths - chunk * kBlock);  // 1 .. kBlock
+          mean = t1 / n_in;
+          var = t2 / n_in - mean * mean;
+        }
+        if (k.d_chunk_mean) k.d_chunk_mean[chunk] = static_cast<float>(mean);
+        if (k.d_chunk_var) k.d_chunk_var[chunk] = static_cast<float>(var > 0.0 ? var : 0.0);
+      }
+    }
+  }
+
+  if (k.clock_probe && threadIdx.x == 0) {
+    atomicAdd(&k.clock_probe[0], __builtin_amdgcn_s_memtime() - clk0);
+    atomicAdd(&k.clock_probe[1], __builtin_amdgcn_s_memrealtime() - real0);
+  }
+  if (want_stats) {
+    // per-lane u32 counters cannot overflow: a lane sees < 2^32 chunks
+    BlockPartial p;
+    p.sum = wave_sum(sum);
+    p.sumsq = wave_sum(sumsq);
+    p.count = wave_sum(static_cast<unsigned long long>(n_count));
+    p.below = wave_sum(static_cast<unsigned long long>(n_below));
+    p.underflow = wave_sum(static_cast<unsigned long long>(n_under));
+    p.overflow = wave_sum(static_cast<unsigned long long>(n_over));
+    p.min = wave_min(vmin);
+    p.max = wave_max(vmax);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) wave_part[wave] = p;
+    __syncthreads();
+    if (tid == 0 && vb < vgrid) {  // one partial per virtual block; the idle half of an odd grid has none
+      BlockPartial t = wave_part[0];
+#pragma unroll
+      for (int w = 1; w < kWaves; ++w) {
+        t.sum += wave_part[w].sum;
+        t.sumsq += wave_part[w].sumsq;
+        t.count += wave_part[w].count;
+        t.below += wave_part[w].below;
+        t.underflow += wave_part[w].underflow;
+        t.overflow += wave_part[w].overflow;
+        t.min = fminf(t.min, wave_part[w].min);
+        t.max = fmaxf(t.max, wave_part[w].max);
+      }
+      k.partials[vb] = t;
+    }
+    if (want_hist) {  // LDS atomics of all waves are complete after the barrier above
+      for (uint32_t b = threadIdx.x; b < k.n_bins; b += kGroup) {
+        const uint32_t c = lds_hist[b];
+        if (c) atomicAdd(&k.d_hist[b], static_cast<unsigned long long>(c));
+      }
+    }
+  }
+}
+
 // Reduces the per-workgroup partials in a fixed order and writes the record header.
 // One 1024-thread workgroup: 16 k partials (64 workgroups per CU) take ~8 us instead of 26.
 constexpr int kFinalizeBlock = 1024;
@@ -833,7 +1018,7 @@ template <bool kDense>
 __device__ __forceinline__ void block_starts(const KernelArgs &k, const DrawRegs &dr, uint32_t path_lo, uint32_t path_hi, uint32_t blk,
                                              uint32_t (&s)[Draws<SMMC_MODE_TABLE, kDense>::value]) {
   uint32_t u[4];
-  philox4x32_10<true>(blk, path_lo, path_hi, mode_tag(SMMC_MODE_TABLE), k.key0, k.key1, dr, u);
+  philox4x32_10<kPhiloxUniformBlock>(blk, path_lo, path_hi, mode_tag(SMMC_MODE_TABLE), k.key0, k.key1, dr, u);
   if constexpr (kDense) {
     uint32_t ia[4], ib[4];
     digits4(u[0], u[1], k.table_len, ia);
@@ -1213,7 +1398,7 @@ __device__ __forceinline__ void walk_periods(const KernelArgs &k, const DrawRegs
       k.n_periods,
       [&](uint32_t blk) {
         prefetch(blk);
-        block_multipliers<kMode, kDense, true>(k, dr, lds_table, path_lo, path_hi, blk, a);
+        block_multipliers<kMode, kDense, kPhiloxUniformBlock>(k, dr, lds_table, path_lo, path_hi, blk, a);
       },
       [&](int j, uint32_t t) { step(j, a[j], t); });
 }
@@ -1427,7 +1612,7 @@ void checkpoints_kernel(const KernelArgs k, const CheckpointArgs c) {
     uint32_t ck = 0, next_p = c.periods[0];
     for (uint32_t blk = 0; blk < n_blocks; ++blk) {
       float a[kDraws];
-      block_multipliers<kMode, kDense, true>(k, dr, s.table, path_lo, path_hi, blk, a);
+      block_multipliers<kMode, kDense, kPhiloxUniformBlock>(k, dr, s.table, path_lo, path_hi, blk, a);
       const uint32_t p_end = (blk + 1) * kDraws;  // periods done after this block
       if (next_p > p_end && p_end <= k.n_periods) {  // uniform: no checkpoint inside, not the partial block
 #pragma unroll
@@ -2395,7 +2580,7 @@ void cashflow_sweep_kernel(const KernelArgs k, const SweepArgs c) {
 // block_starts' with table_len = n_rows -- the indices SMMC_MODE_TABLE draws -- and one Philox block serves D periods of
 // all assets.
 // Gaussian mode.  K Philox blocks per four periods, (blk, id lo, id hi, 1 + 2 j): they differ in a compile-time word
-// only, so the scalarised first rounds of philox4x32_10<true> apply to each, and philox4x32_10_multi interleaves the K
+// only, so the scalarised first rounds of philox4x32_10<kPhiloxUniformBlock> apply to each, and philox4x32_10_multi interleaves the K
 // chains.  The v3 tables are staged once with gauss_std = 1.0f, the draw's additive term is 0.0f (the host sets both):
 // multipliers_of_words_multi then yields STANDARD normals, and the multiplier is the contract's chain of fused
 // multiply-adds over L's row, j = 0 upwards from s_k.  The additions of V_t are __fadd_rn, the weight products
@@ -3297,6 +3482,9 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(paths_kernel<SMMC_MODE_GAUSSIAN, kDivFast, false>),
       reinterpret_cast<const void *>(paths_kernel<SMMC_MODE_GAUSSIAN, kDivExact, false>),
       reinterpret_cast<const void *>(paths_kernel<SMMC_MODE_GAUSSIAN, kDivChecked, false>),
+      reinterpret_cast<const void *>(paths_hi_kernel<SMMC_MODE_GAUSSIAN, kDivFast, false>),
+      reinterpret_cast<const void *>(paths_hi_kernel<SMMC_MODE_GAUSSIAN, kDivExact, false>),
+      reinterpret_cast<const void *>(paths_hi_kernel<SMMC_MODE_GAUSSIAN, kDivChecked, false>),
       reinterpret_cast<const void *>(keepdata_kernel<SMMC_MODE_GAUSSIAN, false, false, 32>),
       reinterpret_cast<const void *>(keepdata_kernel<SMMC_MODE_GAUSSIAN, true, false, 32>),
       reinterpret_cast<const void *>(keepdata_kernel<SMMC_MODE_GAUSSIAN, false, false, 16>),
@@ -3430,6 +3618,26 @@ static hipError_t launch_paths_mode(const KernelArgs &a, int div, uint32_t grid,
   }
 }
 
+// paths_hi_kernel in paths_kernel's place: same grid, workgroup and LDS
+template <int kMode, int kDiv, bool kDense>
+static hipError_t launch_paths_hi_variant(const KernelArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  constexpr uint32_t kHalves = paths_halves(kMode);
+  hipError_t err = allow_lds(paths_hi_kernel<kMode, kDiv, kDense>, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((paths_hi_kernel<kMode, kDiv, kDense>), dim3((grid + kHalves - 1) / kHalves), dim3(kBlock * kHalves), lds,
+                     stream, a, grid);
+  return hipGetLastError();
+}
+
+template <int kMode, bool kDense>
+static hipError_t launch_paths_hi_mode(const KernelArgs &a, int div, uint32_t grid, size_t lds, hipStream_t stream) {
+  switch (div) {
+    case SMMC_DIV_FAST: return launch_paths_hi_variant<kMode, kDivFast, kDense>(a, grid, lds, stream);
+    case SMMC_DIV_CHECKED: return launch_paths_hi_variant<kMode, kDivChecked, kDense>(a, grid, lds, stream);
+    default: return launch_paths_hi_variant<kMode, kDivExact, kDense>(a, grid, lds, stream);
+  }
+}
+
 bool table_is_dense(uint32_t table_len) { return table_len <= kDenseMaxTable; }
 
 template <int kMode, bool kDense>
@@ -3458,6 +3666,9 @@ hipError_t launch_draw_words(const KernelArgs &a, const uint32_t *d_words, uint6
 }
 
 hipError_t launch_paths(const KernelArgs &a, int div, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
+  if (paths_form(a))  // every path of the launch has the same id bits 63..32: stream v3, Gaussian or a dense table
+    return a.mode != SMMC_MODE_TABLE ? launch_paths_hi_mode<SMMC_MODE_GAUSSIAN, false>(a, div, grid, lds_bytes, stream)
+                                     : launch_paths_hi_mode<SMMC_MODE_TABLE, true>(a, div, grid, lds_bytes, stream);
   if (a.mode != SMMC_MODE_TABLE)
     return a.stream == 2 ? launch_paths_mode<kModeGaussianV2, false>(a, div, grid, lds_bytes, stream)
                          : launch_paths_mode<SMMC_MODE_GAUSSIAN, false>(a, div, grid, lds_bytes, stream);

@@ -370,12 +370,19 @@ class Engine:
         """Before enqueuing: launches go to the caller's CURRENT torch stream (a "torch" engine
         re-binds on every call: the caller may be inside `with torch.cuda.stream(s)` now), or the
         engine's own stream first waits for it (its outputs were just allocated there)."""
+        self._uniform_hi_from_env()
         cur = int(self._torch.cuda.current_stream(self.tdevice).cuda_stream)
         if self.follow_torch:
             _lib.check(self._L.smmc_engine_set_stream(self._h, C.c_void_p(cur)))
         elif self.own_stream:
             _lib.check(self._L.smmc_engine_wait_stream(self._h, C.c_void_p(cur)))
         return cur
+
+    def _uniform_hi_from_env(self):
+        """SMMC_UNIFORM_HI (0 | 1, default 1), read before every call: the library itself has the switch as a call
+        (smmc_set_uniform_hi), this wrapper maps the variable onto it so that a whole run -- bench.py, a profile of
+        the generic kernel -- is switched from outside.  Anything but "0" leaves the default."""
+        _lib.check(self._L.smmc_set_uniform_hi(0 if os.environ.get("SMMC_UNIFORM_HI", "1").strip() == "0" else 1))
 
     def _leave(self, cur, *tensors):
         """After enqueuing on an engine-owned stream: torch's current stream waits for the engine's
@@ -1659,6 +1666,16 @@ class Engine:
         """DIV_FAST / DIV_EXACT / DIV_CHECKED: which divide-by-100 a launch of `sim` uses (results
         never depend on it)."""
         rc = self._L.smmc_engine_divide_kind(self._h, C.byref(sim), 1 if keepdata else 0)
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    def paths_form(self, sim):
+        """1 when a `simulate` launch of `sim` gets the kernel that holds the path id's bits 63..32 in a scalar
+        register (every path of the launch shares them, counter stream v3, SMMC_UNIFORM_HI not 0), else 0
+        (results never depend on it)."""
+        self._uniform_hi_from_env()
+        rc = self._L.smmc_engine_paths_form(self._h, C.byref(sim))
         if rc < 0:
             _lib.check(rc)
         return rc

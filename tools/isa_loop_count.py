@@ -7,7 +7,7 @@ there equal what this counts in the kernels as built.  The weighted figure (meas
 costs relative to a plain VALU op, profiles/r01/ubench_instruction_rates.txt) is printed for
 reading only: it over-counted in round 1 (fractions above 1) and is no longer reported.
 
-usage: isa_loop_count.py [kernels.s] <variant> [periods]     variant e.g. ILi1ELi0ELb0E
+usage: isa_loop_count.py [kernels.s] <variant> [periods]     variant e.g. ILi1ELi0ELb0E, gaussian, hi:gaussian
 """
 import os
 import subprocess
@@ -21,6 +21,11 @@ W = {'v_pk_fma_f32': 1.9, 'v_pk_mul_f32': 1.9, 'v_pk_add_f32': 1.9, 'v_mad_u64_u
 # paths_kernel<mode, div, dense>: (template arguments as mangled, periods per Philox block)
 VARIANTS = {"gaussian": ("ILi1ELi0ELb0E", 4), "table": ("ILi0ELi0ELb1E", 8),
             "gaussian_checked": ("ILi1ELi2ELb0E", 4), "table_checked": ("ILi0ELi2ELb1E", 8)}
+# paths_hi_kernel<mode, div, dense>, what a launch inside one multiple of 2^32 path ids runs: count(path, variant, HI_KERNEL)
+HI_KERNEL = "paths_hi_kernel"
+HI_VARIANTS = {"gaussian": ("ILi1ELi0ELb0E", 4), "table": ("ILi0ELi0ELb1E", 8),
+               "gaussian_checked": ("ILi1ELi2ELb0E", 4), "table_checked": ("ILi0ELi2ELb1E", 8),
+               "gaussian_exact": ("ILi1ELi1ELb0E", 4), "table_exact": ("ILi0ELi1ELb1E", 8)}
 
 
 def emit_asm(out_path, source="smmc_kernels.hip"):
@@ -129,9 +134,12 @@ if __name__ == "__main__":
         path = emit_asm("/tmp/smmc_kernels.s")
     variant = args[0]
     periods = int(args[1]) if len(args) > 1 else 4
-    if variant in VARIANTS:
+    kernel = "paths_kernel"
+    if variant.startswith("hi:") and variant[3:] in HI_VARIANTS:  # e.g. hi:gaussian
+        kernel, (variant, periods) = HI_KERNEL, HI_VARIANTS[variant[3:]]
+    elif variant in VARIANTS:
         variant, periods = VARIANTS[variant]
-    c = count(path, variant)
+    c = count(path, variant, kernel)
     tot = sum(n * W.get(k, 1.0) for k, n in c.items() if k.startswith('v_') or k.startswith('ds_'))
     print(f"{variant}: {valu(c)} VALU + {lds(c)} LDS per {periods} periods "
           f"({valu(c) / periods:.2f} VALU/period); weighted {tot:.1f} -> {tot / periods:.1f} issue units per path-period")
