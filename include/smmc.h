@@ -889,6 +889,63 @@ int smmc_engine_simulate_guardrails(smmc_engine *e, const smmc_sim *sim, const s
 int smmc_engine_simulate_guardrails_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                             const smmc_guardrails *gr, const smmc_guardrails_outputs *out);
 
+/* ---- glide paths: target weights that change along a plan -------------------------------------------- */
+
+/* "90/10 at 30, 40/60 at 70" (a target-date glide path, a bond tent, a rising equity glide path):
+ * smmc_engine_simulate_portfolio_cashflow with a list of later target-weight vectors.  sim, pf, cf and the outputs keep
+ * that call's meaning, checks, draws, records, depletion counts and shard merging; pf->weights are the targets at the
+ * start.  It cannot be composed from outside: with a rebalance and a flow the value after a change of weights is no
+ * function of two separate runs, and chained runs would restart the per-path draw counters.  Counter stream v3 only. */
+#define SMMC_MAX_GLIDE_CHANGES 512
+typedef struct smmc_glide {
+  uint32_t struct_size;   /* = sizeof(smmc_glide) */
+  uint32_t n_changes;     /* 0 .. SMMC_MAX_GLIDE_CHANGES */
+  const uint32_t *after;  /* HOST, n_changes periods, strictly increasing, each >= 1 */
+  const float *weights;   /* HOST, n_changes x SMMC_MAX_ASSETS, row c = the targets from change c on; entries k >= K are 0 */
+} smmc_glide;
+
+/* A path trades at the end of every period t = 0 .. P (P = n_periods): at t = 0 the initial purchase
+ * h_k = fl(capital * w_k), at t >= 1 the trade of smmc_engine_simulate_portfolio_cashflow -- the rebalance
+ * h_k = fl(vn * w_k) or the settlement h_k = fl(h_k - fl(w * w_k)).  EVERY trade at the end of period t uses W(t):
+ *   W(t) = row c of glide->weights for the largest c with after[c] <= t;  pf->weights while t < after[0].
+ * Everything else is that call's recurrence unchanged, each operation one binary32 rounding: the order of operations,
+ * vn > floor, depletion, no rebalance at P, the draws.
+ * What follows from it:
+ *   - A change of targets does NOT trade by itself.  The holdings move to the new targets at the next rebalance, and
+ *     flows settle at the new targets from that period on: put a change on a rebalance period to reallocate right there.
+ *   - A change with after[c] > P is legal and never reached, so the outputs of the first p periods do not depend on
+ *     n_periods beyond that call's own dependence (no rebalance at P).  A change at P acts on the last settlement only:
+ *     it moves the final holdings, not the final value.
+ *   - n_changes == 0, or every row equal to pf->weights, gives smmc_engine_simulate_portfolio_cashflow's six outputs bit
+ *     for bit.
+ *   - Zero flows (amount = fraction = 0, floor = 0, no arrays) with rebalance_every == 0 give
+ *     smmc_engine_simulate_portfolio's final values and holdings bit for bit whatever the changes are: nothing trades.
+ *   - With one asset every legal row is w_0 = 1: the call checks its arguments and is
+ *     smmc_engine_simulate_portfolio_cashflow.
+ *   - A path depends only on (seed, global path id, table or means and factor, pf, glide, schedule, floor), never on
+ *     first_path, the shard or the launch geometry.
+ * Enqueues on the engine stream and returns without waiting; the host arrays of cf and glide may be reused on return.
+ * out as smmc_engine_simulate_portfolio_cashflow takes it (DEVICE pointers, any may be NULL); n_paths == 0 launches
+ * nothing and yields the empty record and zero counts.
+ * SMMC_ERR_INVALID with a text: everything smmc_engine_simulate_portfolio_cashflow refuses; a NULL or wrongly sized
+ * glide; n_changes > SMMC_MAX_GLIDE_CHANGES; NULL after or weights with n_changes > 0; after not strictly increasing or
+ * holding a 0; a row that fails smmc_portfolio's weight checks (negative, not finite, non-zero at k >= K, a sum off 1 by
+ * more than 1e-6 in double). */
+int smmc_engine_simulate_glide(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf,
+                               const smmc_glide *glide, const smmc_portfolio_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_glide_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf,
+                                       const smmc_glide *glide, const smmc_portfolio_cashflow_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT (never SMMC_DIV_CHECKED), or an error of the call's argument checks.  Results never
+ * depend on the form.  FAST only if both hold: (1) every row weights the same set of assets positively as pf->weights
+ * does -- an asset whose target is 0 for a stage is no longer bounded from below by its share, and the holding it keeps
+ * from the stage before shrinks without a bound the host knows; (2) the rule of
+ * smmc_engine_portfolio_cashflow_divide_kind with the smallest positive weight, the smallest share fl(amount * w_k) and
+ * the smallest floor * w_k taken over pf->weights and EVERY row (the rows beyond P too).  Anything else, or
+ * SMMC_FLAG_EXACT_DIV, is the IEEE divide ("Glide paths", carries the proof over). */
+int smmc_engine_glide_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf,
+                                  const smmc_glide *glide);
+
 /* Blocks until everything enqueued on the engine stream has finished. */
 int smmc_engine_sync(smmc_engine *e);
 

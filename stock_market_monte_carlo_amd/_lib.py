@@ -34,6 +34,7 @@ MAX_SWEEP = 8  # most scenarios of a simulate_cashflow_sweep or simulate_allocat
 MAX_SWEEP_COUNTERS = 8192  # largest n_scenarios * (n_periods + 1 + n_bins) of one
 MAX_EXCURSION_PERIODS = 4096  # largest n_periods of a simulate_excursions call
 MAX_ASSETS = 4  # most assets of a simulate_portfolio call
+MAX_GLIDE_CHANGES = 512  # most changes of target weights of a simulate_glide call
 
 
 class Sim(C.Structure):
@@ -158,6 +159,16 @@ class RealCashflowOutputs(C.Structure):
         ("ruin_period", C.c_void_p),
         ("stats", C.c_void_p),
         ("depleted_at", C.c_void_p),
+    ]
+
+
+class Glide(C.Structure):
+    """smmc_glide"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_changes", C.c_uint32),
+        ("after", C.POINTER(C.c_uint32)),
+        ("weights", C.POINTER(C.c_float)),
     ]
 
 
@@ -291,6 +302,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Guardrails), C.POINTER(GuardrailsOutputs)]),
     ("smmc_engine_simulate_guardrails_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Guardrails), C.POINTER(GuardrailsOutputs)]),
+    ("smmc_engine_simulate_glide", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Glide), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_simulate_glide_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Glide), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_glide_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Glide)]),
     ("smmc_engine_simulate_to_host", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     ("smmc_engine_prepare_host", C.c_int, [C.c_void_p, C.c_uint64]),

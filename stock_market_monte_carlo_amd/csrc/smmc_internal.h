@@ -335,6 +335,25 @@ hipError_t launch_guardrails(const KernelArgs &a, const GuardrailsArgs &x, uint3
 // [the padded rows or the draw tables][three arrays of n_periods + 1 counters: depleted, cuts, raises][n_bins buckets]
 // [pad][the waves' partials]
 size_t guardrails_lds_bytes(int32_t mode, uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// glide_kernel (smmc_engine_simulate_glide, csrc/smmc_glide.cpp; counter stream v3 only, K = 2, 3, 4):
+// portfolio_cashflow_kernel's paths with target weights that change along the plan ("Glide paths").  p and c
+// as launch_portfolio_cashflow takes them; p.weights are the targets of period 0 and until the first change.  The
+// changes that fall inside the plan are flattened into `table`, one GlideEntry per change in the order they take effect
+// and one more behind them that is never read into the weights (next = 0, weights 0): a launch without a change has a
+// table of that one entry.
+struct GlideEntry {  // 32 bytes, one scalar load
+  uint32_t next;                   // periods from this change to the next one; 0: there is none, the countdown never ends
+  float weights[SMMC_MAX_ASSETS];  // the targets from this change on; entries k >= K are 0
+  uint32_t pad[3];                 // 0
+};
+static_assert(sizeof(GlideEntry) == 32, "a change is one 32-byte scalar load");
+struct GlideArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  uint32_t first;           // periods until the first change: after[0]; 0: no change inside the plan
+  const GlideEntry *table;  // device, 32-byte aligned, never null
+};
+hipError_t launch_glide(const KernelArgs &a, const GlideArgs &x, bool exact_div, uint32_t grid, hipStream_t stream);
 // allocation_sweep_kernel (smmc_engine_simulate_allocation_sweep, csrc/smmc_allocation_sweep.cpp; counter stream v3
 // only): n constant-schedule strategies (weights, rebalance_every, amount, fraction, floor) stepped on ONE joint draw
 // per period ("Allocation sweeps").  p: the law as launch_portfolio takes it (n_assets, shift100, factor;

@@ -3352,6 +3352,105 @@ void guardrails_kernel(const KernelArgs k, const GuardrailsArgs x) {
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- glide paths: target weights that change along a plan -------------------------------------------
+//
+// smmc_engine_simulate_glide (csrc/smmc_glide.cpp; include/smmc.h and DESIGN.md, "Glide paths", state the contract):
+// portfolio_cashflow_kernel's path -- the same draws, the same portfolio_cashflow_step, called, not restated -- with the
+// weights the step trades at held in an array of the kernel's own, `w`, instead of the kernel argument.  A family of
+// its own: portfolio_cashflow_kernel compiles to what it compiled to before.
+//
+// The changes lie flattened in x.table (GlideEntry, smmc_internal.h), in the order they take effect.  A third scalar
+// countdown beside the rebalance countdown, `left`, starts at x.first = after[0] (0: it never ends) and is decremented
+// before the step of every period; when it hits 0 the next entry is read through the constant address space -- one
+// scalar load of 32 bytes at a uniform address --, its weights go into `w` and its `next` into the countdown.  The
+// branch is wave-uniform (everything it depends on is a kernel argument or came through a scalar load), the weights
+// stay in scalar registers, and there is no per-lane global load and no LDS traffic for it: a period without a change is
+// the parent's step and a scalar decrement and compare.  Per chunk of the wave walk the weights go back to p.weights,
+// the countdown to x.first and the entry index to 0: a wave's second chunk starts from stage 0 again.
+typedef const __attribute__((address_space(4))) GlideEntry *const_glide_ptr;  // scalar (uniform) loads
+
+template <int kMode, bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(kMode))
+void glide_kernel(const KernelArgs k, const GlideArgs x) {
+  static_assert(counter_v3(kMode), "counter stream v3 only");
+  static_assert(K >= 2, "one asset has one legal weight vector: the host launches portfolio_cashflow_kernel");
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = Draws<kMode, kDense>::value;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  if constexpr (is_table(kMode)) staged.table_len = k.table_len * portfolio_row_words(K);
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, walk_table_words<kMode>(staged), k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+  const const_glide_ptr changes = (const_glide_ptr)(x.table);
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    // the chunk starts from stage 0: the weights of the request, the countdown to the first change, the first entry
+    float w[SMMC_MAX_ASSETS];
+#pragma unroll
+    for (int y = 0; y < SMMC_MAX_ASSETS; ++y) w[y] = p.weights[y];
+    uint32_t left = x.first;  // periods until the next change; with first == 0 the countdown never ends
+    uint32_t stage = 0u;      // the entry the next change reads
+    float a[kDraws][K];
+    float am[kDraws], fr[kDraws];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) {
+#pragma unroll
+          for (int j = 0; j < kDraws; ++j) {  // the block's schedule entries (padded to whole blocks)
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+          portfolio_multipliers<kMode, kDense, K>(k, p, dr, s.table, path_lo, path_hi, blk, a);
+        },
+        [&](int j, uint32_t t) {
+          if (--left == 0u) {  // uniform: a change takes effect with the trade at the end of this period
+#pragma unroll
+            for (int y = 0; y < K; ++y) w[y] = changes[stage].weights[y];
+            left = changes[stage].next;
+            ++stage;
+          }
+          portfolio_cashflow_step<kExactDiv, K>(a[j], w, am[j], fr[j], c.floor, every, k.n_periods, t, h, v, paid, ruin, alive, until);
+        });
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 // ---- allocation sweeps: up to eight portfolio strategies on one set of draws ------------------------
 //
 // smmc_engine_simulate_allocation_sweep (csrc/smmc_allocation_sweep.cpp; include/smmc.h and DESIGN.md, "Allocation
@@ -3566,7 +3665,17 @@ hipError_t static_lds_bytes(size_t *bytes) {
       reinterpret_cast<const void *>(guardrails_kernel<SMMC_MODE_TABLE, false, K>)
       SMMC_GUARDRAILS_KERNELS(1), SMMC_GUARDRAILS_KERNELS(2), SMMC_GUARDRAILS_KERNELS(3), SMMC_GUARDRAILS_KERNELS(4),
 #undef SMMC_GUARDRAILS_KERNELS
-#define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                                \
+#define SMMC_GLIDE_KERNELS(K, V)                                                                                            \
+  reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),                                      \
+      reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),                                   \
+      reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_TABLE, false, true, K, V>),                                      \
+      reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_TABLE, true, true, K, V>),                                       \
+      reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_TABLE, false, false, K, V>),                                     \
+      reinterpret_cast<const void *>(glide_kernel<SMMC_MODE_TABLE, true, false, K, V>)
+      SMMC_GLIDE_KERNELS(2, false), SMMC_GLIDE_KERNELS(3, false), SMMC_GLIDE_KERNELS(4, false),
+      SMMC_GLIDE_KERNELS(2, true), SMMC_GLIDE_KERNELS(3, true), SMMC_GLIDE_KERNELS(4, true),
+#undef SMMC_GLIDE_KERNELS
+#define SMMC_ALLOCATION_SWEEP_KERNELS(K, S)                                                                               \
   reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, false, false, K, S>),                           \
       reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_GAUSSIAN, true, false, K, S>),                        \
       reinterpret_cast<const void *>(allocation_sweep_kernel<SMMC_MODE_TABLE, false, true, K, S>),                           \
@@ -4156,6 +4265,32 @@ hipError_t launch_guardrails(const KernelArgs &a, const GuardrailsArgs &x, uint3
   if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
   return launch_wave_walk<GuardrailsFamily>(a, x, true, grid, guardrails_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins),
                                             stream);
+}
+
+// ---- glide paths ----
+
+struct GlideFamily {  // K = 2, 3, 4: one asset is the parent's launch (csrc/smmc_glide.cpp)
+  template <int kMode, bool kExactDiv, bool kDense, int K>
+  static WalkKernel<GlideArgs> schedule(const GlideArgs &x) {
+    return x.c.schedule ? glide_kernel<kMode, kExactDiv, kDense, K, true> : glide_kernel<kMode, kExactDiv, kDense, K, false>;
+  }
+  template <int kMode, bool kExactDiv, bool kDense>
+  static WalkKernel<GlideArgs> get(const GlideArgs &x) {
+    switch (x.p.n_assets) {
+      case 2: return schedule<kMode, kExactDiv, kDense, 2>(x);
+      case 3: return schedule<kMode, kExactDiv, kDense, 3>(x);
+      default: return schedule<kMode, kExactDiv, kDense, 4>(x);
+    }
+  }
+};
+hipError_t launch_glide(const KernelArgs &a, const GlideArgs &x, bool exact_div, uint32_t grid, hipStream_t stream) {
+  if (a.stream != 3 || x.p.n_assets < 2 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.mode == SMMC_MODE_TABLE ? (!a.table_len || !a.table_a) : (a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f)) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
+  if (!x.table || reinterpret_cast<uintptr_t>(x.table) % sizeof(GlideEntry) != 0u || x.first > a.n_periods) return hipErrorInvalidValue;
+  return launch_wave_walk<GlideFamily>(a, x, exact_div, grid,
+                                       portfolio_cashflow_lds_bytes(a.mode, a.table_len, x.p.n_assets, a.n_periods, a.n_bins), stream);
 }
 
 // ---- allocation sweeps ----

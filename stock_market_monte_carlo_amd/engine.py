@@ -322,6 +322,32 @@ class GuardrailsResult(PortfolioCashflowResult):
         return np.cumsum(np.asarray(self.cuts_at, dtype=np.float64)) / self.n_paths
 
 
+def glide_linear(w_from, w_to, first, last, every=1):
+    """The `changes` list of Engine.simulate_glide for a straight-line glide: the targets are `w_from` at period `first`,
+    `w_to` at period `last` and move between them in steps of `every` periods -- rows at first, first + every, ... below
+    `last`, and one at `last`.  The two end rows are the inputs as float32, unchanged; the rows between are interpolated
+    in double, cast to float32 and renormalised so that each sums to 1 well within the library's 1e-6.  With first == 0
+    the first row is left out: before the first change the call's own `weights` hold, so pass w_from there."""
+    a, b = np.asarray(w_from, dtype=np.float32).ravel(), np.asarray(w_to, dtype=np.float32).ravel()
+    first, last, every = int(first), int(last), int(every)
+    if a.size != b.size or a.size == 0:
+        raise ValueError("w_from and w_to must have the same number of weights")
+    if not (0 <= first < last) or every < 1:
+        raise ValueError("glide_linear needs 0 <= first < last and every >= 1")
+    out = []
+    for t in range(first, last, every):
+        if t == first:
+            row = a.copy()
+        else:
+            mix = (a.astype(np.float64) * (last - t) + b.astype(np.float64) * (t - first)) / (last - first)
+            row = (mix / mix.sum()).astype(np.float32)
+            row = (row.astype(np.float64) / row.astype(np.float64).sum()).astype(np.float32)
+        if t >= 1:
+            out.append((t, row))
+    out.append((last, b.copy()))
+    return out
+
+
 def cholesky_factor(stds, corr):
     """The lower-triangular factor L (float32 [K, K], percent) of diag(stds) corr diag(stds), for
     Engine.simulate_portfolio(factor=...): numpy's float64 Cholesky, cast once.  Raises ValueError for a matrix that
@@ -1091,6 +1117,110 @@ class Engine:
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rc = self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
         del keep
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
+    # -- glide paths: target weights that change along a plan (smmc_engine_simulate_glide) ---------------------------
+    @staticmethod
+    def make_glide(changes):
+        """smmc_glide from a list of (after, weights); returns (structure, what must stay alive while it is used).  The
+        library checks the periods and the rows."""
+        changes = list(changes or ())
+        after = np.ascontiguousarray([int(a) for a, _ in changes], dtype=np.uint32)
+        rows = np.zeros((len(changes), _lib.MAX_ASSETS), dtype=np.float32)
+        for c, (_, w) in enumerate(changes):
+            w = np.asarray(w, dtype=np.float32).ravel()
+            if w.size > _lib.MAX_ASSETS:
+                raise ValueError("a row of a glide path has at most %d weights" % _lib.MAX_ASSETS)
+            rows[c, :w.size] = w
+        gl = _lib.Glide()
+        gl.struct_size = C.sizeof(_lib.Glide)
+        gl.n_changes = len(changes)
+        if changes:
+            gl.after = after.ctypes.data_as(C.POINTER(C.c_uint32))
+            gl.weights = rows.ctypes.data_as(C.POINTER(C.c_float))
+        return gl, (after, rows)
+
+    def simulate_glide(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                       fractions=None, means=None, factor=None, want_final=True, want_holdings=False, want_paid=False,
+                       want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """simulate_portfolio_cashflow with target weights that change along the plan: `changes` is a list of
+        (after, weights), strictly increasing in `after` >= 1; every trade at the end of period t -- a rebalance or the
+        settlement of the flow -- uses the row of the last change with after <= t, `weights` before the first.  A change
+        does not trade by itself: put it on a rebalance period to reallocate right there.  glide_linear() makes the list of
+        a straight-line glide.  Returns a PortfolioCashflowResult, so survival() works as there; include/smmc.h states
+        the arithmetic."""
+        raw = self.simulate_glide_raw(sim, weights, changes, rebalance_every, amount, fraction, floor, amounts, fractions, means,
+                                      factor, want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at)
+        res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                      n_assets=raw["n_assets"], holdings=raw["holdings"])
+        if want_stats or want_depleted_at:
+            self.sync()
+        if want_stats:
+            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
+            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
+        if want_depleted_at:
+            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
+        return res
+
+    def simulate_glide_raw(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                           fractions=None, means=None, factor=None, want_final=True, want_holdings=False, want_paid=False,
+                           want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict."""
+        torch = self._torch
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        gl, keep_gl = self.make_glide(changes)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
+               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
+               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            t = res[key]
+            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        cur = self._enter()
+        _lib.check(self._L.smmc_engine_simulate_glide(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o)))
+        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        del keep, keep_gl
+        return res
+
+    def simulate_glide_to_host(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                               fractions=None, means=None, factor=None, want_final=True, want_holdings=False, want_paid=False,
+                               want_ruin_period=False, want_stats=False, want_depleted_at=True):
+        """The same through smmc_engine_simulate_glide_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        gl, keep_gl = self.make_glide(changes)
+        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
+        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
+        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
+               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
+               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
+               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
+        o = _lib.PortfolioCashflowOutputs()
+        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
+        for name, key in self._PFCF_OUTPUTS:
+            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
+        self._enter()
+        _lib.check(self._L.smmc_engine_simulate_glide_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o)))
+        del keep, keep_gl
+        if want_stats:
+            res["stats_raw"] = res["stats_raw"].tobytes()
+        return res
+
+    def glide_divide_kind(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
+                          fractions=None, means=None, factor=None):
+        """_lib.DIV_FAST or DIV_EXACT: the divide simulate_glide uses for this request (results never depend on it)."""
+        pf = self.make_portfolio(weights, rebalance_every, means, factor)
+        gl, keep_gl = self.make_glide(changes)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        rc = self._L.smmc_engine_glide_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl))
+        del keep, keep_gl
         if rc < 0:
             _lib.check(rc)
         return rc
