@@ -364,6 +364,63 @@ def cholesky_factor(stds, corr):
         raise ValueError("the covariance matrix is not positive definite") from err
 
 
+# ---------------------------------------------------------------------------
+# The outputs of the feature entries, stated once: Engine._outputs allocates from these tables and fills the outputs
+# structure, Engine._read_back decodes what a simulate_X reads back.  A new feature adds its rows and its short entries.
+# ---------------------------------------------------------------------------
+
+# An output kind: torch dtype (by name) on the device, numpy dtype on the host, device elements per host element.
+_Kind = collections.namedtuple("_Kind", "torch numpy unit")
+_FLOAT = _Kind("float32", np.float32, 1)  # per-path float
+_UINT = _Kind("int32", np.uint32, 1)      # per-path uint32: int32 holding the uint32 values on the device
+_RECORD = _Kind("uint8", np.uint64, 8)    # packed record(s): smmc_stats_bytes(n_bins) bytes on the device; uint64 on the host, handed back as bytes
+_COUNTS = _Kind("int64", np.uint64, 1)    # count array: int64 holding the uint64 counts on the device
+
+# What a shape is a function of: paths, periods, assets, the sweeps' leading scenario dimension -- () or (S,) --, bytes of a record.
+_Dims = collections.namedtuple("_Dims", "n p K S rec")
+
+# field of an outputs structure (or C parameter of the entries that take loose pointers) -> (kind, shape without S)
+_OUTPUT = {"holdings": (_FLOAT, lambda d: (d.K, d.n)),
+           "chunk_mean": (_FLOAT, lambda d: ((d.n + _lib.CHUNK - 1) // _lib.CHUNK,)),
+           "chunk_var": (_FLOAT, lambda d: ((d.n + _lib.CHUNK - 1) // _lib.CHUNK,))}
+_OUTPUT.update({f: (_FLOAT, lambda d: (d.n,)) for f in ("final", "final_real", "index", "paid", "amount_last", "amount_lowest", "peak", "low",
+                                                       "drawdown")})
+_OUTPUT.update({f: (_UINT, lambda d: (d.n,)) for f in ("ruin_period", "cuts", "raises", "drawdown_period", "underwater", "first_below",
+                                                      "first_reach")})
+_OUTPUT.update({f: (_RECORD, lambda d: (d.rec,)) for f in ("stats", "drawdown_stats")})
+_OUTPUT.update({f: (_COUNTS, lambda d: (d.p + 1,)) for f in ("depleted_at", "cuts_at", "raises_at", "first_below_at", "first_reach_at")})
+
+
+def _rows(fields, stats_key="stats_raw"):
+    """The output table of a structure or a parameter list: rows (field, result key, kind, shape), in the C order."""
+    return tuple((f, stats_key if f == "stats" else f) + _OUTPUT[f] for f in fields)
+
+
+def _pointer_fields(struct):
+    return tuple(name for name, _ in struct._fields_ if name not in ("struct_size", "reserved"))
+
+
+_CASHFLOW_ROWS = _rows(("final", "paid", "ruin_period", "stats", "depleted_at"))  # loose pointers: cashflow, cashflow_sweep
+_BLOCKS_ROWS = _rows(("final", "chunk_mean", "chunk_var", "stats"))               # loose pointers: blocks
+_PORTFOLIO_ROWS = _rows(_pointer_fields(_lib.PortfolioOutputs))
+_PFCF_ROWS = _rows(_pointer_fields(_lib.PortfolioCashflowOutputs))                # and smmc_allocation_sweep_outputs
+_REAL_ROWS = _rows(_pointer_fields(_lib.RealCashflowOutputs))
+_GUARDRAILS_ROWS = _rows(_lib.GUARDRAILS_OUTPUTS)
+_EXCURSION_ROWS = _rows(_lib.EXCURSION_OUTPUTS, stats_key="stats")
+
+
+def _buffers(rows, res):
+    return [res[key] for _, key, _, _ in rows]
+
+
+def _records_as_bytes(rows, res):
+    """The host flavour's last step, after the C call: a record is handed back as bytes."""
+    for _, key, kind, _ in rows:
+        if kind is _RECORD and res[key] is not None:
+            res[key] = res[key].tobytes()
+    return res
+
+
 class Engine:
     """One engine per (process, device): table, workspace and stream stay resident."""
 
@@ -591,6 +648,78 @@ class Engine:
         self.sync()
         return raw.cpu().numpy()[: per.size * rec].tobytes(), (final.cpu().numpy() if final is not None else None)
 
+    # -- the binding layer of the feature entries (the tables above) ---------------------------------------------------
+    def _new(self, kind, shape, host):
+        """One output buffer: zeroed numpy on the host, uninitialised torch on the engine's device; `shape` counts device
+        elements."""
+        if host:
+            return np.zeros(shape[:-1] + (shape[-1] // kind.unit,), dtype=kind.numpy)
+        return self._torch.empty(shape, dtype=getattr(self._torch, kind.torch), device=self.tdevice)
+
+    def _outputs(self, rows, struct, sim, wants, host, K=0, S=None, head=None, given=None, host_null_empty=False):
+        """Allocates what `wants` (one flag per row) asks for: (result dict -- `head`, then the rows' keys, None for what is
+        not wanted --, `struct` filled with the addresses, or for struct None the list of pointer arguments).  `given` maps
+        a key to a caller's buffer to use in place of a new one (None: none).  A device output without elements is passed
+        as a null pointer; a host one only with host_null_empty."""
+        d = _Dims(int(sim.n_paths), int(sim.n_periods), int(K), () if S is None else (int(S),), int(self._L.smmc_stats_bytes(sim.n_bins)))
+        assert len(wants) == len(rows)
+        res, addresses = dict(head or {}), []
+        for (field, key, kind, shape), want in zip(rows, wants):
+            buf = (given or {}).get(key) if want else None
+            if want and buf is None:
+                buf = self._new(kind, d.S + shape(d), host)
+            res[key] = buf
+            if buf is None:
+                addresses.append(None)
+            elif host:
+                addresses.append(buf.ctypes.data if buf.size or not host_null_empty else None)
+            else:
+                addresses.append(buf.data_ptr() if buf.numel() else None)
+        if struct is None:
+            return res, [None if a is None else C.c_void_p(a) for a in addresses]
+        o = struct()
+        o.struct_size = C.sizeof(struct)
+        for (field, _, _, _), a in zip(rows, addresses):
+            setattr(o, field, a)
+        return res, o
+
+    def _run(self, entry, *args, device=None):
+        """The stream discipline around the one C call of an entry; `device`: the tensors it writes (a _to_host entry has
+        none, the call has drained its streams when it returns)."""
+        cur = self._enter()
+        _lib.check(entry(self._h, *args))
+        if device is not None:
+            self._leave(cur, *device)
+
+    def _read_back(self, res, sim, raw, rows, n_records=None, also=(), ranges=None):
+        """Finishes a simulate_X: the rows' records and count arrays that `raw` holds go to the host and into `res`, under
+        the field's name -- a record as Stats (n_records given: a list of so many) with sim's bucket range, or the one
+        `ranges` names for the field; a count array as a uint64 copy.  `also`: further (attribute, key, kind, n_records).
+        Waits for the engine only if there is something to read."""
+        items = [(field, key, kind, n_records) for field, key, kind, _ in rows if kind in (_RECORD, _COUNTS)] + list(also)
+        items = [item for item in items if raw[item[1]] is not None]
+        if items:
+            self.sync()
+        rec = int(self._L.smmc_stats_bytes(sim.n_bins))
+        for attr, key, kind, count in items:
+            if kind is _COUNTS:
+                setattr(res, attr, raw[key].cpu().numpy().view(np.uint64).copy())
+                continue
+            host, out = raw[key].cpu().numpy().tobytes(), []
+            for k in range(1 if count is None else count):
+                st = stats_from_bytes(host[k * rec:(k + 1) * rec])
+                st.hist_lo, st.hist_hi = (ranges or {}).get(attr, (float(sim.hist_lo), float(sim.hist_hi)))
+                out.append(st)
+            setattr(res, attr, out[0] if count is None else out)
+        return res
+
+    @staticmethod
+    def _kind(rc):
+        """The tail of a *_divide_kind call: a negative return is the library's error."""
+        if rc < 0:
+            _lib.check(rc)
+        return rc
+
     # -- cash flows: withdrawal and contribution schedules (smmc_engine_simulate_cashflow) ------------
     @staticmethod
     def make_cashflow(n_periods, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0):
@@ -620,14 +749,7 @@ class Engine:
         raw = self.simulate_cashflow_raw(sim, amount, fraction, amounts, fractions, floor, want_final, want_paid,
                                          want_ruin_period, want_stats, want_depleted_at)
         res = CashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _CASHFLOW_ROWS)
 
     def simulate_cashflow_raw(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0,
                               want_final=True, want_paid=False, want_ruin_period=False, want_stats=False,
@@ -635,20 +757,10 @@ class Engine:
         """Enqueues the call and returns its device tensors without waiting: a dict with final, paid (float32),
         ruin_period (int32 holding uint32 values), stats_raw (uint8, the packed record) and depleted_at (int64
         holding uint64 counts, n_periods + 1); None for what was not asked for."""
-        torch = self._torch
-        n, p = int(sim.n_paths), int(sim.n_periods)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, count, dtype: torch.empty(count, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        out = {"final": new(want_final, n, torch.float32), "paid": new(want_paid, n, torch.float32),
-               "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_cashflow(
-            self._h, C.byref(sim), C.byref(cf), ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
-            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
-        self._leave(cur, *out.values())
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        out, ptrs = self._outputs(_CASHFLOW_ROWS, None, sim, (want_final, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                  host=False)
+        self._run(self._L.smmc_engine_simulate_cashflow, C.byref(sim), C.byref(cf), *ptrs, device=_buffers(_CASHFLOW_ROWS, out))
         del keep
         return out
 
@@ -656,31 +768,17 @@ class Engine:
                                   want_final=True, want_paid=False, want_ruin_period=False, want_stats=False,
                                   want_depleted_at=True):
         """The same through smmc_engine_simulate_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
-        n, p = int(sim.n_paths), int(sim.n_periods)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, count, dtype: np.zeros(count, dtype=dtype) if want else None  # noqa: E731
-        out = {"final": new(want_final, n, np.float32), "paid": new(want_paid, n, np.float32),
-               "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_cashflow_to_host(
-            self._h, C.byref(sim), C.byref(cf), ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
-            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        out, ptrs = self._outputs(_CASHFLOW_ROWS, None, sim, (want_final, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                  host=True)
+        self._run(self._L.smmc_engine_simulate_cashflow_to_host, C.byref(sim), C.byref(cf), *ptrs)
         del keep
-        if want_stats:
-            out["stats_raw"] = out["stats_raw"].tobytes()
-        return out
+        return _records_as_bytes(_CASHFLOW_ROWS, out)
 
     def cashflow_divide_kind(self, sim, amount=0.0, fraction=0.0, amounts=None, fractions=None, floor=0.0):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_cashflow uses for this request (results never depend on it)."""
-        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
-        rc = self._L.smmc_engine_cashflow_divide_kind(self._h, C.byref(sim), C.byref(cf))
-        del keep
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)  # keep lives until the return
+        return self._kind(self._L.smmc_engine_cashflow_divide_kind(self._h, C.byref(sim), C.byref(cf)))
 
     # -- cash-flow sweeps: up to MAX_SWEEP constant schedules on the same paths (smmc_engine_simulate_cashflow_sweep) ----
     @staticmethod
@@ -709,70 +807,36 @@ class Engine:
                                                want_stats, want_depleted_at)
         _, am, fr, fl = self.make_sweep(amounts, fractions, floors)
         res = SweepResult(int(sim.n_paths), int(sim.n_periods), am, fr, fl, raw["final"], raw["paid"], raw["ruin_period"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            host, rec = raw["stats_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
-            res.stats = []
-            for s in range(am.size):
-                st = stats_from_bytes(host[s * rec:(s + 1) * rec])
-                st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-                res.stats.append(st)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _CASHFLOW_ROWS, n_records=am.size)
 
     def simulate_cashflow_sweep_raw(self, sim, amounts, fractions=0.0, floors=0.0, want_final=False, want_paid=False,
                                     want_ruin_period=False, want_stats=False, want_depleted_at=True):
         """Enqueues the sweep and returns its device tensors without waiting: a dict with final, paid (float32
         [S, n_paths]), ruin_period (int32 holding uint32 values), stats_raw (uint8 [S, smmc_stats_bytes(n_bins)]) and
         depleted_at (int64 holding uint64 counts, [S, n_periods + 1]); None for what was not asked for."""
-        torch = self._torch
-        n, p = int(sim.n_paths), int(sim.n_periods)
         cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
         S = int(am.size)
-        new = lambda want, count, dtype: torch.empty((S, count), dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        out = {"final": new(want_final, n, torch.float32), "paid": new(want_paid, n, torch.float32),
-               "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_cashflow_sweep(
-            self._h, C.byref(sim), cfs, S, ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
-            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
-        self._leave(cur, *out.values())
+        out, ptrs = self._outputs(_CASHFLOW_ROWS, None, sim, (want_final, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                  host=False, S=S)
+        self._run(self._L.smmc_engine_simulate_cashflow_sweep, C.byref(sim), cfs, S, *ptrs, device=_buffers(_CASHFLOW_ROWS, out))
         return out
 
     def simulate_cashflow_sweep_to_host(self, sim, amounts, fractions=0.0, floors=0.0, want_final=False, want_paid=False,
                                         want_ruin_period=False, want_stats=False, want_depleted_at=True):
         """The same through smmc_engine_simulate_cashflow_sweep_to_host: a dict of numpy arrays, scenario-major
         (stats_raw: the S packed records as bytes)."""
-        n, p = int(sim.n_paths), int(sim.n_periods)
         cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
         S = int(am.size)
-        new = lambda want, count, dtype: np.zeros((S, count), dtype=dtype) if want else None  # noqa: E731
-        out = {"final": new(want_final, n, np.float32), "paid": new(want_paid, n, np.float32),
-               "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_cashflow_sweep_to_host(
-            self._h, C.byref(sim), cfs, S, ptr(out["final"]), ptr(out["paid"]), ptr(out["ruin_period"]),
-            ptr(out["stats_raw"]), ptr(out["depleted_at"])))
-        if want_stats:
-            out["stats_raw"] = out["stats_raw"].tobytes()
-        return out
+        out, ptrs = self._outputs(_CASHFLOW_ROWS, None, sim, (want_final, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                  host=True, S=S)
+        self._run(self._L.smmc_engine_simulate_cashflow_sweep_to_host, C.byref(sim), cfs, S, *ptrs)
+        return _records_as_bytes(_CASHFLOW_ROWS, out)
 
     def cashflow_sweep_divide_kind(self, sim, amounts, fractions=0.0, floors=0.0):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_cashflow_sweep uses for this request: FAST only if every
         scenario's own rule says so (results never depend on it)."""
         cfs, am, _, _ = self.make_sweep(amounts, fractions, floors)
-        rc = self._L.smmc_engine_cashflow_sweep_divide_kind(self._h, C.byref(sim), cfs, int(am.size))
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_cashflow_sweep_divide_kind(self._h, C.byref(sim), cfs, int(am.size)))
 
     # -- excursions: drawdown, running extremes, first passage of levels (smmc_engine_simulate_excursions) --------
     _EXCURSION_WANTS = dict(final=True, peak=False, low=False, drawdown=False, drawdown_period=False, underwater=False,
@@ -787,12 +851,13 @@ class Engine:
         return x
 
     def _excursion_wants(self, wants):
+        """The want_<name> arguments over the defaults: one flag per row of _EXCURSION_ROWS."""
         full = dict(self._EXCURSION_WANTS)
         for key, val in wants.items():
             if not key.startswith("want_") or key[5:] not in full:
                 raise TypeError(f"unknown argument {key!r}")
             full[key[5:]] = bool(val)
-        return full
+        return [full[field] for field in _lib.EXCURSION_OUTPUTS]
 
     def simulate_excursions(self, sim, lower, target, drawdown_threshold=0.2, **wants):
         """One simulation reduced ALONG every path: running peak and low, the deepest relative drawdown and its
@@ -800,69 +865,28 @@ class Engine:
         `target`.  want_<name>=True / False selects the outputs (names: the fields of ExcursionResult; by default
         final, drawdown_stats and the two count arrays).  Per-path outputs stay on the device; the records and count
         arrays are read back (that waits).  include/smmc.h states the arithmetic."""
-        full = self._excursion_wants(wants)
+        self._excursion_wants(wants)
         raw = self.simulate_excursions_raw(sim, lower, target, drawdown_threshold, **wants)
         res = ExcursionResult(int(sim.n_paths), int(sim.n_periods),
                               **{k: raw[k] for k in _lib.EXCURSION_OUTPUTS[:8]})
-        if any(full[k] for k in _lib.EXCURSION_OUTPUTS[8:]):
-            self.sync()
-        if full["stats"]:
-            res.stats = stats_from_bytes(raw["stats"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if full["drawdown_stats"]:
-            res.drawdown_stats = stats_from_bytes(raw["drawdown_stats"].cpu().numpy().tobytes())
-            res.drawdown_stats.hist_lo, res.drawdown_stats.hist_hi = 0.0, 1.0
-        for k in ("first_below_at", "first_reach_at"):
-            if full[k]:
-                setattr(res, k, raw[k].cpu().numpy().view(np.uint64).copy())
-        return res
+        return self._read_back(res, sim, raw, _EXCURSION_ROWS, ranges={"drawdown_stats": (0.0, 1.0)})
 
     def simulate_excursions_raw(self, sim, lower, target, drawdown_threshold=0.2, **wants):
         """Enqueues the call and returns its device tensors without waiting: a dict keyed by the fields of
         smmc_excursion_outputs -- float32 / int32 (holding uint32 values) [n_paths], uint8 packed records, int64
         (holding uint64 counts) [n_periods + 1]; None for what was not asked for."""
-        torch = self._torch
-        full = self._excursion_wants(wants)
-        n, p = int(sim.n_paths), int(sim.n_periods)
-        rec = int(self._L.smmc_stats_bytes(sim.n_bins))
-        shape = {"final": (n, torch.float32), "peak": (n, torch.float32), "low": (n, torch.float32),
-                 "drawdown": (n, torch.float32), "drawdown_period": (n, torch.int32), "underwater": (n, torch.int32),
-                 "first_below": (n, torch.int32), "first_reach": (n, torch.int32), "stats": (rec, torch.uint8),
-                 "drawdown_stats": (rec, torch.uint8), "first_below_at": (p + 1, torch.int64),
-                 "first_reach_at": (p + 1, torch.int64)}
-        out = {k: (torch.empty(shape[k][0], dtype=shape[k][1], device=self.tdevice) if full[k] else None)
-               for k in _lib.EXCURSION_OUTPUTS}
+        out, o = self._outputs(_EXCURSION_ROWS, _lib.ExcursionOutputs, sim, self._excursion_wants(wants), host=False)
         x = self.make_excursions(lower, target, drawdown_threshold)
-        o = _lib.ExcursionOutputs()
-        o.struct_size = C.sizeof(_lib.ExcursionOutputs)
-        for k, t in out.items():
-            setattr(o, k, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_excursions(self._h, C.byref(sim), C.byref(x), C.byref(o)))
-        self._leave(cur, *out.values())
+        self._run(self._L.smmc_engine_simulate_excursions, C.byref(sim), C.byref(x), C.byref(o), device=_buffers(_EXCURSION_ROWS, out))
         return out
 
     def simulate_excursions_to_host(self, sim, lower, target, drawdown_threshold=0.2, **wants):
         """The same through smmc_engine_simulate_excursions_to_host: a dict of numpy arrays (the records: bytes)."""
-        full = self._excursion_wants(wants)
-        n, p = int(sim.n_paths), int(sim.n_periods)
-        rec = int(self._L.smmc_stats_bytes(sim.n_bins)) // 8
-        shape = {"final": (n, np.float32), "peak": (n, np.float32), "low": (n, np.float32), "drawdown": (n, np.float32),
-                 "drawdown_period": (n, np.uint32), "underwater": (n, np.uint32), "first_below": (n, np.uint32),
-                 "first_reach": (n, np.uint32), "stats": (rec, np.uint64), "drawdown_stats": (rec, np.uint64),
-                 "first_below_at": (p + 1, np.uint64), "first_reach_at": (p + 1, np.uint64)}
-        out = {k: (np.zeros(shape[k][0], dtype=shape[k][1]) if full[k] else None) for k in _lib.EXCURSION_OUTPUTS}
+        out, o = self._outputs(_EXCURSION_ROWS, _lib.ExcursionOutputs, sim, self._excursion_wants(wants), host=True,
+                               host_null_empty=True)  # this family alone passes a host array without elements as a null pointer
         x = self.make_excursions(lower, target, drawdown_threshold)
-        o = _lib.ExcursionOutputs()
-        o.struct_size = C.sizeof(_lib.ExcursionOutputs)
-        for k, a in out.items():
-            setattr(o, k, a.ctypes.data if a is not None and a.size else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_excursions_to_host(self._h, C.byref(sim), C.byref(x), C.byref(o)))
-        for k in ("stats", "drawdown_stats"):
-            if out[k] is not None:
-                out[k] = out[k].tobytes()
-        return out
+        self._run(self._L.smmc_engine_simulate_excursions_to_host, C.byref(sim), C.byref(x), C.byref(o))
+        return _records_as_bytes(_EXCURSION_ROWS, out)
 
     # -- block bootstrap: table paths drawn in runs of consecutive months (smmc_engine_simulate_blocks) ----------
     @staticmethod
@@ -882,24 +906,19 @@ class Engine:
                                                                    raw["stats_raw"])
         return res
 
+    def _check_out(self, final, sim):
+        """A caller's `out` must hold the final values as the kernel writes them."""
+        if final is not None:
+            assert final.numel() >= int(sim.n_paths) and final.dtype == self._torch.float32 and final.is_contiguous()
+
     def simulate_blocks_raw(self, sim, block_len, want_final=True, want_chunk_stats=False, want_stats=False, out=None):
         """Enqueues the call and returns its device tensors without waiting: a dict with final, chunk_mean, chunk_var
         (float32) and stats_raw (uint8, the packed record); None for what was not asked for."""
-        torch = self._torch
-        n = int(sim.n_paths)
         blocks = self.make_blocks(block_len)
-        new = lambda want, count, dtype: torch.empty(count, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        nc = (n + _lib.CHUNK - 1) // _lib.CHUNK
-        res = {"final": out if (want_final and out is not None) else new(want_final, n, torch.float32),
-               "chunk_mean": new(want_chunk_stats, nc, torch.float32), "chunk_var": new(want_chunk_stats, nc, torch.float32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8)}
-        if res["final"] is not None:
-            assert res["final"].numel() >= n and res["final"].dtype == torch.float32 and res["final"].is_contiguous()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_blocks(self._h, C.byref(sim), C.byref(blocks), ptr(res["final"]),
-                                                       ptr(res["chunk_mean"]), ptr(res["chunk_var"]), ptr(res["stats_raw"])))
-        self._leave(cur, *res.values())
+        res, ptrs = self._outputs(_BLOCKS_ROWS, None, sim, (want_final, want_chunk_stats, want_chunk_stats, want_stats), host=False,
+                                  given={"final": out})
+        self._check_out(res["final"], sim)
+        self._run(self._L.smmc_engine_simulate_blocks, C.byref(sim), C.byref(blocks), *ptrs, device=_buffers(_BLOCKS_ROWS, res))
         return res
 
     def simulate_blocks_to_host(self, sim, block_len, out=None, want_stats=False, want_chunk_stats=False, progress=None):
@@ -929,10 +948,7 @@ class Engine:
         """DIV_FAST / DIV_EXACT / DIV_CHECKED: the divide simulate_blocks uses for this request (results never depend
         on it)."""
         blocks = self.make_blocks(block_len)
-        rc = self._L.smmc_engine_blocks_divide_kind(self._h, C.byref(sim), C.byref(blocks))
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_blocks_divide_kind(self._h, C.byref(sim), C.byref(blocks)))
 
     # -- portfolios: jointly drawn assets, weights, periodic rebalancing (smmc_engine_simulate_portfolio) -----
     def set_asset_table(self, returns_percent):
@@ -979,64 +995,40 @@ class Engine:
         raw = self.simulate_portfolio_raw(sim, weights, rebalance_every, means, factor, want_final, want_holdings,
                                           want_stats, out)
         res = PortfolioResult(int(sim.n_paths), raw["n_assets"], raw["final"], raw["holdings"])
-        if want_stats:
-            self.sync()
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        return res
+        return self._read_back(res, sim, raw, _PORTFOLIO_ROWS)
 
     def simulate_portfolio_raw(self, sim, weights, rebalance_every=0, means=None, factor=None, want_final=True,
                                want_holdings=False, want_stats=False, out=None):
         """Enqueues the call and returns its device tensors without waiting: a dict with final, holdings (float32) and
         stats_raw (uint8, the packed record); None for what was not asked for."""
-        torch = self._torch
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, K = int(sim.n_paths), int(pf.n_assets)
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": out if (want_final and out is not None) else new(want_final, n, torch.float32),
-               "holdings": new(want_holdings, (K, n), torch.float32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8)}
-        if res["final"] is not None:
-            assert res["final"].numel() >= n and res["final"].dtype == torch.float32 and res["final"].is_contiguous()
-        o = _lib.PortfolioOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioOutputs)
-        for name, key in (("final", "final"), ("holdings", "holdings"), ("stats", "stats_raw")):
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio(self._h, C.byref(sim), C.byref(pf), C.byref(o)))
-        self._leave(cur, res["final"], res["holdings"], res["stats_raw"])
+        K = int(pf.n_assets)
+        res, o = self._outputs(_PORTFOLIO_ROWS, _lib.PortfolioOutputs, sim, (want_final, want_holdings, want_stats), host=False, K=K,
+                               head={"n_assets": K}, given={"final": out})
+        self._check_out(res["final"], sim)
+        self._run(self._L.smmc_engine_simulate_portfolio, C.byref(sim), C.byref(pf), C.byref(o), device=_buffers(_PORTFOLIO_ROWS, res))
         return res
 
     def simulate_portfolio_to_host(self, sim, weights, rebalance_every=0, means=None, factor=None, want_final=True,
                                    want_holdings=False, want_stats=False):
         """The same through smmc_engine_simulate_portfolio_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, K = int(sim.n_paths), int(pf.n_assets)
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64)}
-        o = _lib.PortfolioOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioOutputs)
-        for name, key in (("final", "final"), ("holdings", "holdings"), ("stats", "stats_raw")):
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(o)))
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        K = int(pf.n_assets)
+        res, o = self._outputs(_PORTFOLIO_ROWS, _lib.PortfolioOutputs, sim, (want_final, want_holdings, want_stats), host=True, K=K,
+                               head={"n_assets": K})
+        self._run(self._L.smmc_engine_simulate_portfolio_to_host, C.byref(sim), C.byref(pf), C.byref(o))
+        return _records_as_bytes(_PORTFOLIO_ROWS, res)
 
     def portfolio_divide_kind(self, sim, weights, rebalance_every=0, means=None, factor=None):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_portfolio uses for this request (results never depend on it)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        rc = self._L.smmc_engine_portfolio_divide_kind(self._h, C.byref(sim), C.byref(pf))
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_portfolio_divide_kind(self._h, C.byref(sim), C.byref(pf)))
 
     # -- portfolio cash flows: a schedule on a rebalanced portfolio (smmc_engine_simulate_portfolio_cashflow) -----
-    _PFCF_OUTPUTS = (("final", "final"), ("holdings", "holdings"), ("paid", "paid"), ("ruin_period", "ruin_period"),
-                     ("stats", "stats_raw"), ("depleted_at", "depleted_at"))
+    def _pfcf_outputs(self, sim, K, wants, host, S=None, struct=_lib.PortfolioCashflowOutputs, head=None):
+        """smmc_portfolio_cashflow_outputs (or the sweep's structure of the same fields) for the entries that fill it:
+        (result dict beginning with n_assets and `head`, the structure)."""
+        return self._outputs(_PFCF_ROWS, struct, sim, wants, host, K=K, S=S, head=dict({"n_assets": int(K)}, **(head or {})))
 
     def simulate_portfolio_cashflow(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                                     fractions=None, means=None, factor=None, want_final=True, want_holdings=False,
@@ -1050,14 +1042,7 @@ class Engine:
                                                    want_stats, want_depleted_at)
         res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                       n_assets=raw["n_assets"], holdings=raw["holdings"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _PFCF_ROWS)
 
     def simulate_portfolio_cashflow_raw(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
                                         amounts=None, fractions=None, means=None, factor=None, want_final=True,
@@ -1066,23 +1051,12 @@ class Engine:
         """Enqueues the call and returns its device tensors without waiting: a dict with final, holdings, paid (float32),
         ruin_period (int32 holding uint32 values), stats_raw (uint8, the packed record) and depleted_at (int64 holding
         uint64 counts, n_periods + 1); None for what was not asked for."""
-        torch = self._torch
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
-               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
-        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=False)
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o),
+                  device=_buffers(_PFCF_ROWS, res))
         del keep
         return res
 
@@ -1092,34 +1066,19 @@ class Engine:
                                             want_depleted_at=True):
         """The same through smmc_engine_simulate_portfolio_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=True)
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow_to_host, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o))
         del keep
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        return _records_as_bytes(_PFCF_ROWS, res)
 
     def portfolio_cashflow_divide_kind(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                                        fractions=None, means=None, factor=None):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_portfolio_cashflow uses for this request (results never depend on it)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
-        rc = self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
-        del keep
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)  # keep lives until the return
+        return self._kind(self._L.smmc_engine_portfolio_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf)))
 
     # -- glide paths: target weights that change along a plan (smmc_engine_simulate_glide) ---------------------------
     @staticmethod
@@ -1155,37 +1114,19 @@ class Engine:
                                       factor, want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at)
         res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                       n_assets=raw["n_assets"], holdings=raw["holdings"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _PFCF_ROWS)
 
     def simulate_glide_raw(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                            fractions=None, means=None, factor=None, want_final=True, want_holdings=False, want_paid=False,
                            want_ruin_period=False, want_stats=False, want_depleted_at=True):
         """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict."""
-        torch = self._torch
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         gl, keep_gl = self.make_glide(changes)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
-               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_glide(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o)))
-        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=False)
+        self._run(self._L.smmc_engine_simulate_glide, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o),
+                  device=_buffers(_PFCF_ROWS, res))
         del keep, keep_gl
         return res
 
@@ -1195,35 +1136,20 @@ class Engine:
         """The same through smmc_engine_simulate_glide_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         gl, keep_gl = self.make_glide(changes)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_glide_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o)))
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=True)
+        self._run(self._L.smmc_engine_simulate_glide_to_host, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl), C.byref(o))
         del keep, keep_gl
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        return _records_as_bytes(_PFCF_ROWS, res)
 
     def glide_divide_kind(self, sim, weights, changes, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                           fractions=None, means=None, factor=None):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_glide uses for this request (results never depend on it)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        gl, keep_gl = self.make_glide(changes)
+        gl, keep_gl = self.make_glide(changes)  # keep_gl and keep live until the return
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
-        rc = self._L.smmc_engine_glide_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl))
-        del keep, keep_gl
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_glide_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(gl)))
 
     # -- block-bootstrap plans: portfolio cash flows on runs of consecutive months (smmc_engine_simulate_portfolio_cashflow_blocks) --
     def simulate_portfolio_cashflow_blocks(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
@@ -1238,38 +1164,19 @@ class Engine:
                                                           want_stats, want_depleted_at)
         res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                       n_assets=raw["n_assets"], holdings=raw["holdings"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _PFCF_ROWS)
 
     def simulate_portfolio_cashflow_blocks_raw(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0,
                                                floor=0.0, amounts=None, fractions=None, want_final=True, want_holdings=False,
                                                want_paid=False, want_ruin_period=False, want_stats=False, want_depleted_at=True):
         """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict."""
-        torch = self._torch
         pf = self.make_portfolio(weights, rebalance_every)
         blocks = self.make_blocks(block_len)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
-               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_blocks(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(blocks),
-                                                                          C.byref(o)))
-        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=False)
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow_blocks, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(blocks),
+                  C.byref(o), device=_buffers(_PFCF_ROWS, res))
         del keep
         return res
 
@@ -1279,41 +1186,24 @@ class Engine:
         """The same through smmc_engine_simulate_portfolio_cashflow_blocks_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_portfolio(weights, rebalance_every)
         blocks = self.make_blocks(block_len)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_blocks_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf),
-                                                                                  C.byref(blocks), C.byref(o)))
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=True)
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow_blocks_to_host, C.byref(sim), C.byref(pf), C.byref(cf),
+                  C.byref(blocks), C.byref(o))
         del keep
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        return _records_as_bytes(_PFCF_ROWS, res)
 
     def portfolio_cashflow_blocks_divide_kind(self, sim, weights, block_len, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0,
                                               amounts=None, fractions=None):
         """_lib.DIV_FAST or DIV_EXACT: what portfolio_cashflow_divide_kind says of the same plan (results never depend on it)."""
         pf = self.make_portfolio(weights, rebalance_every)
         blocks = self.make_blocks(block_len)
-        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
-        rc = self._L.smmc_engine_portfolio_cashflow_blocks_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(blocks))
-        del keep
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)  # keep lives until the return
+        return self._kind(self._L.smmc_engine_portfolio_cashflow_blocks_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf),
+                                                                                   C.byref(blocks)))
 
     # -- guardrails: a withdrawal that a review rule adjusts per path (smmc_engine_simulate_guardrails) --------------
-    _GUARDRAILS_WANTS = ("final", "holdings", "paid", "ruin_period", "stats", "depleted_at", "amount_last", "amount_lowest",
-                         "cuts", "raises", "cuts_at", "raises_at")  # _lib.GUARDRAILS_OUTPUTS; the result key of stats is stats_raw
-
     @staticmethod
     def make_guardrails(amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1, index=1.0, amount_min=0.0,
                         amount_max=float("inf"), floor=0.0):
@@ -1324,13 +1214,6 @@ class Engine:
         gr.amount, gr.index, gr.upper, gr.lower = float(amount), float(index), float(upper), float(lower)
         gr.cut, gr.raise_, gr.amount_min, gr.amount_max, gr.floor = float(cut), float(raise_), float(amount_min), float(amount_max), float(floor)
         return gr
-
-    @staticmethod
-    def _guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at, want_amount_last,
-                          want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at):
-        return dict(zip(Engine._GUARDRAILS_WANTS, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
-                                                    want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at,
-                                                    want_raises_at)))
 
     def simulate_guardrails(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1, index=1.0,
                             amount_min=0.0, amount_max=float("inf"), floor=0.0, rebalance_every=0, means=None, factor=None,
@@ -1349,15 +1232,7 @@ class Engine:
         res = GuardrailsResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                n_assets=raw["n_assets"], holdings=raw["holdings"], amount_last=raw["amount_last"],
                                amount_lowest=raw["amount_lowest"], cuts=raw["cuts"], raises=raw["raises"])
-        if want_stats or want_depleted_at or want_cuts_at or want_raises_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        for key in ("depleted_at", "cuts_at", "raises_at"):
-            if raw[key] is not None:
-                setattr(res, key, raw[key].cpu().numpy().view(np.uint64).copy())
-        return res
+        return self._read_back(res, sim, raw, _GUARDRAILS_ROWS)
 
     def simulate_guardrails_raw(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1,
                                 index=1.0, amount_min=0.0, amount_max=float("inf"), floor=0.0, rebalance_every=0, means=None,
@@ -1368,26 +1243,14 @@ class Engine:
         amount_last, amount_lowest (float32), ruin_period, cuts, raises (int32 holding uint32 values), stats_raw (uint8,
         the packed record) and depleted_at, cuts_at, raises_at (int64 holding uint64 counts, n_periods + 1); None for
         what was not asked for."""
-        torch = self._torch
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         gr = self.make_guardrails(amount, review_every, upper, lower, cut, raise_, index, amount_min, amount_max, floor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        want = self._guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
-                                      want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
-        shapes = {"final": (n, torch.float32), "holdings": ((K, n), torch.float32), "paid": (n, torch.float32),
-                  "ruin_period": (n, torch.int32), "stats": (int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-                  "depleted_at": (p + 1, torch.int64), "amount_last": (n, torch.float32), "amount_lowest": (n, torch.float32),
-                  "cuts": (n, torch.int32), "raises": (n, torch.int32), "cuts_at": (p + 1, torch.int64), "raises_at": (p + 1, torch.int64)}
-        res = {"n_assets": K}
-        o = _lib.GuardrailsOutputs()
-        o.struct_size = C.sizeof(_lib.GuardrailsOutputs)
-        for name in self._GUARDRAILS_WANTS:
-            t = torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.tdevice) if want[name] else None
-            res["stats_raw" if name == "stats" else name] = t
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_guardrails(self._h, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o)))
-        self._leave(cur, *[res["stats_raw" if name == "stats" else name] for name in self._GUARDRAILS_WANTS])
+        K = int(pf.n_assets)
+        wants = (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at, want_amount_last,
+                 want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
+        res, o = self._outputs(_GUARDRAILS_ROWS, _lib.GuardrailsOutputs, sim, wants, host=False, K=K, head={"n_assets": K})
+        self._run(self._L.smmc_engine_simulate_guardrails, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o),
+                  device=_buffers(_GUARDRAILS_ROWS, res))
         return res
 
     def simulate_guardrails_to_host(self, sim, weights, amount, review_every=12, upper=float("inf"), lower=0.0, cut=0.9, raise_=1.1,
@@ -1398,25 +1261,12 @@ class Engine:
         """The same through smmc_engine_simulate_guardrails_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
         gr = self.make_guardrails(amount, review_every, upper, lower, cut, raise_, index, amount_min, amount_max, floor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        want = self._guardrails_wants(want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at,
-                                      want_amount_last, want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
-        shapes = {"final": (n, np.float32), "holdings": ((K, n), np.float32), "paid": (n, np.float32), "ruin_period": (n, np.uint32),
-                  "stats": (int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64), "depleted_at": (p + 1, np.uint64),
-                  "amount_last": (n, np.float32), "amount_lowest": (n, np.float32), "cuts": (n, np.uint32), "raises": (n, np.uint32),
-                  "cuts_at": (p + 1, np.uint64), "raises_at": (p + 1, np.uint64)}
-        res = {"n_assets": K}
-        o = _lib.GuardrailsOutputs()
-        o.struct_size = C.sizeof(_lib.GuardrailsOutputs)
-        for name in self._GUARDRAILS_WANTS:
-            t = np.zeros(shapes[name][0], dtype=shapes[name][1]) if want[name] else None
-            res["stats_raw" if name == "stats" else name] = t
-            setattr(o, name, t.ctypes.data if t is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_guardrails_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o)))
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        K = int(pf.n_assets)
+        wants = (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at, want_amount_last,
+                 want_amount_lowest, want_cuts, want_raises, want_cuts_at, want_raises_at)
+        res, o = self._outputs(_GUARDRAILS_ROWS, _lib.GuardrailsOutputs, sim, wants, host=True, K=K, head={"n_assets": K})
+        self._run(self._L.smmc_engine_simulate_guardrails_to_host, C.byref(sim), C.byref(pf), C.byref(gr), C.byref(o))
+        return _records_as_bytes(_GUARDRAILS_ROWS, res)
 
     # -- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods
     #    (smmc_engine_simulate_portfolio_cashflow_checkpoints) ---------------------------------------------------------
@@ -1441,19 +1291,7 @@ class Engine:
         per = raw["periods"]
         res = PortfolioCashflowCheckpointsResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                                  n_assets=raw["n_assets"], holdings=raw["holdings"], periods=per)
-        self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        host, rec = raw["records_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
-        res.checkpoints = []
-        for k in range(per.size):
-            st = stats_from_bytes(host[k * rec:(k + 1) * rec])
-            st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-            res.checkpoints.append(st)
-        return res
+        return self._read_back(res, sim, raw, _PFCF_ROWS, also=[("checkpoints", "records_raw", _RECORD, per.size)])  # always something to read
 
     def simulate_portfolio_cashflow_checkpoints_raw(self, sim, weights, periods, rebalance_every=0, amount=0.0, fraction=0.0,
                                                     floor=0.0, amounts=None, fractions=None, means=None, factor=None,
@@ -1461,30 +1299,18 @@ class Engine:
                                                     want_ruin_period=False, want_stats=False, want_depleted_at=True):
         """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict with
         records_raw (uint8, n_checkpoints packed records) and periods (numpy uint32)."""
-        torch = self._torch
         per = self._checkpoint_periods(periods)
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rec = int(self._L.smmc_stats_bytes(sim.n_bins))
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "periods": per, "final": new(want_final, n, torch.float32),
-               "holdings": new(want_holdings, (K, n), torch.float32), "paid": new(want_paid, n, torch.float32),
-               "ruin_period": new(want_ruin_period, n, torch.int32), "stats_raw": new(want_stats, rec, torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64),
-               "records_raw": torch.empty(max(per.size, 1) * rec, dtype=torch.uint8, device=self.tdevice)}
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints(
-            self._h, C.byref(sim), C.byref(pf), C.byref(cf), per.ctypes.data_as(C.c_void_p), per.size, C.byref(o),
-            C.c_void_p(res["records_raw"].data_ptr())))
-        self._leave(cur, res["records_raw"], *[res[key] for _, key in self._PFCF_OUTPUTS])
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=False, head={"periods": per})
+        records = self._new(_RECORD, (max(per.size, 1) * rec,), host=False)  # the library wants a buffer even without a period
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints, C.byref(sim), C.byref(pf), C.byref(cf),
+                  per.ctypes.data_as(C.c_void_p), per.size, C.byref(o), C.c_void_p(records.data_ptr()),
+                  device=[records] + _buffers(_PFCF_ROWS, res))
         del keep
-        res["records_raw"] = res["records_raw"][: per.size * rec]
+        res["records_raw"] = records[: per.size * rec]
         return res
 
     def simulate_portfolio_cashflow_checkpoints_to_host(self, sim, weights, periods, rebalance_every=0, amount=0.0, fraction=0.0,
@@ -1495,32 +1321,18 @@ class Engine:
         and records_raw: bytes)."""
         per = self._checkpoint_periods(periods)
         pf = self.make_portfolio(weights, rebalance_every, means, factor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         rec = int(self._L.smmc_stats_bytes(sim.n_bins))
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "periods": per, "final": new(want_final, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, rec // 8, np.uint64), "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        records = np.zeros(max(per.size, 1) * rec // 8, dtype=np.uint64)
-        o = _lib.PortfolioCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.PortfolioCashflowOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints_to_host(
-            self._h, C.byref(sim), C.byref(pf), C.byref(cf), per.ctypes.data_as(C.c_void_p), per.size, C.byref(o),
-            records.ctypes.data_as(C.c_void_p)))
+        res, o = self._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=True, head={"periods": per})
+        records = self._new(_RECORD, (max(per.size, 1) * rec,), host=True)
+        self._run(self._L.smmc_engine_simulate_portfolio_cashflow_checkpoints_to_host, C.byref(sim), C.byref(pf), C.byref(cf),
+                  per.ctypes.data_as(C.c_void_p), per.size, C.byref(o), records.ctypes.data_as(C.c_void_p))
         del keep
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
         res["records_raw"] = records.tobytes()[: per.size * rec]
-        return res
+        return _records_as_bytes(_PFCF_ROWS, res)
 
     # -- real cash flows: the schedule in money of period 0, inflation drawn jointly (smmc_engine_simulate_real_cashflow) --
-    _REAL_OUTPUTS = (("final", "final"), ("final_real", "final_real"), ("index", "index"), ("holdings", "holdings"), ("paid", "paid"),
-                     ("ruin_period", "ruin_period"), ("stats", "stats_raw"), ("depleted_at", "depleted_at"))
-
     @staticmethod
     def make_real_portfolio(weights, rebalance_every=0, means=None, factor=None):
         """smmc_portfolio of K = len(weights) invested assets for the real cash-flow calls; means [K + 1] and factor
@@ -1538,19 +1350,8 @@ class Engine:
                                    want_depleted_at=True):
         """(smmc_real_cashflow_outputs, dict of the device tensors it points to) for a request of sim's size with
         n_assets invested assets; None for what was not asked for."""
-        torch = self._torch
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(n_assets)
-        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, torch.float32), "final_real": new(want_final_real, n, torch.float32),
-               "index": new(want_index, n, torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
-               "paid": new(want_paid, n, torch.float32), "ruin_period": new(want_ruin_period, n, torch.int32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)), torch.uint8),
-               "depleted_at": new(want_depleted_at, p + 1, torch.int64)}
-        o = _lib.RealCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.RealCashflowOutputs)
-        for name, key in self._REAL_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
+        wants = (want_final, want_final_real, want_index, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at)
+        res, o = self._outputs(_REAL_ROWS, _lib.RealCashflowOutputs, sim, wants, host=False, K=n_assets, head={"n_assets": int(n_assets)})
         return o, res
 
     def simulate_real_cashflow(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
@@ -1568,14 +1369,7 @@ class Engine:
                                               want_ruin_period, want_stats, want_depleted_at)
         res = RealCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
                                  n_assets=raw["n_assets"], holdings=raw["holdings"], final_real=raw["final_real"], index=raw["index"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            res.stats = stats_from_bytes(raw["stats_raw"].cpu().numpy().tobytes())
-            res.stats.hist_lo, res.stats.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _REAL_ROWS)
 
     def simulate_real_cashflow_raw(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                                    fractions=None, means=None, factor=None, want_final=True, want_final_real=True,
@@ -1588,9 +1382,8 @@ class Engine:
         cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
         o, res = self.make_real_cashflow_outputs(sim, pf.n_assets, want_final, want_final_real, want_index, want_holdings,
                                                  want_paid, want_ruin_period, want_stats, want_depleted_at)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_real_cashflow(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
-        self._leave(cur, *[res[key] for _, key in self._REAL_OUTPUTS])
+        self._run(self._L.smmc_engine_simulate_real_cashflow, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o),
+                  device=_buffers(_REAL_ROWS, res))
         del keep
         return res
 
@@ -1600,35 +1393,20 @@ class Engine:
                                        want_stats=False, want_depleted_at=True):
         """The same through smmc_engine_simulate_real_cashflow_to_host: a dict of numpy arrays (stats_raw: bytes)."""
         pf = self.make_real_portfolio(weights, rebalance_every, means, factor)
-        n, p, K = int(sim.n_paths), int(sim.n_periods), int(pf.n_assets)
-        cf, keep = self.make_cashflow(p, amount, fraction, amounts, fractions, floor)
-        new = lambda want, shape, dtype: np.zeros(shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, n, np.float32), "final_real": new(want_final_real, n, np.float32),
-               "index": new(want_index, n, np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, n, np.float32), "ruin_period": new(want_ruin_period, n, np.uint32),
-               "stats_raw": new(want_stats, int(self._L.smmc_stats_bytes(sim.n_bins)) // 8, np.uint64),
-               "depleted_at": new(want_depleted_at, p + 1, np.uint64)}
-        o = _lib.RealCashflowOutputs()
-        o.struct_size = C.sizeof(_lib.RealCashflowOutputs)
-        for name, key in self._REAL_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_real_cashflow_to_host(self._h, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o)))
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+        K = int(pf.n_assets)
+        wants = (want_final, want_final_real, want_index, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at)
+        res, o = self._outputs(_REAL_ROWS, _lib.RealCashflowOutputs, sim, wants, host=True, K=K, head={"n_assets": K})
+        self._run(self._L.smmc_engine_simulate_real_cashflow_to_host, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(o))
         del keep
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        return _records_as_bytes(_REAL_ROWS, res)
 
     def real_cashflow_divide_kind(self, sim, weights, rebalance_every=0, amount=0.0, fraction=0.0, floor=0.0, amounts=None,
                                   fractions=None, means=None, factor=None):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_real_cashflow uses for this request (results never depend on it)."""
         pf = self.make_real_portfolio(weights, rebalance_every, means, factor)
-        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
-        rc = self._L.smmc_engine_real_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf))
-        del keep
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        cf, keep = self.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)  # keep lives until the return
+        return self._kind(self._L.smmc_engine_real_cashflow_divide_kind(self._h, C.byref(sim), C.byref(pf), C.byref(cf)))
 
     # -- allocation sweeps: up to MAX_SWEEP portfolio strategies on one set of draws (smmc_engine_simulate_allocation_sweep) --
     @staticmethod
@@ -1667,18 +1445,7 @@ class Engine:
         _, _, w, every, am, fr, fl = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
         res = AllocationSweepResult(int(sim.n_paths), int(sim.n_periods), am, fr, fl, raw["final"], raw["paid"], raw["ruin_period"],
                                     weights=w, rebalance_every=every, n_assets=raw["n_assets"], holdings=raw["holdings"])
-        if want_stats or want_depleted_at:
-            self.sync()
-        if want_stats:
-            host, rec = raw["stats_raw"].cpu().numpy().tobytes(), int(self._L.smmc_stats_bytes(sim.n_bins))
-            res.stats = []
-            for s in range(am.size):
-                st = stats_from_bytes(host[s * rec:(s + 1) * rec])
-                st.hist_lo, st.hist_hi = float(sim.hist_lo), float(sim.hist_hi)
-                res.stats.append(st)
-        if want_depleted_at:
-            res.depleted_at = raw["depleted_at"].cpu().numpy().view(np.uint64).copy()
-        return res
+        return self._read_back(res, sim, raw, _PFCF_ROWS, n_records=am.size)
 
     def simulate_allocation_sweep_raw(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None,
                                       factor=None, want_final=False, want_holdings=False, want_paid=False,
@@ -1687,22 +1454,11 @@ class Engine:
         [S, n_paths]), holdings (float32 [S, K, n_paths]), ruin_period (int32 holding uint32 values), stats_raw (uint8
         [S, smmc_stats_bytes(n_bins)]) and depleted_at (int64 holding uint64 counts, [S, n_periods + 1]); None for what
         was not asked for."""
-        torch = self._torch
         pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
-        n, p, (S, K) = int(sim.n_paths), int(sim.n_periods), w.shape
-        new = lambda want, shape, dtype: torch.empty((S,) + shape, dtype=dtype, device=self.tdevice) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, (n,), torch.float32), "holdings": new(want_holdings, (K, n), torch.float32),
-               "paid": new(want_paid, (n,), torch.float32), "ruin_period": new(want_ruin_period, (n,), torch.int32),
-               "stats_raw": new(want_stats, (int(self._L.smmc_stats_bytes(sim.n_bins)),), torch.uint8),
-               "depleted_at": new(want_depleted_at, (p + 1,), torch.int64)}
-        o = _lib.AllocationSweepOutputs()
-        o.struct_size = C.sizeof(_lib.AllocationSweepOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            t = res[key]
-            setattr(o, name, t.data_ptr() if t is not None and t.numel() else None)
-        cur = self._enter()
-        _lib.check(self._L.smmc_engine_simulate_allocation_sweep(self._h, C.byref(sim), pfs, cfs, S, C.byref(o)))
-        self._leave(cur, *[res[key] for _, key in self._PFCF_OUTPUTS])
+        S, K = w.shape
+        res, o = self._pfcf_outputs(sim, K, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=False, S=S, struct=_lib.AllocationSweepOutputs)
+        self._run(self._L.smmc_engine_simulate_allocation_sweep, C.byref(sim), pfs, cfs, S, C.byref(o), device=_buffers(_PFCF_ROWS, res))
         return res
 
     def simulate_allocation_sweep_to_host(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0,
@@ -1711,31 +1467,18 @@ class Engine:
         """The same through smmc_engine_simulate_allocation_sweep_to_host: a dict of numpy arrays, scenario-major
         (stats_raw: the S packed records as bytes)."""
         pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
-        n, p, (S, K) = int(sim.n_paths), int(sim.n_periods), w.shape
-        new = lambda want, shape, dtype: np.zeros((S,) + shape, dtype=dtype) if want else None  # noqa: E731
-        res = {"n_assets": K, "final": new(want_final, (n,), np.float32), "holdings": new(want_holdings, (K, n), np.float32),
-               "paid": new(want_paid, (n,), np.float32), "ruin_period": new(want_ruin_period, (n,), np.uint32),
-               "stats_raw": new(want_stats, (int(self._L.smmc_stats_bytes(sim.n_bins)) // 8,), np.uint64),
-               "depleted_at": new(want_depleted_at, (p + 1,), np.uint64)}
-        o = _lib.AllocationSweepOutputs()
-        o.struct_size = C.sizeof(_lib.AllocationSweepOutputs)
-        for name, key in self._PFCF_OUTPUTS:
-            setattr(o, name, res[key].ctypes.data if res[key] is not None else None)
-        self._enter()
-        _lib.check(self._L.smmc_engine_simulate_allocation_sweep_to_host(self._h, C.byref(sim), pfs, cfs, S, C.byref(o)))
-        if want_stats:
-            res["stats_raw"] = res["stats_raw"].tobytes()
-        return res
+        S, K = w.shape
+        res, o = self._pfcf_outputs(sim, K, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                                    host=True, S=S, struct=_lib.AllocationSweepOutputs)
+        self._run(self._L.smmc_engine_simulate_allocation_sweep_to_host, C.byref(sim), pfs, cfs, S, C.byref(o))
+        return _records_as_bytes(_PFCF_ROWS, res)
 
     def allocation_sweep_divide_kind(self, sim, weights, rebalance_every=0, amounts=0.0, fractions=0.0, floors=0.0, means=None,
                                      factor=None):
         """_lib.DIV_FAST or DIV_EXACT: the divide simulate_allocation_sweep uses for this request: FAST only if every
         scenario's own rule says so (results never depend on it)."""
         pfs, cfs, w, _, _, _, _ = self.make_allocation_sweep(weights, rebalance_every, amounts, fractions, floors, means, factor)
-        rc = self._L.smmc_engine_allocation_sweep_divide_kind(self._h, C.byref(sim), pfs, cfs, int(w.shape[0]))
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_allocation_sweep_divide_kind(self._h, C.byref(sim), pfs, cfs, int(w.shape[0])))
 
     def read_stats(self, stats_raw):
         """Copies a device record to the host after the engine stream has drained."""
@@ -1795,20 +1538,14 @@ class Engine:
     def divide_kind(self, sim, keepdata=False):
         """DIV_FAST / DIV_EXACT / DIV_CHECKED: which divide-by-100 a launch of `sim` uses (results
         never depend on it)."""
-        rc = self._L.smmc_engine_divide_kind(self._h, C.byref(sim), 1 if keepdata else 0)
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_divide_kind(self._h, C.byref(sim), 1 if keepdata else 0))
 
     def paths_form(self, sim):
         """1 when a `simulate` launch of `sim` gets the kernel that holds the path id's bits 63..32 in a scalar
         register (every path of the launch shares them, counter stream v3, SMMC_UNIFORM_HI not 0), else 0
         (results never depend on it)."""
         self._uniform_hi_from_env()
-        rc = self._L.smmc_engine_paths_form(self._h, C.byref(sim))
-        if rc < 0:
-            _lib.check(rc)
-        return rc
+        return self._kind(self._L.smmc_engine_paths_form(self._h, C.byref(sim)))
 
     def simulate_keepdata(self, sim, want_final=True):
         torch = self._torch

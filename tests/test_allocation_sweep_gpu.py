@@ -25,6 +25,12 @@ from test_allocation_sweep_cpu import LEDGER
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("allocation_sweep")
+
 BINS, LO, HI, BELOW = ref.BINS, ref.LO, ref.HI, ref.BELOW
 STATS = dict(n_bins=BINS, hist_lo=LO, hist_hi=HI, below_threshold=BELOW)
 ALL = dict(want_final=True, want_holdings=True, want_paid=True, want_ruin_period=True, want_stats=True, want_depleted_at=True)

@@ -21,6 +21,12 @@ import blocks_reference as ref
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream(table):
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check_blocks(table)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (table, L, P, n_paths)
 CASES = [

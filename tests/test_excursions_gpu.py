@@ -15,6 +15,12 @@ import excursions_reference as ref
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("excursions")
+
 N_MAX = ref.N_MAX
 PATHS = [1, 255, 4099, N_MAX]   # one path; a partial wave; a ragged last chunk; past one workgroup walk
 PERIODS = [7, 360, 1000]        # below one Philox block; a multiple of 8 and of 4; neither

@@ -24,6 +24,12 @@ import test_feature_matrix_gpu as FG
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("glide")
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WANTS = ("final", "holdings", "paid", "ruin_period", "stats", "depleted_at")
 KEYS = tuple("stats_raw" if k == "stats" else k for k in WANTS)

@@ -28,6 +28,12 @@ import portfolio_reference as ref
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("portfolio")
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [("t37", 1), ("t37", 2), ("t37", 3), ("t37", 4), ("t2500", 2), ("gauss", 1), ("gauss", 2), ("gauss", 3), ("gauss", 4)]
 REBALANCE = [0, 1, 5, 12]

@@ -26,6 +26,12 @@ import real_cashflow_reference as ref
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("real_cashflow")
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BINS, LO, HI, BELOW = ref.BINS, ref.LO, ref.HI, ref.BELOW
 STATS = dict(n_bins=BINS, hist_lo=LO, hist_hi=HI, below_threshold=BELOW)

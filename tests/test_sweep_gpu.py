@@ -23,6 +23,12 @@ from test_sweep_cpu import AMOUNTS, SHARES
 
 pytestmark = pytest.mark.gpu
 
+
+def test_raw_and_to_host_give_the_same_bytes_on_an_engine_with_its_own_stream():
+    """300 paths, 8 periods, every want on: the device tensors, read through torch's stream, against the host entry's."""
+    import raw_to_host_check
+    raw_to_host_check.check("cashflow_sweep")
+
 N_MAX = 2 * 4099 + 1
 PATHS = [1, 255, 4099, N_MAX]   # one path; a partial wave; a ragged last chunk past one workgroup walk; more of it
 MODES = ["gaussian", "table", "table3001"]
