@@ -408,7 +408,8 @@ int smmc_engine_simulate_excursions_to_host(smmc_engine *e, const smmc_sim *sim,
  * A path depends only on (seed, global path id, table, L); the launch shape and the sharding are invisible, and the
  * value after p periods does not depend on n_periods (a run with n_periods = p yields column p of a longer run).
  * With block_len = 1 every output is bit-identical to smmc_engine_simulate's in table mode. */
-#define SMMC_BLOCKS_CIRCULAR 0 /* the only kind for now; anything else is SMMC_ERR_INVALID */
+#define SMMC_BLOCKS_CIRCULAR 0 /* the only kind; anything else is SMMC_ERR_INVALID (runs of random length have entries of
+                                  their own: smmc_engine_simulate_stationary) */
 typedef struct smmc_blocks {
   uint32_t struct_size; /* = sizeof(smmc_blocks) */
   uint32_t block_len;   /* L >= 1 */
@@ -436,6 +437,55 @@ int smmc_engine_simulate_blocks_to_host(smmc_engine *e, const smmc_sim *sim, con
  * the IEEE divide. */
 int smmc_engine_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_blocks *blocks);
 
+/* ---- stationary bootstrap: table paths in runs of geometric length ------------------------------- */
+
+/* The block bootstrap cuts every path at the same periods 0, L, 2L, ...: a statistic at period t then depends on
+ * t mod L, the series is not stationary.  The stationary bootstrap (Politis and Romano, 1994) starts a new run at every
+ * period with probability p and otherwise continues with the next month of the table: run lengths are geometric with
+ * mean 1 / p and the series is stationary.  Counter stream v3, table mode only; the table a[i] = 100.0f + r[i] of T
+ * entries, P = n_periods, and ONE parameter q = renew_q16 in [0, 65536]: p = q / 65536.
+ *   candidate start c_t of period t = 0 .. P - 1 is EXACTLY the index the SMMC_MODE_TABLE stream draws for that path at
+ *     period t: Philox4x32-10 block t / D with the key (seed lo, seed hi) and the counter (t / D, id lo, id hi, 0), digit
+ *     t % D, D and the digits as the block bootstrap states them above.  No new index construction.
+ *   renewal field f_t is a 16-bit field of a SECOND Philox4x32-10 block with the same key and the counter
+ *     (t / 8, id lo, id hi, 2): word (t % 8) / 2 of its output, the low half for an even t % 8, the high half for an odd
+ *     one.  The block index is t / 8 whatever D is.  Fourth counter word 2 belongs to these fields alone: 0 is the
+ *     table's, the odd values 1, 3, ... are the Gaussian series' (portfolios below), no other stream uses an even one.
+ *   index: i_0 = c_0; for t >= 1, i_t = c_t if f_t < q, else i_t = i_{t-1} + 1, wrapped to 0 at T (circular, as the block
+ *     bootstrap).  The field of period 0 is not used.
+ *   the step is smmc_update_fund's: total = fl(fl(total * a[i_t]) / 100.0f).
+ * A path depends only on (seed, global path id, table, q); the launch shape and the sharding are invisible, and the value
+ * after p periods does not depend on n_periods.  Two identities, bit for bit in every output:
+ *   q = 65536 is smmc_engine_simulate in table mode;
+ *   q = 0 is smmc_engine_simulate_blocks with any block_len >= n_periods.
+ * The resolution of p is 2^-16. */
+#define SMMC_RENEW_Q16_ONE 65536u /* renew_q16 of p = 1; the largest value accepted */
+typedef struct smmc_stationary {
+  uint32_t struct_size; /* = sizeof(smmc_stationary) */
+  uint32_t renew_q16;   /* q: 0 .. SMMC_RENEW_Q16_ONE */
+  uint32_t reserved[2]; /* 0 */
+} smmc_stationary;
+
+/* smmc_engine_simulate_blocks with these draws: the same outputs with the same meaning (DEVICE pointers, any may be
+ * NULL; d_final, d_chunk_mean, d_chunk_var 4-byte and d_stats 8-byte aligned), enqueued on the engine stream;
+ * n_periods == 0 and n_paths == 0 behave as there.
+ * SMMC_ERR_INVALID with a text: NULL st, a wrong struct_size, renew_q16 > 65536, a reserved word != 0; mode !=
+ * SMMC_MODE_TABLE; SMMC_FLAG_STREAM_V2 or SMMC_FLAG_STREAM_REF; no table set; table and histogram beyond the device's
+ * LDS; the other argument errors of smmc_engine_simulate.
+ * Divide by 100: smmc_engine_stationary_divide_kind; the result does not depend on it. */
+int smmc_engine_simulate_stationary(smmc_engine *e, const smmc_sim *sim, const smmc_stationary *st, float *d_final,
+                                    float *d_chunk_mean, float *d_chunk_var, void *d_stats);
+/* smmc_engine_simulate_to_host with these draws: HOST pointers, the same chunked pipeline, pinning rules, progress
+ * reports and merged record. */
+int smmc_engine_simulate_stationary_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_stationary *st, float *host_final,
+                                            float *host_chunk_mean, float *host_chunk_var, volatile int64_t *progress,
+                                            smmc_stats *stats, uint64_t *hist);
+/* SMMC_DIV_FAST, SMMC_DIV_CHECKED or SMMC_DIV_EXACT: the divide a smmc_engine_simulate_stationary of (sim, st) uses, or
+ * an error of that call's argument checks.  The rule of smmc_engine_divide_kind(e, sim, 0): its bounds come from the
+ * table's extremes, the capital and n_periods, never from the order of the draws; the kernel tests the checked window
+ * once every 8 periods and redoes a path that ever leaves it with the IEEE divide. */
+int smmc_engine_stationary_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_stationary *st);
+
 /* ---- portfolios: jointly drawn assets, weights, periodic rebalancing ---------------------------- */
 
 /* K = n_assets return series per path, drawn JOINTLY, held with weights w_k and rebalanced to them every R =
@@ -462,7 +512,7 @@ int smmc_engine_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const sm
  * Gaussian mode: correlated normals.  Asset j's STANDARD normals z_j for the periods 4b .. 4b + 3 are counter stream
  * v3's Box-Muller draws of the Philox block (b, id lo, id hi, 1 + 2 j) with the launch's key, taken with scale 1.0f and
  * shift 0.0f: asset 0 reads the very words of the plain Gaussian stream; odd fourth words belong to Gaussian assets,
- * even ones stay reserved for the table.  With s_k = fl(100.0f + means[k]) and the lower-triangular factor L (percent),
+ * even ones belong to the table side (0: its indices, 2: the stationary bootstrap's renewal fields).  With s_k = fl(100.0f + means[k]) and the lower-triangular factor L (percent),
  *   a_k = fma(L[k][k], z_k, fma(L[k][k-1], z_{k-1}, ... fma(L[k][0], z_0, s_k))),
  * the terms taken from j = 0 upwards, each step ONE fused multiply-add.  sim->gauss_mean and sim->gauss_std are not
  * read.  K = 1 gives the LAW of the plain Gaussian mode with gauss_std = L[0][0] but not its bits: the plain mode

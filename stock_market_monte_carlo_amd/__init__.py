@@ -5,3 +5,4 @@ from .engine import (AllocationSweepResult, CashflowResult, Engine, ExcursionRes
                      mc_simulations_gpu_reduceBlock, mc_simulations_keepdata, read_historical_returns,
                      reduce_mean_gpu, update_count_below_min, update_fund, update_mean_std, update_quartiles,
                      vector_add_gpu)
+from .stationary import renew_q16_of, simulate_stationary, simulate_stationary_raw, simulate_stationary_to_host, stationary_divide_kind  # noqa: F401

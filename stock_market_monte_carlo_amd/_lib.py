@@ -108,6 +108,18 @@ class Blocks(C.Structure):
 BLOCKS_CIRCULAR = 0
 
 
+class Stationary(C.Structure):
+    """smmc_stationary"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("renew_q16", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+RENEW_Q16_ONE = 65536
+
+
 class Portfolio(C.Structure):
     """smmc_portfolio"""
     _fields_ = [
@@ -262,6 +274,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
       C.c_void_p]),
     ("smmc_engine_blocks_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Blocks)]),
+    ("smmc_engine_simulate_stationary", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Stationary), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_stationary_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Stationary), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+      C.c_void_p]),
+    ("smmc_engine_stationary_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Stationary)]),
     ("smmc_engine_set_asset_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("smmc_engine_simulate_portfolio", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioOutputs)]),

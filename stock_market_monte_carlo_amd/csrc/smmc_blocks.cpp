@@ -26,8 +26,9 @@ int check_blocks(const smmc_engine *e, const smmc_sim *sim, const smmc_blocks *b
 }
 
 constexpr size_t kLdsPerCU = 160u * 1024u;  // CDNA4
+constexpr const char *kLdsHolds = "table, its circular extension and the histogram";
 
-// The LDS layout of a request, and the refusal that follows from it; asked before any device work.
+// The LDS layout of a request; asked before any device work.
 struct Plan {
   bool wide;
   size_t lds;
@@ -44,49 +45,66 @@ int plan(const smmc::EngineView &view, const smmc::KernelArgs &a, uint32_t n_bin
     else if (*env) return host_fail(SMMC_ERR_INVALID, "SMMC_BLOCKS_READ is '%s': b32 or b128", env);
   }
   p->lds = p->wide ? wide : narrow;
-  if (p->lds + 2048 > view.max_lds)
-    return host_fail(SMMC_ERR_INVALID, "table, its circular extension and the histogram need %zu bytes of LDS, device allows %zu",
-                     p->lds, view.max_lds);
-  return SMMC_OK;
+  return SMMC_OK;  // whether it fits: host_check_lds, in host_enqueue_paths and before the _to_host pipeline
 }
 
-// smmc_capi.cpp's enqueue_simulation with blocks_kernel in paths_kernel's place.  Device must be current.
+struct Launch {  // what launch_blocks takes beside the kernel arguments
+  uint32_t block_len;
+  bool wide;
+};
+
+// host_enqueue_paths with blocks_kernel.  Device must be current.
 int enqueue_blocks(smmc_engine *e, const smmc_sim *s, const smmc_blocks *b, float *d_final, float *d_chunk_mean, float *d_chunk_var,
                    void *d_stats) {
-  const smmc::EngineView view = smmc::engine_view(e);
-  smmc::KernelArgs a = smmc::host_make_args(e, s);
+  Plan p = {false, 0};
+  const int rc = s->n_paths ? plan(smmc::engine_view(e), smmc::host_make_args(e, s), d_stats ? s->n_bins : 0u, &p) : SMMC_OK;
+  if (rc) return rc;
+  const Launch l = {b->block_len, p.wide};
+  const smmc::PathLaunch w = {"launch_blocks",
+                              [](const smmc::KernelArgs &a, int div, uint32_t grid, hipStream_t stream, const void *ctx) {
+                                const Launch *l = static_cast<const Launch *>(ctx);
+                                return smmc::launch_blocks(a, l->block_len, l->wide, div, grid, stream);
+                              },
+                              &l, p.lds, kLdsHolds};
+  return smmc::host_enqueue_paths(e, s, w, d_final, d_chunk_mean, d_chunk_var, d_stats);
+}
+
+}  // namespace
+
+// The enqueue this unit lends (smmc_host.h, "lend"): every statement around the launch of a path kernel, once.
+int smmc::host_enqueue_paths(smmc_engine *e, const smmc_sim *s, const PathLaunch &w, float *d_final, float *d_chunk_mean,
+                             float *d_chunk_var, void *d_stats) {
+  const EngineView view = engine_view(e);
+  KernelArgs a = host_make_args(e, s);
   a.d_final = d_final;
   a.d_chunk_mean = d_chunk_mean;
   a.d_chunk_var = d_chunk_var;
-  const uint64_t n_chunks = (s->n_paths + smmc::kBlock - 1) / smmc::kBlock;
+  const uint64_t n_chunks = (s->n_paths + kBlock - 1) / kBlock;
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(n_chunks, view.max_grid));
-  Plan p = {false, 0};
-  int rc = grid ? plan(view, a, d_stats ? s->n_bins : 0u, &p) : SMMC_OK;  // nothing is launched for n_paths == 0
+  int rc = grid ? host_check_lds(view, w.lds, w.lds_holds) : SMMC_OK;  // nothing is launched for n_paths == 0
   if (rc) return rc;
-  smmc::ZeroLease lease;
+  ZeroLease lease;
   if (d_stats) {  // no memset: finalize_kernel writes the whole record and leaves the accumulator zero again
     a.partials = view.d_partials;
     if (s->n_bins) {
-      rc = smmc::engine_acc_lease(e, &lease);
+      rc = engine_acc_lease(e, &lease);
       if (rc) return rc;
       a.d_hist = lease.acc();
     }
   }
   a.clock_probe = view.clock_probe;
   if (grid > 0) {
-    const int div = smmc::host_divide_kind(e, s, true, &a.chk_lo, &a.chk_hi);
-    rc = smmc::host_timed_launch(e, "launch_blocks", [&] { return smmc::launch_blocks(a, b->block_len, p.wide, div, grid, view.stream); });
+    const int div = host_divide_kind(e, s, true, &a.chk_lo, &a.chk_hi);
+    rc = host_timed_launch(e, w.name, [&] { return w.launch(a, div, grid, view.stream, w.ctx); });
     if (rc) return rc;
   }
   if (d_stats) {
-    SMMC_HIP(smmc::launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, lease.acc(),
-                                   s->n_bins ? 1u : 0u));
+    SMMC_HIP(launch_finalize(view.d_partials, grid, static_cast<smmc_stats *>(d_stats), s->n_bins, view.stream, lease.acc(),
+                             s->n_bins ? 1u : 0u));
     lease.finalize_queued();
   }
   return SMMC_OK;
 }
-
-}  // namespace
 
 // What this unit refuses about `blocks`, the mode and the stream of a checked sim (smmc_host.h, "lend").
 int smmc::blocks_check(const smmc_sim *sim, const smmc_blocks *b) {
@@ -126,6 +144,7 @@ int smmc_engine_simulate_blocks_to_host(smmc_engine *e, const smmc_sim *sim, con
   if (rc) return rc;
   Plan p;  // refuse before the pipeline allocates anything
   rc = sim->n_paths ? plan(smmc::engine_view(e), smmc::host_make_args(e, sim), (stats || hist) ? sim->n_bins : 0u, &p) : SMMC_OK;
+  if (!rc && sim->n_paths) rc = smmc::host_check_lds(smmc::engine_view(e), p.lds, kLdsHolds);
   if (rc) return rc;
   return smmc::host_simulate_to_host(
       e, sim, host_final, host_chunk_mean, host_chunk_var, progress, stats, hist,

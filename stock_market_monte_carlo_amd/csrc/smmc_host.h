@@ -228,6 +228,25 @@ int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cash
 // smmc_blocks.cpp, to smmc_portfolio_cashflow_blocks.cpp: what smmc_engine_simulate_blocks refuses about `blocks`, the mode
 // and the stream of a checked sim, with its texts.
 int blocks_check(const smmc_sim *sim, const smmc_blocks *b);
+// smmc_blocks.cpp, to smmc_stationary.cpp: its enqueue -- smmc_capi.cpp's enqueue_simulation around another path kernel:
+// the kernel arguments of a checked sim, the grid, the LDS refusal, the accumulator lease, the divide, the timed launch
+// and the fold -- with the kernel left to the caller.  Device must be current.  launch(a, div, grid, stream, ctx)
+// enqueues the kernel and is reported under `name` when it fails; `lds` is what it asks of LDS for these outputs and
+// `lds_holds` the words of the refusal ("<lds_holds> need N bytes of LDS, device allows M").  Nothing is launched and
+// nothing refused for n_paths == 0.
+struct PathLaunch {
+  const char *name;
+  hipError_t (*launch)(const KernelArgs &a, int div, uint32_t grid, hipStream_t stream, const void *ctx);
+  const void *ctx;
+  size_t lds;
+  const char *lds_holds;
+};
+inline int host_check_lds(const EngineView &view, size_t lds, const char *lds_holds) {  // 2 KiB stay free for the runtime
+  if (lds + 2048 > view.max_lds) return host_fail(SMMC_ERR_INVALID, "%s need %zu bytes of LDS, device allows %zu", lds_holds, lds, view.max_lds);
+  return SMMC_OK;
+}
+int host_enqueue_paths(smmc_engine *e, const smmc_sim *s, const PathLaunch &w, float *d_final, float *d_chunk_mean, float *d_chunk_var,
+                       void *d_stats);
 
 // ---- what the entries of the feature units share: the checks of their outputs, the run, the _to_host form ----------
 // An *_outputs structure of include/smmc.h that begins with struct_size and reserved; `type` is its name.

@@ -236,6 +236,12 @@ size_t excursions_lds_bytes(int32_t mode, uint32_t table_len, uint32_t n_periods
 // `grid` workgroups of kBlock threads, one partial each.
 hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int div, uint32_t grid, hipStream_t stream);
 size_t blocks_lds_bytes(uint32_t table_len, uint32_t n_bins, bool wide);
+// stationary_kernel (smmc_engine_simulate_stationary, csrc/smmc_stationary.cpp; counter stream v3, table mode): the
+// outputs of launch_paths for paths that start a new run of consecutive table entries with probability renew_q16 / 65536
+// at every period ("Stationary bootstrap").  renew_q16 <= SMMC_RENEW_Q16_ONE; `grid` workgroups of kBlock
+// threads, one partial each; one plain copy of the table in LDS.
+hipError_t launch_stationary(const KernelArgs &a, uint32_t renew_q16, int div, uint32_t grid, hipStream_t stream);
+size_t stationary_lds_bytes(uint32_t table_len, uint32_t n_bins);
 // portfolio_kernel (smmc_engine_simulate_portfolio, csrc/smmc_portfolio.cpp; counter stream v3 only): K jointly drawn
 // assets per path, held with weights and rebalanced every `rebalance_every` periods ("Portfolios").
 // Table mode: a.table_a is the asset table, a.table_len rows of portfolio_row_words(K) words (a = 100.0f + r, padding

@@ -1301,6 +1301,100 @@ void blocks_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t bloc
   blocks_body<BlocksWalk<kDiv, kDense, kWide>>(k, vgrid, block_len, lds_raw);
 }
 
+// ---- stationary bootstrap: table paths in runs of geometric length ---------------------------------
+//
+// smmc_engine_simulate_stationary (csrc/smmc_stationary.cpp; DESIGN.md, "Stationary bootstrap").  Every period t of a
+// path has a candidate start c_t -- exactly the index the table stream draws for that path at period t, block_starts'
+// digits -- and a 16-bit renewal field f_t out of a second Philox block (t / 8, id lo, id hi, kRenewTag) with the same
+// key: the path starts a new run at c_t when f_t < q and otherwise reads on, i_t = i_{t-1} + 1, wrapped to 0 at T.
+// Every lane has boundaries of its own, so nothing of block_run's wave-uniform run applies; but both counters are
+// wave-uniform, the scalar rounds 0 and 1 of philox4x32_10<kPhiloxUniformBlock> hold for both blocks, and the loop has
+// no divergent branch: the choice is a select.  One plain copy of the table is staged: the wrap is a select too.
+constexpr uint32_t kRenewTag = 2u;  // fourth counter word of the renewal fields: 0 is the table's, odd ones the Gaussian series'
+constexpr int kRenewSeg = 8;        // periods per block of renewal fields: four words, two 16-bit fields each
+
+// Field j = 0 .. 7 of a block of renewal fields: word j / 2, the low half for an even j, the high half for an odd one.
+__device__ __forceinline__ uint32_t renewal_field(const uint32_t (&f)[4], int j) { return (j & 1) ? f[j >> 1] >> 16 : f[j >> 1] & 0xffffu; }
+
+// The table index of a period from the index of the period before (prev < T), the period's candidate start and its
+// renewal field; `first` (wave-uniform): period 0, which takes its candidate whatever the field.  The device-side draw
+// of the stationary bootstrap, for whichever kernel walks such paths.
+__device__ __forceinline__ uint32_t stationary_index(uint32_t prev, uint32_t candidate, uint32_t field, uint32_t q, uint32_t T, bool first) {
+  const uint32_t next = prev + 1u;
+  const uint32_t on = next >= T ? 0u : next;
+  return (first || field < q) ? candidate : on;
+}
+
+// Periods 8 g .. 8 g + n - 1 of a path, n = 8 (kFull) or the path's last 1 .. 7 (wave-uniform).
+template <bool kExactDiv, bool kDense, bool kFull>
+__device__ __forceinline__ void stationary_segment(const KernelArgs &k, uint32_t q, const DrawRegs &dr, const float *lds, uint32_t path_lo,
+                                                   uint32_t path_hi, uint32_t g, uint32_t n, uint32_t &idx, float &total) {
+  uint32_t c[kRenewSeg];
+  if constexpr (kDense) {
+    block_starts<true>(k, dr, path_lo, path_hi, g, c);
+  } else {  // four candidates per block of the table stream: blocks 2 g and 2 g + 1 (g < 2^29)
+    uint32_t lo[4], hi[4] = {0u, 0u, 0u, 0u};
+    block_starts<false>(k, dr, path_lo, path_hi, 2u * g, lo);
+    if (kFull || n > 4u) block_starts<false>(k, dr, path_lo, path_hi, 2u * g + 1u, hi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      c[j] = lo[j];
+      c[4 + j] = hi[j];
+    }
+  }
+  uint32_t f[4];
+  philox4x32_10<kPhiloxUniformBlock>(g, path_lo, path_hi, kRenewTag, k.key0, k.key1, dr, f);
+#pragma unroll
+  for (int j = 0; j < kRenewSeg; ++j) {
+    if (kFull || static_cast<uint32_t>(j) < n) {
+      idx = stationary_index(idx, c[j], renewal_field(f, j), q, k.table_len, j == 0 && g == 0u);
+      total = compound<kExactDiv>(total, lds[idx]);
+    }
+  }
+}
+
+template <int kDiv, bool kDense>
+__device__ __forceinline__ float simulate_stationary_path(const KernelArgs &k, uint32_t q, const DrawRegs &dr, const float *lds, uint64_t path) {
+  constexpr bool kExactDiv = kDiv == kDivExact;
+  const uint32_t path_lo = static_cast<uint32_t>(path);
+  const uint32_t path_hi = static_cast<uint32_t>(path >> 32);
+  float total = k.initial_capital;
+  bool left_window = false;
+  uint32_t idx = 0;
+  const uint32_t full = k.n_periods / kRenewSeg;
+  for (uint32_t g = 0; g < full; ++g) {
+    stationary_segment<kExactDiv, kDense, true>(k, q, dr, lds, path_lo, path_hi, g, kRenewSeg, idx, total);
+    // one test per 8 periods, the span the host derives the window for (smmc_capi.cpp, divide_kind)
+    if constexpr (kDiv == kDivChecked) left_window |= !(total > k.chk_lo && total < k.chk_hi);  // NaN leaves too
+  }
+  const uint32_t rem = k.n_periods - full * kRenewSeg;
+  if (rem) stationary_segment<kExactDiv, kDense, false>(k, q, dr, lds, path_lo, path_hi, full, rem, idx, total);  // wave-uniform
+  if constexpr (kDiv == kDivChecked) {
+    if (left_window) total = simulate_stationary_path<kDivExact, kDense>(k, q, dr, lds, path);
+  }
+  return total;
+}
+
+template <int kDiv, bool kDense>
+struct StationaryWalk {  // aux: renew_q16, the renewal probability in units of 2^-16
+  static __device__ __forceinline__ uint32_t table_words(const KernelArgs &k, uint32_t) { return k.table_len; }
+  static __device__ __forceinline__ void stage(const KernelArgs &k, uint32_t, float *lds_table, uint32_t threads) {
+    for (uint32_t i = threadIdx.x; i < k.table_len; i += threads) lds_table[i] = k.table_a[i];
+  }
+  static __device__ __forceinline__ float simulate(const KernelArgs &k, uint32_t q, const DrawRegs &dr, const float *lds_table, uint64_t path) {
+    return simulate_stationary_path<kDiv, kDense>(k, q, dr, lds_table, path);
+  }
+};
+// The stationary walk inside blocks_body: its chunk walk, outputs and epilogue as they are.  65 .. 69 VGPRs, seven waves
+// per SIMD: eight candidates and four words of fields are live beside the Philox state and the round keys; asked for
+// eight waves (64 VGPRs, as blocks_kernel) the compiler spills one 64-bit accumulator around the period loop.
+template <int kDiv, bool kDense>
+__global__ __launch_bounds__(kBlock)
+void stationary_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t renew_q16) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  blocks_body<StationaryWalk<kDiv, kDense>>(k, vgrid, renew_q16, lds_raw);
+}
+
 // ---- the wave walk: the skeleton of checkpoints_kernel, cashflow_kernel and excursions_kernel ------
 //
 // Three kernels are one program with another step in the middle: the paths of paths_kernel, looked at after every
@@ -4051,6 +4145,38 @@ hipError_t launch_blocks(const KernelArgs &a, uint32_t block_len, bool wide, int
                 : launch_blocks_layout<false, false>(a, block_len, div, grid, lds, stream);
   return wide ? launch_blocks_layout<true, true>(a, block_len, div, grid, lds, stream)
               : launch_blocks_layout<true, false>(a, block_len, div, grid, lds, stream);
+}
+
+// ---- stationary bootstrap ----
+
+size_t stationary_lds_bytes(uint32_t table_len, uint32_t n_bins) {
+  // paths_lds_bytes in table mode: one plain copy of the table in front of the histogram
+  const size_t words = (static_cast<size_t>(table_len) + n_bins + 1u) & ~static_cast<size_t>(1);
+  return words * 4u + 4u * kWaves * sizeof(double) + kWaves * sizeof(BlockPartial);
+}
+
+template <int kDiv, bool kDense>
+static hipError_t launch_stationary_variant(const KernelArgs &a, uint32_t renew_q16, uint32_t grid, size_t lds, hipStream_t stream) {
+  hipError_t err = allow_lds(stationary_kernel<kDiv, kDense>, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((stationary_kernel<kDiv, kDense>), dim3(grid), dim3(kBlock), lds, stream, a, grid, renew_q16);
+  return hipGetLastError();
+}
+
+template <bool kDense>
+static hipError_t launch_stationary_layout(const KernelArgs &a, uint32_t renew_q16, int div, uint32_t grid, size_t lds, hipStream_t stream) {
+  switch (div) {
+    case SMMC_DIV_FAST: return launch_stationary_variant<kDivFast, kDense>(a, renew_q16, grid, lds, stream);
+    case SMMC_DIV_CHECKED: return launch_stationary_variant<kDivChecked, kDense>(a, renew_q16, grid, lds, stream);
+    default: return launch_stationary_variant<kDivExact, kDense>(a, renew_q16, grid, lds, stream);
+  }
+}
+
+hipError_t launch_stationary(const KernelArgs &a, uint32_t renew_q16, int div, uint32_t grid, hipStream_t stream) {
+  if (a.mode != SMMC_MODE_TABLE || a.stream != 3 || !a.table_len || renew_q16 > SMMC_RENEW_Q16_ONE) return hipErrorInvalidValue;
+  const size_t lds = stationary_lds_bytes(a.table_len, a.partials ? a.n_bins : 0u);
+  return table_is_dense(a.table_len) ? launch_stationary_layout<true>(a, renew_q16, div, grid, lds, stream)
+                                     : launch_stationary_layout<false>(a, renew_q16, div, grid, lds, stream);
 }
 
 // ---- excursions ----
