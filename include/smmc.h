@@ -687,6 +687,53 @@ int smmc_engine_simulate_portfolio_cashflow_blocks_to_host(smmc_engine *e, const
 int smmc_engine_portfolio_cashflow_blocks_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                       const smmc_cashflow *cf, const smmc_blocks *blocks);
 
+/* ---- stationary-bootstrap plans: portfolio cash flows on runs of geometric length ---------------- */
+
+/* smmc_engine_simulate_portfolio_cashflow on rows chosen as smmc_engine_simulate_stationary chooses its entries: the block
+ * plan above cuts every path at the same periods, so a survival probability or a depletion count at period t depends on
+ * t mod L; here a path starts a new run at every period with probability p = st->renew_q16 / 65536 and the series of rows
+ * is stationary.  Scope: SMMC_MODE_TABLE and counter stream v3 only; the table is the one given by
+ * smmc_engine_set_asset_table, T = n_rows; K = 1 .. 4 assets, P = n_periods, q = renew_q16 in [0, 65536].
+ * Row rule: period t = 0 .. P - 1 (0-based) of a path reads row i_t of the asset table, for every asset.  i_0 = c_0; for
+ *     t > 0, i_t = c_t if f_t < q, else i_{t-1} + 1, wrapped to 0 at n_rows.
+ *   c_t is EXACTLY the row smmc_engine_simulate_portfolio's table stream draws for that path at 0-based period t: the same
+ *     key, counter (t / D, id lo, id hi, 0) and digits over n_rows, D = 8 for n_rows <= 2048 and 4 above.
+ *   f_t is the renewal field of the stationary bootstrap above, unchanged: the Philox4x32-10 block with the launch's key
+ *     and the counter (t / 8, id lo, id hi, 2), word (t % 8) / 2 of its output, the low half for an even t % 8, the high
+ *     half for an odd one.  The field of period 0 is not used.
+ * No other random numbers are drawn.
+ * Recurrence: everything after the row is smmc_engine_simulate_portfolio_cashflow's, word for word (0-based period t is
+ *     that call's period t + 1) -- the holdings, the left-to-right value, the flow, settling at the target weights, the
+ *     rebalance, the floor, depletion, the six outputs, the exactness of the record and the counts, byte-identical repeat
+ *     calls, shards merged by smmc_stats_merge and by adding d_depleted_at, n_paths == 0.
+ * Depleted paths: a depleted path keeps drawing its candidates and fields and walking its index; nothing of a path depends
+ *     on another path's state.  A path depends only on (seed, global path id, table, weights, R, schedule, floor, q).
+ * Identities, bit for bit on every output (sum and sumsq of the record follow the launch shape, which is the same):
+ *   1. q = 65536 is smmc_engine_simulate_portfolio_cashflow in table mode.
+ *   2. q = 0 is smmc_engine_simulate_portfolio_cashflow_blocks with any block_len >= n_periods: one run from c_0.
+ *   3. K = 1, w_0 = 1, zero amount and fraction, floor 0: d_final equals the final values of
+ *      smmc_engine_simulate_stationary for the same column (also given to smmc_engine_set_table), seed, ids and q, for
+ *      every path that never depletes, whatever divide either call takes.
+ * SMMC_ERR_INVALID with a text, before any device work, in this order: everything smmc_engine_simulate_portfolio refuses
+ * of (sim, pf); everything smmc_engine_simulate_cashflow refuses of the schedule; everything
+ * smmc_engine_simulate_stationary refuses of st (NULL, a wrong struct_size, mode != SMMC_MODE_TABLE, a stream flag,
+ * renew_q16 > 65536, a reserved word != 0); the outputs structure; the asset table, the n_periods + 1 depletion counters,
+ * the n_bins buckets and the waves' partials beyond the device's LDS less 2048 bytes (the text names both numbers).  out
+ * holds DEVICE pointers as in the parent.  Asynchronous on the engine stream. */
+int smmc_engine_simulate_portfolio_cashflow_stationary(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                       const smmc_cashflow *cf, const smmc_stationary *st,
+                                                       const smmc_portfolio_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_portfolio_cashflow_stationary_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                               const smmc_cashflow *cf, const smmc_stationary *st,
+                                                               const smmc_portfolio_cashflow_outputs *out);
+/* After the call's argument checks, st included: what smmc_engine_portfolio_cashflow_divide_kind(e, sim, pf, cf) returns,
+ * SMMC_DIV_FAST or SMMC_DIV_EXACT (this family has no checked form).  That rule's bounds never depend on the order of the
+ * rows ("Block-bootstrap plans"), and a stationary path is the parent's recurrence on another order of the same
+ * rows.  Results never depend on the form. */
+int smmc_engine_portfolio_cashflow_stationary_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                          const smmc_cashflow *cf, const smmc_stationary *st);
+
 /* ---- portfolio cash-flow checkpoints: the value distribution along a plan ----------------------- */
 
 /* "What does my wealth look like in year 5, 10, 15 ... under this plan": smmc_engine_simulate_portfolio_cashflow with

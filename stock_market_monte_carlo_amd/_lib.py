@@ -298,6 +298,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Blocks), C.POINTER(PortfolioCashflowOutputs)]),
     ("smmc_engine_portfolio_cashflow_blocks_divide_kind", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Blocks)]),
+    ("smmc_engine_simulate_portfolio_cashflow_stationary", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Stationary), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_simulate_portfolio_cashflow_stationary_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Stationary), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_portfolio_cashflow_stationary_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Stationary)]),
     ("smmc_engine_simulate_portfolio_cashflow_checkpoints", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_void_p, C.c_uint32,
       C.POINTER(PortfolioCashflowOutputs), C.c_void_p]),

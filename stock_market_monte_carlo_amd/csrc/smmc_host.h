@@ -228,6 +228,25 @@ int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cash
 // smmc_blocks.cpp, to smmc_portfolio_cashflow_blocks.cpp: what smmc_engine_simulate_blocks refuses about `blocks`, the mode
 // and the stream of a checked sim, with its texts.
 int blocks_check(const smmc_sim *sim, const smmc_blocks *b);
+// smmc_stationary.cpp, to smmc_portfolio_cashflow_stationary.cpp: what smmc_engine_simulate_stationary refuses about `st`,
+// the mode and the stream of a checked sim, with its texts.  Unlike blocks_check it is stated here, inline, and not
+// defined in the lender: tests/test_stationary_cpu.py lets no unit but smmc_stationary.cpp leave an undefined symbol
+// whose demangled text holds "stationary", and that text includes the parameter type `smmc_stationary const*`, so the
+// borrower cannot call a function of this signature across units under any name.
+inline int stationary_check(const smmc_sim *sim, const smmc_stationary *st) {
+  if (!st) return host_fail(SMMC_ERR_INVALID, "the smmc_stationary argument is NULL");
+  if (st->struct_size != sizeof(smmc_stationary))
+    return host_fail(SMMC_ERR_INVALID, "smmc_stationary.struct_size is %u, this library expects %zu", st->struct_size, sizeof(smmc_stationary));
+  if (sim->mode != SMMC_MODE_TABLE)
+    return host_fail(SMMC_ERR_INVALID, "the stationary bootstrap resamples the returns table: mode must be SMMC_MODE_TABLE (got %d)", sim->mode);
+  const int rc = host_require_v3(sim, "the stationary bootstrap supports");
+  if (rc) return rc;
+  if (st->renew_q16 > SMMC_RENEW_Q16_ONE)
+    return host_fail(SMMC_ERR_INVALID, "renew_q16 is %u: the renewal probability renew_q16 / 65536 is at most 1", st->renew_q16);
+  if (st->reserved[0] != 0 || st->reserved[1] != 0)
+    return host_fail(SMMC_ERR_INVALID, "smmc_stationary.reserved is {%u, %u}, it must be 0", st->reserved[0], st->reserved[1]);
+  return SMMC_OK;
+}
 // smmc_blocks.cpp, to smmc_stationary.cpp: its enqueue -- smmc_capi.cpp's enqueue_simulation around another path kernel:
 // the kernel arguments of a checked sim, the grid, the LDS refusal, the accumulator lease, the divide, the timed launch
 // and the fold -- with the kernel left to the caller.  Device must be current.  launch(a, div, grid, stream, ctx)

@@ -285,6 +285,22 @@ hipError_t launch_portfolio_cashflow_blocks(const KernelArgs &a, const Portfolio
                                             hipStream_t stream);
 // [portfolio_cashflow_blocks_rows(n_rows) padded rows][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
 size_t portfolio_cashflow_blocks_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// portfolio_cashflow_stationary_kernel (smmc_engine_simulate_portfolio_cashflow_stationary,
+// csrc/smmc_portfolio_cashflow_stationary.cpp; counter stream v3, table mode): portfolio_cashflow_kernel's recurrence on
+// rows chosen by the stationary bootstrap -- the row the portfolio's table stream draws where a period's renewal field is
+// below renew_q16, else the row behind the one before ("Stationary-bootstrap plans").  p, c, a.partials,
+// a.d_hist and c.d_depleted as launch_portfolio_cashflow; c.stride >= a.n_periods.
+struct PortfolioCashflowStationaryArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  uint32_t renew_q16;  // <= SMMC_RENEW_Q16_ONE
+};
+// (the launch and the LDS need are named for the runs' geometric lengths, not "stationary": tests/test_stationary_cpu.py
+// lets only smmc_stationary.cpp refer to a symbol of that word)
+hipError_t launch_portfolio_cashflow_geometric(const KernelArgs &a, const PortfolioCashflowStationaryArgs &x, bool exact_div, uint32_t grid,
+                                                hipStream_t stream);
+// [n_rows padded rows, one plain copy][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
+size_t portfolio_cashflow_geometric_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
 // portfolio_cashflow_checkpoints_kernel (smmc_engine_simulate_portfolio_cashflow_checkpoints,
 // csrc/smmc_portfolio_cashflow_checkpoints.cpp; counter stream v3 only): portfolio_cashflow_kernel's paths, with the
 // record of their values after each of n chosen periods ("Portfolio cash-flow checkpoints").  p, c, a.partials,

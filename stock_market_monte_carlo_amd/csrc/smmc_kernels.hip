@@ -1326,6 +1326,8 @@ __device__ __forceinline__ uint32_t stationary_index(uint32_t prev, uint32_t can
 }
 
 // Periods 8 g .. 8 g + n - 1 of a path, n = 8 (kFull) or the path's last 1 .. 7 (wave-uniform).
+// stationary_rows (stationary-bootstrap plans, below) gathers candidates and fields the same way, line for line: a
+// change to how either is taken here must be made there too.
 template <bool kExactDiv, bool kDense, bool kFull>
 __device__ __forceinline__ void stationary_segment(const KernelArgs &k, uint32_t q, const DrawRegs &dr, const float *lds, uint32_t path_lo,
                                                    uint32_t path_hi, uint32_t g, uint32_t n, uint32_t &idx, float &total) {
@@ -3054,6 +3056,139 @@ void portfolio_cashflow_blocks_kernel(const KernelArgs k, const PortfolioCashflo
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- stationary-bootstrap plans: portfolio cash flows on runs of geometric length -------------------
+//
+// smmc_engine_simulate_portfolio_cashflow_stationary (csrc/smmc_portfolio_cashflow_stationary.cpp; include/smmc.h and
+// DESIGN.md, "Stationary-bootstrap plans", state the contract): portfolio_cashflow_kernel's recurrence -- the same
+// portfolio_cashflow_step, called, not restated -- on rows chosen as stationary_kernel chooses its entries: the same
+// stationary_index, renewal_field, kRenewTag and kRenewSeg, called, not restated.  Table mode only; a family of its own:
+// portfolio_cashflow_kernel, portfolio_cashflow_blocks_kernel and stationary_kernel compile to what they compiled to before.
+//
+// Rows.  One plain copy of the asset table at LDS address 0, one row per month padded to 1, 2 or 4 words
+// (load_asset_row): the wrap at n_rows is stationary_index's select, so nothing is staged beyond the last row.
+//
+// Segments.  A path is walked in segments of kRenewSeg = 8 periods.  stationary_rows takes the segment's eight
+// candidates -- one block_starts<true> block for a dense table; blocks 2 g and 2 g + 1 for a four-draw one, the second
+// only if the segment has more than four periods -- and one block of renewal fields, and forms the segment's row
+// indices BEFORE the first step: candidates and fields are dead when the holdings' chains begin.  Then eight times
+// load_asset_row and portfolio_cashflow_step; the path's last 1 .. 7 periods under a wave-uniform test per period.  A
+// depleted lane keeps drawing and walking its index: nothing of a path depends on another path's state.
+//
+// Control flow is wave-uniform: the period, the segment's end and the rebalance countdown are scalars, the row is a
+// per-lane select.  Both Philox counters are wave-uniform in word 0: philox4x32_10<kPhiloxUniformBlock> for both blocks.
+//
+// Schedule (kVarying): entry t - 1 is read for period t with the wave-uniform index through the constant address space,
+// only for periods that exist (t <= P <= stride), as portfolio_cashflow_blocks_kernel does.
+//
+// LDS: [n_rows padded rows][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
+// (portfolio_cashflow_geometric_lds_bytes).
+//
+// The row indices of periods 8 g .. 8 g + n - 1 (0-based) of a path, n = 8 (kFull) or the path's last 1 .. 7
+// (wave-uniform); idx: the index of the period before, left at that of the segment's last period.
+// The gathering of candidates and fields repeats stationary_segment's (stationary bootstrap, above) line for line, so
+// that stationary_kernel keeps its instructions: the two copies must change together.
+template <bool kDense, bool kFull>
+__device__ __forceinline__ void stationary_rows(const KernelArgs &k, uint32_t q, const DrawRegs &dr, uint32_t path_lo, uint32_t path_hi,
+                                                uint32_t g, uint32_t n, uint32_t &idx, uint32_t (&row)[kRenewSeg]) {
+  uint32_t c[kRenewSeg];
+  if constexpr (kDense) {
+    block_starts<true>(k, dr, path_lo, path_hi, g, c);
+  } else {  // four candidates per block of the table stream: blocks 2 g and 2 g + 1 (g < 2^29)
+    uint32_t lo[4], hi[4] = {0u, 0u, 0u, 0u};
+    block_starts<false>(k, dr, path_lo, path_hi, 2u * g, lo);
+    if (kFull || n > 4u) block_starts<false>(k, dr, path_lo, path_hi, 2u * g + 1u, hi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      c[j] = lo[j];
+      c[4 + j] = hi[j];
+    }
+  }
+  uint32_t f[4];
+  philox4x32_10<kPhiloxUniformBlock>(g, path_lo, path_hi, kRenewTag, k.key0, k.key1, dr, f);
+#pragma unroll
+  for (int j = 0; j < kRenewSeg; ++j) {
+    if (kFull || static_cast<uint32_t>(j) < n) {  // row[j] of a period that does not exist is left unset and never read
+      idx = stationary_index(idx, c[j], renewal_field(f, j), q, k.table_len, j == 0 && g == 0u);
+      row[j] = idx;
+    }
+  }
+}
+
+template <bool kExactDiv, bool kDense, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(SMMC_MODE_TABLE))
+void portfolio_cashflow_stationary_kernel(const KernelArgs k, const PortfolioCashflowStationaryArgs x) {
+  constexpr int kMode = SMMC_MODE_TABLE;
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  KernelArgs staged = k;  // what walk_setup stages: whole rows (k.table_len stays the number of rows, for the draw)
+  staged.table_len = k.table_len * portfolio_row_words(K);
+  const WalkLds s = walk_setup<kMode>(staged, lds_raw, staged.table_len, k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+  const uint32_t P = k.n_periods, q = x.renew_q16;
+  const uint32_t full = P / kRenewSeg, rem = P - full * kRenewSeg;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    uint32_t idx = 0u;       // the row of the period before; period 0 takes its candidate
+    uint32_t row[kRenewSeg];
+    // period t0 + j + 1 (1-based) on row[j]
+    auto period = [&](uint32_t t0, int j) {
+      float a[K];
+      load_asset_row<K>(row[j], a);
+      const float am = kVarying ? amounts[t0 + j] : c.amount;
+      const float fr = kVarying ? fractions[t0 + j] : c.fraction;
+      portfolio_cashflow_step<kExactDiv, K>(a, p.weights, am, fr, c.floor, every, P, t0 + j + 1u, h, v, paid, ruin, alive, until);
+    };
+    for (uint32_t g = 0; g < full; ++g) {
+      stationary_rows<kDense, true>(k, q, dr, path_lo, path_hi, g, kRenewSeg, idx, row);
+#pragma unroll
+      for (int j = 0; j < kRenewSeg; ++j) period(g * kRenewSeg, j);
+    }
+    if (rem) {  // wave-uniform: the path's last 1 .. 7 periods
+      stationary_rows<kDense, false>(k, q, dr, path_lo, path_hi, full, rem, idx, row);
+#pragma unroll
+      for (int j = 0; j < kRenewSeg - 1; ++j)
+        if (static_cast<uint32_t>(j) < rem) period(full * kRenewSeg, j);
+    }
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 // ---- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods ---------------
 //
 // smmc_engine_simulate_portfolio_cashflow_checkpoints (csrc/smmc_portfolio_cashflow_checkpoints.cpp; include/smmc.h and
@@ -3731,6 +3866,16 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_BLOCKS_KERNELS
+#define SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(K, V) /* table mode only */                                               \
+  reinterpret_cast<const void *>(portfolio_cashflow_stationary_kernel<false, true, K, V>),                                   \
+      reinterpret_cast<const void *>(portfolio_cashflow_stationary_kernel<true, true, K, V>),                                \
+      reinterpret_cast<const void *>(portfolio_cashflow_stationary_kernel<false, false, K, V>),                              \
+      reinterpret_cast<const void *>(portfolio_cashflow_stationary_kernel<true, false, K, V>)
+      SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(1, false), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(2, false),
+      SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(3, false), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(4, false),
+      SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(2, true),
+      SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(4, true),
+#undef SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS
 #define SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(K, V)                                                                  \
   reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),             \
       reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),          \
@@ -4289,6 +4434,47 @@ hipError_t launch_portfolio_cashflow_blocks(const KernelArgs &a, const Portfolio
   if (x.c.schedule && x.c.stride < a.n_periods) return hipErrorInvalidValue;
   const size_t lds = portfolio_cashflow_blocks_lds_bytes(a.table_len, x.p.n_assets, a.n_periods, a.n_bins);
   const WalkKernel<PortfolioCashflowBlocksArgs> kernel = PortfolioCashflowBlocksFamily::get(a, x, exact_div);
+  const hipError_t err = allow_lds(kernel, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(SMMC_MODE_TABLE)), lds, stream, a, x);
+  return hipGetLastError();
+}
+
+// ---- stationary-bootstrap plans ----
+
+size_t portfolio_cashflow_geometric_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins) {
+  // the parent's table-mode layout: one plain copy of the padded rows, the wrap is the draw's select
+  return wave_walk_lds_bytes(SMMC_MODE_TABLE, n_rows * portfolio_row_words(n_assets), static_cast<size_t>(n_periods) + 1u + n_bins, 1u);
+}
+
+struct PortfolioCashflowStationaryFamily {  // table mode only: its own ladder, dense | four-draw table times exact | fast divide
+  template <bool kExactDiv, bool kDense, int K>
+  static WalkKernel<PortfolioCashflowStationaryArgs> schedule(const PortfolioCashflowStationaryArgs &x) {
+    return x.c.schedule ? portfolio_cashflow_stationary_kernel<kExactDiv, kDense, K, true>
+                        : portfolio_cashflow_stationary_kernel<kExactDiv, kDense, K, false>;
+  }
+  template <bool kExactDiv, bool kDense>
+  static WalkKernel<PortfolioCashflowStationaryArgs> assets(const PortfolioCashflowStationaryArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return schedule<kExactDiv, kDense, 1>(x);
+      case 2: return schedule<kExactDiv, kDense, 2>(x);
+      case 3: return schedule<kExactDiv, kDense, 3>(x);
+      default: return schedule<kExactDiv, kDense, 4>(x);
+    }
+  }
+  static WalkKernel<PortfolioCashflowStationaryArgs> get(const KernelArgs &a, const PortfolioCashflowStationaryArgs &x, bool exact_div) {
+    if (table_is_dense(a.table_len)) return exact_div ? assets<true, true>(x) : assets<false, true>(x);
+    return exact_div ? assets<true, false>(x) : assets<false, false>(x);
+  }
+};
+hipError_t launch_portfolio_cashflow_geometric(const KernelArgs &a, const PortfolioCashflowStationaryArgs &x, bool exact_div, uint32_t grid,
+                                                hipStream_t stream) {
+  if (a.stream != 3 || a.mode != SMMC_MODE_TABLE || !a.table_len || !a.table_a || x.renew_q16 > SMMC_RENEW_Q16_ONE) return hipErrorInvalidValue;
+  if (x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && x.c.stride < a.n_periods) return hipErrorInvalidValue;
+  const size_t lds = portfolio_cashflow_geometric_lds_bytes(a.table_len, x.p.n_assets, a.n_periods, a.n_bins);
+  const WalkKernel<PortfolioCashflowStationaryArgs> kernel = PortfolioCashflowStationaryFamily::get(a, x, exact_div);
   const hipError_t err = allow_lds(kernel, lds);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(SMMC_MODE_TABLE)), lds, stream, a, x);

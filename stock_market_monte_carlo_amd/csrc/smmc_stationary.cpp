@@ -1,7 +1,8 @@
 // smmc_stationary.cpp -- smmc_engine_simulate_stationary, its _to_host form and smmc_engine_stationary_divide_kind
 // (include/smmc.h): table paths in runs of geometric length, the stationary bootstrap of Politis and Romano.
 //
-// A translation unit of its own, as smmc_blocks.cpp: it holds the argument checks, the LDS need and the three entries.
+// A translation unit of its own, as smmc_blocks.cpp: it holds the LDS need and the three entries; the checks of `st`
+// are stationary_check (smmc_host.h), shared with smmc_portfolio_cashflow_stationary.cpp.
 // The run -- kernel arguments, grid, accumulator lease, divide, timed launch, fold -- is smmc_blocks.cpp's, lent through
 // smmc_host.h (host_enqueue_paths) with launch_stationary as its kernel; the _to_host form is host_simulate_to_host
 // around the same enqueue.  It keeps no state per engine.  The reference resamples single months
@@ -19,20 +20,8 @@ using smmc::host_fail;
 constexpr const char *kLdsHolds = "table and histogram";
 
 int check_stationary(const smmc_engine *e, const smmc_sim *sim, const smmc_stationary *st) {
-  int rc = smmc::host_check_sim(e, sim);
-  if (rc) return rc;
-  if (!st) return host_fail(SMMC_ERR_INVALID, "the smmc_stationary argument is NULL");
-  if (st->struct_size != sizeof(smmc_stationary))
-    return host_fail(SMMC_ERR_INVALID, "smmc_stationary.struct_size is %u, this library expects %zu", st->struct_size, sizeof(smmc_stationary));
-  if (sim->mode != SMMC_MODE_TABLE)
-    return host_fail(SMMC_ERR_INVALID, "the stationary bootstrap resamples the returns table: mode must be SMMC_MODE_TABLE (got %d)", sim->mode);
-  rc = smmc::host_require_v3(sim, "the stationary bootstrap supports");
-  if (rc) return rc;
-  if (st->renew_q16 > SMMC_RENEW_Q16_ONE)
-    return host_fail(SMMC_ERR_INVALID, "renew_q16 is %u: the renewal probability renew_q16 / 65536 is at most 1", st->renew_q16);
-  if (st->reserved[0] != 0 || st->reserved[1] != 0)
-    return host_fail(SMMC_ERR_INVALID, "smmc_stationary.reserved is {%u, %u}, it must be 0", st->reserved[0], st->reserved[1]);
-  return SMMC_OK;
+  const int rc = smmc::host_check_sim(e, sim);
+  return rc ? rc : smmc::stationary_check(sim, st);
 }
 
 // What a launch for these outputs asks of LDS: one plain copy of the table and the histogram, if a record is wanted.

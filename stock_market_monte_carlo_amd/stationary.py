@@ -3,13 +3,17 @@ consecutive months with probability p = renew_q16 / 65536 at every period, so th
 1 / p and no period of a path is a fixed block boundary.
 
 Functions of an Engine, not methods: they go through the engine's binding helpers exactly as Engine.simulate_blocks does
-and return what it returns.  Exactly one of mean_block_len and renew_q16 says how long the runs are."""
+and return what it returns.  Exactly one of mean_block_len and renew_q16 says how long the runs are.
+
+The same draw under a plan (smmc_engine_simulate_portfolio_cashflow_stationary): simulate_portfolio_cashflow_stationary and
+its _raw, _to_host and divide_kind forms, which go through the helpers exactly as Engine.simulate_portfolio_cashflow_blocks
+does."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .engine import SimResult, Stats, _BLOCKS_ROWS, _buffers
+from .engine import PortfolioCashflowResult, SimResult, Stats, _BLOCKS_ROWS, _PFCF_ROWS, _buffers, _records_as_bytes
 
 RENEW_Q16_ONE = _lib.RENEW_Q16_ONE
 
@@ -88,3 +92,61 @@ def stationary_divide_kind(eng, sim, mean_block_len=None, renew_q16=None):
     """DIV_FAST / DIV_EXACT / DIV_CHECKED: the divide simulate_stationary uses for this request (results never depend on it)."""
     st = make_stationary(mean_block_len, renew_q16)
     return eng._kind(eng._L.smmc_engine_stationary_divide_kind(eng._h, C.byref(sim), C.byref(st)))
+
+
+def simulate_portfolio_cashflow_stationary(eng, sim, weights, mean_block_len=None, renew_q16=None, rebalance_every=0, amount=0.0,
+                                           fraction=0.0, floor=0.0, amounts=None, fractions=None, want_final=True, want_holdings=False,
+                                           want_paid=False, want_ruin_period=False, want_stats=False, want_depleted_at=True):
+    """Engine.simulate_portfolio_cashflow on rows of set_asset_table's table chosen by the stationary bootstrap (table mode,
+    counter stream v3; include/smmc.h states the row rule): a path starts a new run where the portfolio's table stream would
+    have drawn a single row, with probability renew_q16 / 65536 at every period.  renew_q16 = 65536 is
+    simulate_portfolio_cashflow bit for bit, renew_q16 = 0 simulate_portfolio_cashflow_blocks with one block.  Returns the
+    same PortfolioCashflowResult, so survival() works as there."""
+    raw = simulate_portfolio_cashflow_stationary_raw(eng, sim, weights, mean_block_len, renew_q16, rebalance_every, amount, fraction,
+                                                     floor, amounts, fractions, want_final, want_holdings, want_paid, want_ruin_period,
+                                                     want_stats, want_depleted_at)
+    res = PortfolioCashflowResult(int(sim.n_paths), int(sim.n_periods), raw["final"], raw["paid"], raw["ruin_period"],
+                                  n_assets=raw["n_assets"], holdings=raw["holdings"])
+    return eng._read_back(res, sim, raw, _PFCF_ROWS)
+
+
+def simulate_portfolio_cashflow_stationary_raw(eng, sim, weights, mean_block_len=None, renew_q16=None, rebalance_every=0, amount=0.0,
+                                               fraction=0.0, floor=0.0, amounts=None, fractions=None, want_final=True,
+                                               want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                                               want_depleted_at=True):
+    """Enqueues the call and returns its device tensors without waiting: simulate_portfolio_cashflow_raw's dict."""
+    pf = eng.make_portfolio(weights, rebalance_every)
+    st = make_stationary(mean_block_len, renew_q16)
+    cf, keep = eng.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+    res, o = eng._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                               host=False)
+    eng._run(eng._L.smmc_engine_simulate_portfolio_cashflow_stationary, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(st), C.byref(o),
+             device=_buffers(_PFCF_ROWS, res))
+    del keep
+    return res
+
+
+def simulate_portfolio_cashflow_stationary_to_host(eng, sim, weights, mean_block_len=None, renew_q16=None, rebalance_every=0,
+                                                   amount=0.0, fraction=0.0, floor=0.0, amounts=None, fractions=None, want_final=True,
+                                                   want_holdings=False, want_paid=False, want_ruin_period=False, want_stats=False,
+                                                   want_depleted_at=True):
+    """The same through smmc_engine_simulate_portfolio_cashflow_stationary_to_host: a dict of numpy arrays (stats_raw: bytes)."""
+    pf = eng.make_portfolio(weights, rebalance_every)
+    st = make_stationary(mean_block_len, renew_q16)
+    cf, keep = eng.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)
+    res, o = eng._pfcf_outputs(sim, pf.n_assets, (want_final, want_holdings, want_paid, want_ruin_period, want_stats, want_depleted_at),
+                               host=True)
+    eng._run(eng._L.smmc_engine_simulate_portfolio_cashflow_stationary_to_host, C.byref(sim), C.byref(pf), C.byref(cf), C.byref(st),
+             C.byref(o))
+    del keep
+    return _records_as_bytes(_PFCF_ROWS, res)
+
+
+def portfolio_cashflow_stationary_divide_kind(eng, sim, weights, mean_block_len=None, renew_q16=None, rebalance_every=0, amount=0.0,
+                                              fraction=0.0, floor=0.0, amounts=None, fractions=None):
+    """_lib.DIV_FAST or DIV_EXACT: what portfolio_cashflow_divide_kind says of the same plan (results never depend on it)."""
+    pf = eng.make_portfolio(weights, rebalance_every)
+    st = make_stationary(mean_block_len, renew_q16)
+    cf, keep = eng.make_cashflow(int(sim.n_periods), amount, fraction, amounts, fractions, floor)  # keep lives until the return
+    return eng._kind(eng._L.smmc_engine_portfolio_cashflow_stationary_divide_kind(eng._h, C.byref(sim), C.byref(pf), C.byref(cf),
+                                                                                  C.byref(st)))
