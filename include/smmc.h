@@ -486,6 +486,65 @@ int smmc_engine_simulate_stationary_to_host(smmc_engine *e, const smmc_sim *sim,
  * once every 8 periods and redoes a path that ever leaves it with the IEEE divide. */
 int smmc_engine_stationary_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_stationary *st);
 
+/* ---- regime-switching Gaussian paths: a two-state Markov law for returns ------------------------- */
+
+/* SMMC_MODE_GAUSSIAN draws every period from one normal law.  Here a path carries a hidden state s_t in {0, 1} (Hamilton's
+ * two regimes: bull and bear) that persists from period to period, each regime with a mean and a deviation of its own:
+ * the Gaussian counterpart of what runs of consecutive months do for the table.  SMMC_MODE_GAUSSIAN, counter stream v3
+ * only.  sim->gauss_mean and sim->gauss_std are NOT read: the two regimes' numbers stand in `rg`.  For a path with its
+ * 64-bit global id and the 0-based period t:
+ *   z_t is EXACTLY the standard normal that smmc_engine_simulate_portfolio (below) draws in Gaussian mode for asset 0 at
+ *     period t: Philox4x32-10 block (t / 4, id lo, id hi, 1) under the key (seed lo, seed hi), draw t % 4, the v3 tables
+ *     at scale 1 and shift 0.  No new normal construction.
+ *   f_t is a 16-bit field of a SECOND Philox4x32-10 block with the same key and the counter (t / 8, id lo, id hi, 4): word
+ *     (t % 8) / 2 of its output, the low half for an even t % 8, the high half for an odd one -- the stationary bootstrap's
+ *     field with fourth counter word 4 in place of 2.  Even fourth words are field streams: 0 is the table's, 2 the
+ *     renewal's, 4 belongs to these fields alone.
+ *   state: s_0 = 1 if f_0 < start1_q16, else 0; for t >= 1, s_t = s_{t-1} ^ (f_t < leave_q16[s_{t-1}] ? 1 : 0).
+ *   multiplier: a_t = fmaf(std[s_t], z_t, fl(100.0f + mean[s_t])), ONE fused operation: the portfolio's own form for one
+ *     asset.
+ *   the step is smmc_update_fund's: total = fl(fl(total * a_t) / 100.0f).
+ * A path depends only on (seed, global path id, rg); the launch shape and the sharding are invisible.  Identities, bit for
+ * bit on the final values, the chunk means and variances and the statistics record:
+ *   1. mean[0] == mean[1] and std[0] == std[1], with any probabilities, is smmc_engine_simulate_portfolio in Gaussian mode
+ *      with n_assets = 1, weight 1, means = {mean[0]}, factor = {std[0]}, rebalance_every = 0;
+ *   2. start1_q16 = 0 and leave_q16[0] = 0 is that call with regime 0's numbers whatever regime 1 holds; start1_q16 =
+ *      65536 and leave_q16[1] = 0 is that call with regime 1's numbers;
+ *   3. the first P' periods of a P-period request are the P'-period request.
+ * The resolution of every probability is 2^-16; the mean sojourn in regime r is 65536 / leave_q16[r] periods and the
+ * chain's stationary share of regime 1 is leave_q16[0] / (leave_q16[0] + leave_q16[1]). */
+#define SMMC_REGIME_Q16_ONE 65536u /* a q16 of probability 1; the largest value accepted */
+typedef struct smmc_regimes {
+  uint32_t struct_size;  /* = sizeof(smmc_regimes) */
+  float mean[2];         /* percent per period, regime 0 and 1 */
+  float std[2];          /* percent per period, >= 0 */
+  uint32_t leave_q16[2]; /* probability of leaving regime r at a period, in units of 2^-16: 0 .. 65536 */
+  uint32_t start1_q16;   /* probability that period 0 is in regime 1: 0 .. 65536 */
+  uint32_t reserved[2];  /* 0 */
+} smmc_regimes;
+
+/* smmc_engine_simulate with these draws: the same outputs with the same meaning (DEVICE pointers, any may be NULL;
+ * d_final, d_chunk_mean, d_chunk_var 4-byte and d_stats 8-byte aligned), enqueued on the engine stream; n_periods == 0
+ * and n_paths == 0 behave as there.
+ * SMMC_ERR_INVALID with a text, before any device work: NULL rg, a wrong struct_size, a mode other than
+ * SMMC_MODE_GAUSSIAN, SMMC_FLAG_STREAM_V2 or SMMC_FLAG_STREAM_REF, a q16 above 65536, a mean or deviation that is not
+ * finite, a negative deviation, a reserved word != 0; draw tables and histogram beyond the device's LDS; the other
+ * argument errors of smmc_engine_simulate.
+ * Divide by 100: smmc_engine_regimes_divide_kind; the result does not depend on it. */
+int smmc_engine_simulate_regimes(smmc_engine *e, const smmc_sim *sim, const smmc_regimes *rg, float *d_final,
+                                 float *d_chunk_mean, float *d_chunk_var, void *d_stats);
+/* smmc_engine_simulate_to_host with these draws: HOST pointers, the same chunked pipeline, pinning rules, progress
+ * reports and merged record. */
+int smmc_engine_simulate_regimes_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_regimes *rg, float *host_final,
+                                         float *host_chunk_mean, float *host_chunk_var, volatile int64_t *progress,
+                                         smmc_stats *stats, uint64_t *hist);
+/* SMMC_DIV_FAST, SMMC_DIV_CHECKED or SMMC_DIV_EXACT: the divide a smmc_engine_simulate_regimes of (sim, rg) uses, or an
+ * error of that call's argument checks.  The rule of smmc_engine_divide_kind(e, sim, 0) on the UNION of the two regimes'
+ * multiplier bounds, each regime's as one Gaussian asset's (mean[r], std[r] rounded up): a path's multipliers are, period
+ * by period, one regime's or the other's.  No bounds for either regime is SMMC_DIV_EXACT.  The kernel tests the checked
+ * window once every 8 periods and redoes a path that ever leaves it with the IEEE divide. */
+int smmc_engine_regimes_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_regimes *rg);
+
 /* ---- portfolios: jointly drawn assets, weights, periodic rebalancing ---------------------------- */
 
 /* K = n_assets return series per path, drawn JOINTLY, held with weights w_k and rebalanced to them every R =

@@ -6,3 +6,4 @@ from .engine import (AllocationSweepResult, CashflowResult, Engine, ExcursionRes
                      reduce_mean_gpu, update_count_below_min, update_fund, update_mean_std, update_quartiles,
                      vector_add_gpu)
 from .stationary import renew_q16_of, simulate_stationary, simulate_stationary_raw, simulate_stationary_to_host, stationary_divide_kind  # noqa: F401
+from .regimes import make_regimes, regimes_divide_kind, simulate_regimes, simulate_regimes_raw, simulate_regimes_to_host  # noqa: F401

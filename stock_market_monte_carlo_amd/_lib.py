@@ -120,6 +120,21 @@ class Stationary(C.Structure):
 RENEW_Q16_ONE = 65536
 
 
+class Regimes(C.Structure):
+    """smmc_regimes"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mean", C.c_float * 2),
+        ("std", C.c_float * 2),
+        ("leave_q16", C.c_uint32 * 2),
+        ("start1_q16", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+REGIME_Q16_ONE = 65536
+
+
 class Portfolio(C.Structure):
     """smmc_portfolio"""
     _fields_ = [
@@ -280,6 +295,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Stationary), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
       C.c_void_p]),
     ("smmc_engine_stationary_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Stationary)]),
+    ("smmc_engine_simulate_regimes", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Regimes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("smmc_engine_simulate_regimes_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Regimes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+      C.c_void_p]),
+    ("smmc_engine_regimes_divide_kind", C.c_int, [C.c_void_p, C.POINTER(Sim), C.POINTER(Regimes)]),
     ("smmc_engine_set_asset_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("smmc_engine_simulate_portfolio", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioOutputs)]),

@@ -220,14 +220,13 @@ bool multiplier_bounds(const smmc_engine *e, const smmc_sim *s, double *lo_a, do
 // so the kernel tests that window once per block and redoes the rare path that leaves it with the
 // IEEE divide.  EXACT otherwise, or on request.
 constexpr double kFastDivLog2Min = -89.0;  // products stay above 2^-89: one bit above the 2^-90 the divide is used from
-int divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi) {
+// ... for multipliers known to lie in [lo_a, hi_a], lo_a > 0: the rule itself, whatever law the bounds come from.
+int divide_kind_of_bounds(const smmc_sim *s, double lo_a, double hi_a, bool allow_checked, float *chk_lo, float *chk_hi) {
   *chk_lo = 0.0f;
   *chk_hi = 0.0f;
   if (s->flags & SMMC_FLAG_EXACT_DIV) return SMMC_DIV_EXACT;
   const double cap = s->initial_capital;
   if (!(cap > 0.0) || !std::isfinite(cap)) return SMMC_DIV_EXACT;
-  double lo_a, hi_a;
-  if (!multiplier_bounds(e, s, &lo_a, &hi_a)) return SMMC_DIV_EXACT;
   const double p = static_cast<double>(s->n_periods);
   const double grow = std::max(0.0, std::log2(hi_a / 100.0)), shrink = std::max(0.0, -std::log2(lo_a / 100.0));
   const double top = std::log2(hi_a), bottom = std::min(0.0, std::log2(lo_a));
@@ -241,6 +240,13 @@ int divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, flo
   *chk_lo = static_cast<float>(std::exp2(lo_w));
   *chk_hi = static_cast<float>(std::exp2(hi_w));
   return SMMC_DIV_CHECKED;
+}
+int divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi) {
+  *chk_lo = 0.0f;
+  *chk_hi = 0.0f;
+  double lo_a, hi_a;
+  if (!multiplier_bounds(e, s, &lo_a, &hi_a)) return SMMC_DIV_EXACT;
+  return divide_kind_of_bounds(s, lo_a, hi_a, allow_checked, chk_lo, chk_hi);
 }
 
 smmc::KernelArgs make_args(const smmc_engine *e, const smmc_sim *s) {
@@ -1687,6 +1693,9 @@ int host_outputs_to_host(smmc_engine *e, const char *what, const HostPiece *piec
 }
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi) {
   return divide_kind(e, s, allow_checked, chk_lo, chk_hi);
+}
+int host_divide_kind_of_bounds(const smmc_sim *s, double lo_a, double hi_a, bool allow_checked, float *chk_lo, float *chk_hi) {
+  return divide_kind_of_bounds(s, lo_a, hi_a, allow_checked, chk_lo, chk_hi);
 }
 
 }  // namespace smmc

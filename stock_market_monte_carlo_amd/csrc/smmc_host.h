@@ -204,6 +204,9 @@ EngineView engine_view(const smmc_engine *e);
 EngineExt *engine_ext(smmc_engine *e, const void *owner);
 // smmc_engine_divide_kind's rule with the window of SMMC_DIV_CHECKED (KernelArgs::chk_lo, chk_hi)
 int host_divide_kind(const smmc_engine *e, const smmc_sim *s, bool allow_checked, float *chk_lo, float *chk_hi);
+// the same rule for multipliers that lie in [lo_a, hi_a], lo_a > 0, whatever law they come from (smmc_regimes.cpp: the
+// union of two regimes' bounds)
+int host_divide_kind_of_bounds(const smmc_sim *s, double lo_a, double hi_a, bool allow_checked, float *chk_lo, float *chk_hi);
 // smmc_engine_simulate_to_host's pipeline -- chunks, staging buffers, pinning, progress, merged record -- around
 // another enqueue: `enqueue` is called with the device current, once per chunk, with that chunk's smmc_sim and
 // device buffers (any may be null), and enqueues on the engine stream as smmc_engine_simulate does.

@@ -242,6 +242,19 @@ size_t blocks_lds_bytes(uint32_t table_len, uint32_t n_bins, bool wide);
 // threads, one partial each; one plain copy of the table in LDS.
 hipError_t launch_stationary(const KernelArgs &a, uint32_t renew_q16, int div, uint32_t grid, hipStream_t stream);
 size_t stationary_lds_bytes(uint32_t table_len, uint32_t n_bins);
+// regimes_kernel (smmc_engine_simulate_regimes, csrc/smmc_regimes.cpp; counter stream v3, Gaussian mode): the outputs of
+// launch_paths for paths whose multiplier is fma(scale[s], z, shift100[s]) in a hidden state s that leaves regime r with
+// probability leave_q16[r] / 65536 at every period ("Regime-switching Gaussian paths").  a.gauss_std = 1.0f and
+// a.gauss_shift100 = 0.0f (the staged draw yields standard normals, as launch_portfolio's); every q16 <=
+// SMMC_REGIME_Q16_ONE; `grid` workgroups of kBlock threads, one partial each.
+struct RegimeArgs {
+  float scale[2];     // std[r]
+  float shift100[2];  // 100.0f + mean[r], rounded once
+  uint32_t leave_q16[2];
+  uint32_t start1_q16;
+};
+hipError_t launch_regimes(const KernelArgs &a, const RegimeArgs &r, int div, uint32_t grid, hipStream_t stream);
+size_t regimes_lds_bytes(uint32_t n_bins);
 // portfolio_kernel (smmc_engine_simulate_portfolio, csrc/smmc_portfolio.cpp; counter stream v3 only): K jointly drawn
 // assets per path, held with weights and rebalanced every `rebalance_every` periods ("Portfolios").
 // Table mode: a.table_a is the asset table, a.table_len rows of portfolio_row_words(K) words (a = 100.0f + r, padding

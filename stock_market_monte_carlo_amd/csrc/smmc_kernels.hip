@@ -1120,7 +1120,7 @@ __device__ __forceinline__ float simulate_block_path(const KernelArgs &k, const 
 // paths_kernel's chunk walk, outputs and epilogue for a 256-thread workgroup, as a function of what is staged in front
 // of the histogram and of how a lane walks its path: `Walk` names both in static functions -- table_words(k, aux),
 // stage(k, aux, lds_table, threads per workgroup), simulate(k, aux, dr, lds_table, path) -- and `aux` is a launch
-// parameter of the walk's own (the block length).
+// parameter of the walk's own (the block length; a structure for RegimesWalk).
 //
 // The statements are paths_kernel's (without its two-halves form), and they are here a second time because
 // paths_kernel has to stay the instruction sequence its counters were taken on (profiles/pmc_traffic.json: 1047
@@ -1136,8 +1136,8 @@ __device__ __forceinline__ float simulate_block_path(const KernelArgs &k, const 
 //   only the accumulators gathered in a struct, no function at all                              reordered / reordered
 //   only the histogram flush loop                                                               reordered / reordered
 // A change to one copy belongs in the other; tests/test_blocks_gpu.py holds block length 1 to paths_kernel's bytes.
-template <typename Walk>
-__device__ __forceinline__ void blocks_body(const KernelArgs &k, const uint32_t vgrid, const uint32_t aux, unsigned char *lds_raw) {
+template <typename Walk, typename Aux = uint32_t>
+__device__ __forceinline__ void blocks_body(const KernelArgs &k, const uint32_t vgrid, const Aux aux, unsigned char *lds_raw) {
   const uint32_t table_words = Walk::table_words(k, aux);
   constexpr uint32_t kGroup = kBlock;  // threads per workgroup
   float *lds_table = reinterpret_cast<float *>(lds_raw);  // returns table, or the Box-Muller tables
@@ -1395,6 +1395,98 @@ __global__ __launch_bounds__(kBlock)
 void stationary_kernel(const KernelArgs k, const uint32_t vgrid, const uint32_t renew_q16) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   blocks_body<StationaryWalk<kDiv, kDense>>(k, vgrid, renew_q16, lds_raw);
+}
+
+// ---- regime-switching Gaussian paths: a two-state Markov law for returns ---------------------------
+//
+// smmc_engine_simulate_regimes (csrc/smmc_regimes.cpp; include/smmc.h and DESIGN.md, "Regime-switching Gaussian paths",
+// state the contract).  Every period t of a path has a standard normal z_t -- exactly the one portfolio_kernel draws for
+// asset 0, Philox block (t / 4, id lo, id hi, 1) over the v3 tables staged at scale 1 with dr.shift100 = 0 -- and a
+// 16-bit field f_t out of a second Philox block (t / 8, id lo, id hi, kRegimeTag), taken by renewal_field.  The path's
+// regime flips when f_t < leave_q16[regime before] (period 0: regime 1 when f_0 < start1_q16), and the multiplier is
+// fma(std[s_t], z_t, 100 + mean[s_t]).  Every lane has a state of its own, both counters are wave-uniform, the scalar
+// first rounds of philox4x32_10<kPhiloxUniformBlock> hold for all three blocks of a segment, and the loop has no
+// divergent branch: the state is a lane mask, scale and shift are selects of kernel arguments.
+constexpr uint32_t kRegimeTag = 4u;  // fourth counter word of the regime fields: even tags are field streams (0 the table's, 2 the renewal's)
+constexpr int kRegimeSeg = 8;        // periods per block of fields, as kRenewSeg: two blocks of normals
+
+// Periods 8 g .. 8 g + n - 1 of a path, n = 8 (kFull) or the path's last 1 .. 7 (wave-uniform).  The eight states are
+// formed first, so the field words are dead when the compounding chain begins (as stationary_rows forms its rows).
+template <bool kExactDiv, bool kFull>
+__device__ __forceinline__ void regimes_segment(const KernelArgs &k, const RegimeArgs &r, const DrawRegs &dr, const float *lds,
+                                                uint32_t path_lo, uint32_t path_hi, uint32_t g, uint32_t n, bool &state, float &total) {
+  uint32_t f[4];
+  philox4x32_10<kPhiloxUniformBlock>(g, path_lo, path_hi, kRegimeTag, k.key0, k.key1, dr, f);
+  // period 0 comes from "regime 0" (the state's initial value) with start1_q16 in leave_q16[0]'s place: a scalar select
+  const uint32_t q0 = g == 0u ? r.start1_q16 : r.leave_q16[0];
+  bool s[kRegimeSeg];
+#pragma unroll
+  for (int j = 0; j < kRegimeSeg; ++j) {
+    s[j] = false;
+    if (kFull || static_cast<uint32_t>(j) < n) {
+      const uint32_t q = state ? r.leave_q16[1] : (j == 0 ? q0 : r.leave_q16[0]);
+      state = state != (renewal_field(f, j) < q);
+      s[j] = state;
+    }
+  }
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    if (half == 0 || kFull || n > 4u) {  // the second block of normals only if the segment has more than four periods
+      float z[4];  // standard normals: the tables are staged at scale 1, dr.shift100 is 0
+      block_multipliers<SMMC_MODE_GAUSSIAN, false, kPhiloxUniformBlock>(k, dr, lds, path_lo, path_hi, 2u * g + half, z);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 4 * half + i;
+        if (kFull || static_cast<uint32_t>(j) < n) {
+          const float scale = s[j] ? r.scale[1] : r.scale[0], shift = s[j] ? r.shift100[1] : r.shift100[0];
+          total = compound<kExactDiv>(total, __builtin_fmaf(scale, z[i], shift));
+        }
+      }
+    }
+  }
+}
+
+template <int kDiv>
+__device__ __forceinline__ float simulate_regimes_path(const KernelArgs &k, const RegimeArgs &r, const DrawRegs &dr, const float *lds,
+                                                       uint64_t path) {
+  constexpr bool kExactDiv = kDiv == kDivExact;
+  const uint32_t path_lo = static_cast<uint32_t>(path);
+  const uint32_t path_hi = static_cast<uint32_t>(path >> 32);
+  float total = k.initial_capital;
+  bool left_window = false;
+  bool state = false;
+  const uint32_t full = k.n_periods / kRegimeSeg;  // < 2^28: 2 g + 1 is a block index
+  for (uint32_t g = 0; g < full; ++g) {
+    regimes_segment<kExactDiv, true>(k, r, dr, lds, path_lo, path_hi, g, kRegimeSeg, state, total);
+    // one test per 8 periods, the span the host derives the window for (smmc_capi.cpp, divide_kind)
+    if constexpr (kDiv == kDivChecked) left_window |= !(total > k.chk_lo && total < k.chk_hi);  // NaN leaves too
+  }
+  const uint32_t rem = k.n_periods - full * kRegimeSeg;
+  if (rem) regimes_segment<kExactDiv, false>(k, r, dr, lds, path_lo, path_hi, full, rem, state, total);  // wave-uniform
+  if constexpr (kDiv == kDivChecked) {
+    if (left_window) total = simulate_regimes_path<kDivExact>(k, r, dr, lds, path);
+  }
+  return total;
+}
+
+template <int kDiv>
+struct RegimesWalk {  // aux: the two regimes' scales, shifts and probabilities
+  static __device__ __forceinline__ uint32_t table_words(const KernelArgs &, const RegimeArgs &) { return bm_lds_words(SMMC_MODE_GAUSSIAN); }
+  static __device__ __forceinline__ void stage(const KernelArgs &k, const RegimeArgs &, float *lds_table, uint32_t threads) {
+    stage_tables<SMMC_MODE_GAUSSIAN>(k, lds_table, threads);  // k.gauss_std is 1.0f: the tables as they are
+  }
+  static __device__ __forceinline__ float simulate(const KernelArgs &k, const RegimeArgs &r, const DrawRegs &dr, const float *lds_table,
+                                                   uint64_t path) {
+    return simulate_regimes_path<kDiv>(k, r, dr, lds_table, path);
+  }
+};
+// The regime walk inside blocks_body: its chunk walk, outputs and epilogue as they are.  A family of its own; no
+// amdgpu_waves_per_eu: nothing measured asks for one.
+template <int kDiv>
+__global__ __launch_bounds__(kBlock)
+void regimes_kernel(const KernelArgs k, const uint32_t vgrid, const RegimeArgs r) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  blocks_body<RegimesWalk<kDiv>, RegimeArgs>(k, vgrid, r, lds_raw);
 }
 
 // ---- the wave walk: the skeleton of checkpoints_kernel, cashflow_kernel and excursions_kernel ------
@@ -4322,6 +4414,34 @@ hipError_t launch_stationary(const KernelArgs &a, uint32_t renew_q16, int div, u
   const size_t lds = stationary_lds_bytes(a.table_len, a.partials ? a.n_bins : 0u);
   return table_is_dense(a.table_len) ? launch_stationary_layout<true>(a, renew_q16, div, grid, lds, stream)
                                      : launch_stationary_layout<false>(a, renew_q16, div, grid, lds, stream);
+}
+
+// ---- regime-switching Gaussian paths ----
+
+size_t regimes_lds_bytes(uint32_t n_bins) {
+  // paths_lds_bytes in Gaussian mode, one 256-thread workgroup: the v3 draw tables in front of the histogram
+  const size_t words = (static_cast<size_t>(bm_lds_words(SMMC_MODE_GAUSSIAN)) + n_bins + 1u) & ~static_cast<size_t>(1);
+  return words * 4u + 4u * kWaves * sizeof(double) + kWaves * sizeof(BlockPartial);
+}
+
+template <int kDiv>
+static hipError_t launch_regimes_variant(const KernelArgs &a, const RegimeArgs &r, uint32_t grid, size_t lds, hipStream_t stream) {
+  hipError_t err = allow_lds(regimes_kernel<kDiv>, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL((regimes_kernel<kDiv>), dim3(grid), dim3(kBlock), lds, stream, a, grid, r);
+  return hipGetLastError();
+}
+
+hipError_t launch_regimes(const KernelArgs &a, const RegimeArgs &r, int div, uint32_t grid, hipStream_t stream) {
+  if (a.mode != SMMC_MODE_GAUSSIAN || a.stream != 3 || a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f) return hipErrorInvalidValue;
+  if (r.leave_q16[0] > SMMC_REGIME_Q16_ONE || r.leave_q16[1] > SMMC_REGIME_Q16_ONE || r.start1_q16 > SMMC_REGIME_Q16_ONE)
+    return hipErrorInvalidValue;
+  const size_t lds = regimes_lds_bytes(a.partials ? a.n_bins : 0u);
+  switch (div) {
+    case SMMC_DIV_FAST: return launch_regimes_variant<kDivFast>(a, r, grid, lds, stream);
+    case SMMC_DIV_CHECKED: return launch_regimes_variant<kDivChecked>(a, r, grid, lds, stream);
+    default: return launch_regimes_variant<kDivExact>(a, r, grid, lds, stream);
+  }
 }
 
 // ---- excursions ----
