@@ -793,6 +793,69 @@ int smmc_engine_simulate_portfolio_cashflow_stationary_to_host(smmc_engine *e, c
 int smmc_engine_portfolio_cashflow_stationary_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
                                                           const smmc_cashflow *cf, const smmc_stationary *st);
 
+/* ---- regime-switching plans: portfolio cash flows under a two-state law ---------------------------- */
+
+/* smmc_engine_simulate_portfolio_cashflow in Gaussian mode with the hidden state of smmc_engine_simulate_regimes: every
+ * regime has a joint law of its own for the K assets (bear markets persist, and correlations rise in them), and a month's
+ * multipliers are those of the regime the path is in.  The composition of those two contracts; neither is restated here.
+ * Scope: SMMC_MODE_GAUSSIAN and counter stream v3 only; sim->gauss_mean and sim->gauss_std are NOT read.  pf gives
+ * n_assets, weights and rebalance_every; pf->means and pf->factor must be all zero, the laws stand in `rg`.  For a path
+ * with its 64-bit global id and the 0-based period t:
+ *   normals: z_k(t) are EXACTLY the standard normals smmc_engine_simulate_portfolio draws in Gaussian mode: Philox block
+ *     (t / 4, id lo, id hi, 1 + 2 k), draw t % 4, the v3 tables at scale 1 and shift 0.  No new normal construction.
+ *   state: s_t is EXACTLY the state of smmc_engine_simulate_regimes for the same (leave_q16, start1_q16): field f_t of the
+ *     block (t / 8, id lo, id hi, 4), s_0 = f_0 < start1_q16, s_t = s_{t-1} ^ (f_t < leave_q16[s_{t-1}]).  No new random
+ *     numbers: a plan and a one-asset regime run with the same seed and ids see the same bull and bear months.
+ *   multiplier: a_k(t) is smmc_portfolio's chain of fused multiply-adds over row k of L_{s_t} = factor[s_t], from j = 0
+ *     upwards, starting at fl(100.0f + means[s_t][k]).
+ *   step: everything after the multipliers is smmc_engine_simulate_portfolio_cashflow's, word for word (0-based period t
+ *     is that call's period t + 1) -- the holdings, the left-to-right value, the flow settling at the target weights, the
+ *     rebalance at t mod R == 0 && t != P, depletion, the lane mask of a depleted path, the six outputs and the exact
+ *     counts, byte-identical repeat calls, shards merged by smmc_stats_merge and by adding d_depleted_at, n_paths == 0.
+ *     A depleted path's draws are still consumed, and its state still moves.
+ * A path depends only on (seed, global path id, rg, weights, R, schedule, floor).  Identities, bit for bit on d_final,
+ * d_holdings, d_paid, d_ruin_period and d_depleted_at, and on the record's integer fields, min, max and buckets (sum and
+ * sumsq follow the launch shape, which is the parent's: the grid rule is the same):
+ *   1. means[0] == means[1] and factor[0] == factor[1], with any probabilities, is
+ *      smmc_engine_simulate_portfolio_cashflow in Gaussian mode with those means and that factor;
+ *   2. start1_q16 = 0 and leave_q16[0] = 0 is that call with regime 0's law whatever regime 1 holds; start1_q16 = 65536
+ *      and leave_q16[1] = 0 is that call with regime 1's law;
+ *   3. K = 1, w_0 = 1, zero flows and floor 0 give the final values of smmc_engine_simulate_regimes with mean[r] =
+ *      means[r][0] and std[r] = factor[r][0], for any R, while every value stays finite and above 0;
+ *   4. for P' < P, d_ruin_period restricted to values <= P' and d_depleted_at[1 .. P'] of the P-period run equal those of
+ *      the P'-period run of the same schedule prefix. */
+typedef struct smmc_portfolio_regimes {
+  uint32_t struct_size;                               /* = sizeof(smmc_portfolio_regimes) = 184 */
+  uint32_t leave_q16[2];                              /* as smmc_regimes */
+  uint32_t start1_q16;                                /* as smmc_regimes */
+  float means[2][SMMC_MAX_ASSETS];                    /* regime r, asset k: percent per period; 0 at k >= K */
+  float factor[2][SMMC_MAX_ASSETS * SMMC_MAX_ASSETS]; /* regime r: lower-triangular L_r, laid out as smmc_portfolio.factor */
+  uint32_t reserved[2];                               /* 0 */
+} smmc_portfolio_regimes;
+
+/* out holds DEVICE pointers as in the parent; asynchronous on the engine stream.
+ * SMMC_ERR_INVALID with a text, before any device work: a mode other than SMMC_MODE_GAUSSIAN; SMMC_FLAG_STREAM_V2 or
+ * SMMC_FLAG_STREAM_REF; everything smmc_engine_simulate_portfolio_cashflow refuses of sim, pf, cf and out; a non-zero
+ * pf->means or pf->factor entry; NULL rg or a wrong struct_size; a q16 above 65536; in either regime a mean or factor
+ * entry that is not finite, a non-zero entry above the diagonal or at k >= K, a negative diagonal; a reserved word != 0;
+ * draw tables, depletion counters and histogram beyond the device's LDS less 2048 bytes. */
+int smmc_engine_simulate_portfolio_cashflow_regimes(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                    const smmc_portfolio_regimes *rg, const smmc_cashflow *cf,
+                                                    const smmc_portfolio_cashflow_outputs *out);
+/* Synchronous convenience: the same with HOST pointers in out. */
+int smmc_engine_simulate_portfolio_cashflow_regimes_to_host(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                            const smmc_portfolio_regimes *rg, const smmc_cashflow *cf,
+                                                            const smmc_portfolio_cashflow_outputs *out);
+/* SMMC_DIV_FAST or SMMC_DIV_EXACT (never SMMC_DIV_CHECKED, as the parent), or an error of the call's argument checks.
+ * The rule of smmc_engine_portfolio_cashflow_divide_kind on the UNION of the two regimes' per-asset bounds: per asset, the
+ * smaller of the two lower bounds and the larger of the two upper ones, each regime's as a portfolio with that regime's
+ * means and factor has them.  Every multiplier of a path is one regime's or the other's, and every condition of the rule
+ * is monotone in the bounds.  "FAST in each regime separately" is no proof: the rule's two sufficient conditions could
+ * then hold in different regimes, and a path mixes them.  No bounds for a regime is SMMC_DIV_EXACT, also for a regime that
+ * is never entered.  Results never depend on the form. */
+int smmc_engine_portfolio_cashflow_regimes_divide_kind(smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf,
+                                                       const smmc_portfolio_regimes *rg, const smmc_cashflow *cf);
+
 /* ---- portfolio cash-flow checkpoints: the value distribution along a plan ----------------------- */
 
 /* "What does my wealth look like in year 5, 10, 15 ... under this plan": smmc_engine_simulate_portfolio_cashflow with

@@ -7,3 +7,5 @@ from .engine import (AllocationSweepResult, CashflowResult, Engine, ExcursionRes
                      vector_add_gpu)
 from .stationary import renew_q16_of, simulate_stationary, simulate_stationary_raw, simulate_stationary_to_host, stationary_divide_kind  # noqa: F401
 from .regimes import make_regimes, regimes_divide_kind, simulate_regimes, simulate_regimes_raw, simulate_regimes_to_host  # noqa: F401
+from .regimes import (make_portfolio_regimes, portfolio_cashflow_regimes_divide_kind, simulate_portfolio_cashflow_regimes,  # noqa: F401
+                      simulate_portfolio_cashflow_regimes_raw, simulate_portfolio_cashflow_regimes_to_host)

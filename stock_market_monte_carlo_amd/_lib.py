@@ -135,6 +135,18 @@ class Regimes(C.Structure):
 REGIME_Q16_ONE = 65536
 
 
+class PortfolioRegimes(C.Structure):
+    """smmc_portfolio_regimes"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("leave_q16", C.c_uint32 * 2),
+        ("start1_q16", C.c_uint32),
+        ("means", (C.c_float * 4) * 2),
+        ("factor", (C.c_float * 16) * 2),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class Portfolio(C.Structure):
     """smmc_portfolio"""
     _fields_ = [
@@ -325,6 +337,12 @@ SYMBOLS = [
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Stationary), C.POINTER(PortfolioCashflowOutputs)]),
     ("smmc_engine_portfolio_cashflow_stationary_divide_kind", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.POINTER(Stationary)]),
+    ("smmc_engine_simulate_portfolio_cashflow_regimes", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioRegimes), C.POINTER(Cashflow), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_simulate_portfolio_cashflow_regimes_to_host", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioRegimes), C.POINTER(Cashflow), C.POINTER(PortfolioCashflowOutputs)]),
+    ("smmc_engine_portfolio_cashflow_regimes_divide_kind", C.c_int,
+     [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(PortfolioRegimes), C.POINTER(Cashflow)]),
     ("smmc_engine_simulate_portfolio_cashflow_checkpoints", C.c_int,
      [C.c_void_p, C.POINTER(Sim), C.POINTER(Portfolio), C.POINTER(Cashflow), C.c_void_p, C.c_uint32,
       C.POINTER(PortfolioCashflowOutputs), C.c_void_p]),

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libsmmc_hip.so")
 
-SOURCES = ["smmc_kernels.hip", "smmc_ref_kernels.hip", "smmc_stats_kernels.hip", "smmc_vector_add.hip", "smmc_capi.cpp", "smmc_cashflow.cpp", "smmc_sweep.cpp", "smmc_excursions.cpp", "smmc_blocks.cpp", "smmc_stationary.cpp", "smmc_regimes.cpp", "smmc_portfolio.cpp", "smmc_portfolio_cashflow.cpp", "smmc_portfolio_cashflow_blocks.cpp", "smmc_portfolio_cashflow_stationary.cpp", "smmc_portfolio_cashflow_checkpoints.cpp", "smmc_real_cashflow.cpp", "smmc_guardrails.cpp", "smmc_glide.cpp", "smmc_allocation_sweep.cpp", "smmc_group.cpp", "smmc_dropin.cpp"]
+SOURCES = ["smmc_kernels.hip", "smmc_ref_kernels.hip", "smmc_stats_kernels.hip", "smmc_vector_add.hip", "smmc_capi.cpp", "smmc_cashflow.cpp", "smmc_sweep.cpp", "smmc_excursions.cpp", "smmc_blocks.cpp", "smmc_stationary.cpp", "smmc_regimes.cpp", "smmc_portfolio.cpp", "smmc_portfolio_cashflow.cpp", "smmc_portfolio_cashflow_blocks.cpp", "smmc_portfolio_cashflow_stationary.cpp", "smmc_portfolio_cashflow_regimes.cpp", "smmc_portfolio_cashflow_checkpoints.cpp", "smmc_real_cashflow.cpp", "smmc_guardrails.cpp", "smmc_glide.cpp", "smmc_allocation_sweep.cpp", "smmc_group.cpp", "smmc_dropin.cpp"]
 HEADERS = [os.path.join(CSRC, "smmc_internal.h"), os.path.join(CSRC, "smmc_device.h"), os.path.join(CSRC, "smmc_host.h"),
            os.path.join(CSRC, "smmc_bm_tables.inc"),
            os.path.join(CSRC, "smmc_synthetic_table.inc"), os.path.join(ROOT, "include", "smmc.h"),

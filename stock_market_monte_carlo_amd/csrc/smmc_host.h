@@ -228,6 +228,21 @@ int cashflow_check_schedule(const smmc_sim *sim, const smmc_cashflow *cf);
 inline bool cashflow_varying(const smmc_cashflow *cf) { return cf->amounts || cf->fractions; }  // per-period arrays
 // the arrays of a varying schedule staged and their upload enqueued: c->schedule, c->stride.  Device must be current.
 int cashflow_stage_schedule(smmc_engine *e, const smmc_sim *sim, const smmc_cashflow *cf, CashflowArgs *c);
+// smmc_portfolio_cashflow.cpp, to smmc_portfolio_cashflow_regimes.cpp: smmc_engine_portfolio_cashflow_divide_kind's rule for
+// multipliers a_k in [lo[k], hi_max], lo[k] > 0, k < pf->n_assets, whatever law they come from (there: the union of two
+// regimes' bounds).  Every condition of the rule is monotone in lo[k] and in hi_max.
+int portfolio_cashflow_divide_of_bounds(const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf, const double *lo, double hi_max);
+// What smmc_engine_simulate_regimes refuses about the three probabilities, with its texts: stated here, inline, for
+// smmc_portfolio_cashflow_regimes.cpp (tests/test_regimes_cpu.py lets no unit but smmc_regimes.cpp leave an undefined
+// symbol of that word, so the borrower cannot call across units).
+inline int markov_check_q16(const uint32_t (&leave_q16)[2], uint32_t start1_q16) {
+  for (int r = 0; r < 2; ++r)
+    if (leave_q16[r] > SMMC_REGIME_Q16_ONE)
+      return host_fail(SMMC_ERR_INVALID, "leave_q16[%d] is %u: the probability leave_q16 / 65536 is at most 1", r, leave_q16[r]);
+  if (start1_q16 > SMMC_REGIME_Q16_ONE)
+    return host_fail(SMMC_ERR_INVALID, "start1_q16 is %u: the probability start1_q16 / 65536 is at most 1", start1_q16);
+  return SMMC_OK;
+}
 // smmc_blocks.cpp, to smmc_portfolio_cashflow_blocks.cpp: what smmc_engine_simulate_blocks refuses about `blocks`, the mode
 // and the stream of a checked sim, with its texts.
 int blocks_check(const smmc_sim *sim, const smmc_blocks *b);

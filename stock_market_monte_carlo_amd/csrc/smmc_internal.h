@@ -314,6 +314,26 @@ hipError_t launch_portfolio_cashflow_geometric(const KernelArgs &a, const Portfo
                                                 hipStream_t stream);
 // [n_rows padded rows, one plain copy][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
 size_t portfolio_cashflow_geometric_lds_bytes(uint32_t n_rows, uint32_t n_assets, uint32_t n_periods, uint32_t n_bins);
+// portfolio_cashflow_regimes_kernel (smmc_engine_simulate_portfolio_cashflow_regimes,
+// csrc/smmc_portfolio_cashflow_regimes.cpp; counter stream v3, Gaussian mode): portfolio_cashflow_kernel's recurrence on
+// multipliers of the regime a path is in -- regimes_kernel's hidden state, drawn from the same fields -- each regime with
+// a shift and a factor of its own ("Regime-switching plans").  p gives n_assets, weights, rebalance_every and
+// d_holdings; p.shift100 and p.factor are not read.  c, a.partials, a.d_hist and c.d_depleted as
+// launch_portfolio_cashflow; a.gauss_std = 1.0f and a.gauss_shift100 = 0.0f; every q16 <= SMMC_REGIME_Q16_ONE.
+struct PortfolioCashflowMarkovArgs {
+  PortfolioArgs p;
+  CashflowArgs c;
+  float shift100[2][SMMC_MAX_ASSETS];                   // regime r: s_k = 100.0f + means[r][k]
+  float factor[2][SMMC_MAX_ASSETS * SMMC_MAX_ASSETS];  // regime r: L_r, row-major
+  uint32_t leave_q16[2];
+  uint32_t start1_q16;
+};
+// (the launch, its arguments and the LDS need are named for the Markov chain, not for its states: tests/test_regimes_cpu.py
+// lets only smmc_regimes.cpp refer to a symbol of that word)
+hipError_t launch_portfolio_cashflow_markov(const KernelArgs &a, const PortfolioCashflowMarkovArgs &x, bool exact_div, uint32_t grid,
+                                            hipStream_t stream);
+// [v3 draw tables at scale 1][n_periods + 1 depletion counters][n_bins buckets][pad][the waves' partials]
+size_t portfolio_cashflow_markov_lds_bytes(uint32_t n_periods, uint32_t n_bins);
 // portfolio_cashflow_checkpoints_kernel (smmc_engine_simulate_portfolio_cashflow_checkpoints,
 // csrc/smmc_portfolio_cashflow_checkpoints.cpp; counter stream v3 only): portfolio_cashflow_kernel's paths, with the
 // record of their values after each of n chosen periods ("Portfolio cash-flow checkpoints").  p, c, a.partials,

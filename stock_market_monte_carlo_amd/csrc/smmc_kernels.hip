@@ -3281,6 +3281,150 @@ void portfolio_cashflow_stationary_kernel(const KernelArgs k, const PortfolioCas
   if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
 }
 
+// ---- regime-switching plans: portfolio cash flows under a two-state law ------------------------------
+//
+// smmc_engine_simulate_portfolio_cashflow_regimes (csrc/smmc_portfolio_cashflow_regimes.cpp; include/smmc.h and
+// DESIGN.md, "Regime-switching plans", state the contract): portfolio_cashflow_kernel's Gaussian path -- the same K
+// chains of standard normals, the same portfolio_cashflow_step, called, not restated -- with the multipliers of the regime
+// the path is in this period, and regimes_kernel's state: the same fields (kRegimeTag, kRegimeSeg, renewal_field), the
+// same update.  Gaussian mode only; a family of its own: portfolio_cashflow_kernel and regimes_kernel compile to what
+// they compiled to before.
+//
+// Fields.  One block of fields serves kRegimeSeg = 8 periods, two draw blocks: walk_blocks' block index is wave-uniform,
+// so "even block" is a scalar test.  markov_states draws the field block there and forms all eight states at once -- also
+// those of periods past the last, which nothing reads --, so the four field words are dead before the K normal chains
+// start; the states live on as lane masks, the second draw block of the segment moves its four to the front.
+//
+// Multipliers.  Per period and asset, s_k and the row of L are selects of kernel arguments on the lane's state, then the
+// parent's chain of fused multiply-adds: K + K (K + 1) / 2 selects per period on top of the parent's.  Forming both
+// regimes' multipliers and selecting K of them would double the half-rate FMAs for the full-rate selects saved.
+//
+// Control flow is wave-uniform: the state is data, the rebalance the scalar countdown.  LDS: the parent's Gaussian
+// layout (portfolio_cashflow_markov_lds_bytes).
+//
+// The states of periods 8 g .. 8 g + 7 of a path; `state`: that of the period before, left at that of the segment's last.
+__device__ __forceinline__ void markov_states(const KernelArgs &k, const PortfolioCashflowMarkovArgs &x, const DrawRegs &dr,
+                                              uint32_t path_lo, uint32_t path_hi, uint32_t g, bool &state, bool (&s)[kRegimeSeg]) {
+  uint32_t f[4];
+  philox4x32_10<kPhiloxUniformBlock>(g, path_lo, path_hi, kRegimeTag, k.key0, k.key1, dr, f);
+  // period 0 comes from "regime 0" (the state's initial value) with start1_q16 in leave_q16[0]'s place: a scalar select
+  const uint32_t q0 = g == 0u ? x.start1_q16 : x.leave_q16[0];
+#pragma unroll
+  for (int j = 0; j < kRegimeSeg; ++j) {
+    const uint32_t q = state ? x.leave_q16[1] : (j == 0 ? q0 : x.leave_q16[0]);
+    state = state != (renewal_field(f, j) < q);
+    s[j] = state;
+  }
+}
+
+// The multipliers a[j][i] of asset i at draw j of Philox block `blk` (wave-uniform) of a path whose state at draw j is s[j]:
+// portfolio_multipliers' normals, the chain over the row of the state's factor from the state's shift.
+template <int K>
+__device__ __forceinline__ void markov_multipliers(const KernelArgs &k, const PortfolioCashflowMarkovArgs &x, const DrawRegs &dr,
+                                                   const float *lds_table, uint32_t path_lo, uint32_t path_hi, uint32_t blk,
+                                                   const bool (&s)[kRegimeSeg], float (&a)[4][K]) {
+  uint32_t u[K][4];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    u[i][0] = blk;
+    u[i][1] = path_lo;
+    u[i][2] = path_hi;
+    u[i][3] = 1u + 2u * static_cast<uint32_t>(i);
+  }
+  philox4x32_10_multi<K, true>(u, k.key0, k.key1, dr);
+  float z[K][4];  // standard normals: the tables are staged at scale 1, dr.shift100 is 0
+  multipliers_of_words_multi<SMMC_MODE_GAUSSIAN, false, K>(k, dr, lds_table, u, z);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      float acc = s[j] ? x.shift100[1][i] : x.shift100[0][i];
+#pragma unroll
+      for (int m = 0; m <= i; ++m) {
+        const float l = s[j] ? x.factor[1][i * SMMC_MAX_ASSETS + m] : x.factor[0][i * SMMC_MAX_ASSETS + m];
+        acc = __builtin_fmaf(l, z[m][j], acc);
+      }
+      a[j][i] = acc;
+    }
+}
+
+// No amdgpu_waves_per_eu: nothing measured asks for one.
+template <bool kExactDiv, int K, bool kVarying>
+__global__ __launch_bounds__(64 * walk_waves(SMMC_MODE_GAUSSIAN))
+void portfolio_cashflow_regimes_kernel(const KernelArgs k, const PortfolioCashflowMarkovArgs x) {
+  constexpr int kMode = SMMC_MODE_GAUSSIAN;
+  constexpr uint32_t kW = walk_waves(kMode);
+  constexpr uint32_t kGroup = 64u * kW;
+  constexpr int kDraws = 4;
+  static_assert(kRegimeSeg == 2 * kDraws, "a block of fields serves two blocks of normals");
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const PortfolioArgs &p = x.p;
+  const CashflowArgs &c = x.c;
+  const WalkLds s = walk_setup<kMode>(k, lds_raw, walk_table_words<kMode>(k), k.n_periods + 1u + k.n_bins);
+  uint32_t *lds_dep = s.counters;                     // [n_periods + 1]
+  uint32_t *lds_hist = lds_dep + (k.n_periods + 1u);  // [n_bins]
+
+  const bool want_stats = k.partials != nullptr;  // all uniform
+  const bool want_hist = want_stats && k.n_bins != 0;
+  const bool want_dep = c.d_depleted != nullptr;
+  LaneRecord rec;
+  const DrawRegs dr = make_draw_regs(k);
+  const uint32_t every = p.rebalance_every;
+  const const_float_ptr amounts = (const_float_ptr)(c.schedule);
+  const const_float_ptr fractions = amounts + c.stride;
+
+  wave_chunks<kMode>(k, s, [&](uint64_t i, bool active, uint32_t path_lo, uint32_t path_hi) {
+    float h[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) h[a] = __fmul_rn(k.initial_capital, p.weights[a]);
+    float v = 0.0f, paid = 0.0f;  // v: set by the first period (n_periods >= 1)
+    uint32_t ruin = 0u;
+    bool alive = true;
+    uint32_t until = every;  // periods until the next rebalance; with every == 0 the countdown never ends
+    bool state = false;      // the regime of the period before; period 0 takes start1_q16
+    bool st[kRegimeSeg];     // the states of this draw block's periods in st[0 .. 3]
+    float a[kDraws][K];
+    float am[kDraws], fr[kDraws];
+    walk_blocks<kDraws>(
+        k.n_periods,
+        [&](uint32_t blk) {
+#pragma unroll
+          for (int j = 0; j < kDraws; ++j) {  // the block's schedule entries (padded to whole blocks)
+            am[j] = kVarying ? amounts[blk * kDraws + j] : c.amount;
+            fr[j] = kVarying ? fractions[blk * kDraws + j] : c.fraction;
+          }
+          if ((blk & 1u) == 0u) {  // wave-uniform: the segment's first draw block
+            markov_states(k, x, dr, path_lo, path_hi, blk >> 1, state, st);
+          } else {
+#pragma unroll
+            for (int j = 0; j < kDraws; ++j) st[j] = st[kDraws + j];
+          }
+          markov_multipliers<K>(k, x, dr, s.table, path_lo, path_hi, blk, st, a);
+        },
+        [&](int j, uint32_t t) {
+          portfolio_cashflow_step<kExactDiv, K>(a[j], p.weights, am[j], fr[j], c.floor, every, k.n_periods, t, h, v, paid, ruin, alive,
+                                                until);
+        });
+    if (active) {
+      if (k.d_final) k.d_final[i] = v;
+      if (p.d_holdings) {
+#pragma unroll
+        for (int y = 0; y < K; ++y) p.d_holdings[static_cast<uint64_t>(y) * k.n_paths + i] = h[y];
+      }
+      if (c.d_paid) c.d_paid[i] = paid;
+      if (c.d_ruin_period) c.d_ruin_period[i] = ruin;
+      if (want_dep) atomicAdd(&lds_dep[ruin], 1u);  // ruin <= n_periods
+    }
+    if (want_stats && active) rec.add(k, v, want_hist, lds_hist);
+  });
+
+  if (want_stats) rec.store(s);
+  __syncthreads();  // the waves' partials are written and their LDS adds complete
+  if (want_stats && threadIdx.x == 0) fold_wave_partials<kW>(s.wave_part, &k.partials[blockIdx.x]);
+  if (want_dep) flush_counters<kGroup>(lds_dep, k.n_periods + 1u, c.d_depleted);
+  if (want_hist) flush_counters<kGroup>(lds_hist, k.n_bins, k.d_hist);
+}
+
 // ---- portfolio cash-flow checkpoints: the plan's value distribution at chosen periods ---------------
 //
 // smmc_engine_simulate_portfolio_cashflow_checkpoints (csrc/smmc_portfolio_cashflow_checkpoints.cpp; include/smmc.h and
@@ -3968,6 +4112,14 @@ hipError_t static_lds_bytes(size_t *bytes) {
       SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(2, true),
       SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS(4, true),
 #undef SMMC_PORTFOLIO_CASHFLOW_STATIONARY_KERNELS
+#define SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(K, V) /* Gaussian mode only */                                              \
+  reinterpret_cast<const void *>(portfolio_cashflow_regimes_kernel<false, K, V>),                                            \
+      reinterpret_cast<const void *>(portfolio_cashflow_regimes_kernel<true, K, V>)
+      SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(1, false), SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(2, false),
+      SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(3, false), SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(4, false),
+      SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(1, true), SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(2, true),
+      SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(3, true), SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS(4, true),
+#undef SMMC_PORTFOLIO_CASHFLOW_REGIMES_KERNELS
 #define SMMC_PORTFOLIO_CASHFLOW_CHECKPOINTS_KERNELS(K, V)                                                                  \
   reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, false, false, K, V>),             \
       reinterpret_cast<const void *>(portfolio_cashflow_checkpoints_kernel<SMMC_MODE_GAUSSIAN, true, false, K, V>),          \
@@ -4598,6 +4750,45 @@ hipError_t launch_portfolio_cashflow_geometric(const KernelArgs &a, const Portfo
   const hipError_t err = allow_lds(kernel, lds);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(SMMC_MODE_TABLE)), lds, stream, a, x);
+  return hipGetLastError();
+}
+
+// ---- regime-switching plans ----
+
+size_t portfolio_cashflow_markov_lds_bytes(uint32_t n_periods, uint32_t n_bins) {
+  // the parent's Gaussian layout: the v3 draw tables; counters: depletion [n_periods + 1], histogram [n_bins]; one partial per wave
+  return wave_walk_lds_bytes(SMMC_MODE_GAUSSIAN, 0u, static_cast<size_t>(n_periods) + 1u + n_bins, 1u);
+}
+
+struct PortfolioCashflowMarkovFamily {  // Gaussian mode only: its own ladder, exact | fast divide
+  template <bool kExactDiv, int K>
+  static WalkKernel<PortfolioCashflowMarkovArgs> schedule(const PortfolioCashflowMarkovArgs &x) {
+    return x.c.schedule ? portfolio_cashflow_regimes_kernel<kExactDiv, K, true> : portfolio_cashflow_regimes_kernel<kExactDiv, K, false>;
+  }
+  template <bool kExactDiv>
+  static WalkKernel<PortfolioCashflowMarkovArgs> get(const PortfolioCashflowMarkovArgs &x) {
+    switch (x.p.n_assets) {
+      case 1: return schedule<kExactDiv, 1>(x);
+      case 2: return schedule<kExactDiv, 2>(x);
+      case 3: return schedule<kExactDiv, 3>(x);
+      default: return schedule<kExactDiv, 4>(x);
+    }
+  }
+};
+hipError_t launch_portfolio_cashflow_markov(const KernelArgs &a, const PortfolioCashflowMarkovArgs &x, bool exact_div, uint32_t grid,
+                                            hipStream_t stream) {
+  if (a.stream != 3 || a.mode != SMMC_MODE_GAUSSIAN || a.gauss_std != 1.0f || a.gauss_shift100 != 0.0f) return hipErrorInvalidValue;
+  if (x.p.n_assets < 1 || x.p.n_assets > SMMC_MAX_ASSETS) return hipErrorInvalidValue;
+  if (x.leave_q16[0] > SMMC_REGIME_Q16_ONE || x.leave_q16[1] > SMMC_REGIME_Q16_ONE || x.start1_q16 > SMMC_REGIME_Q16_ONE)
+    return hipErrorInvalidValue;
+  if (a.n_periods == 0 || a.n_periods > SMMC_MAX_CASHFLOW_PERIODS) return hipErrorInvalidValue;
+  if (x.c.schedule && (x.c.stride % 8u != 0u || x.c.stride < a.n_periods)) return hipErrorInvalidValue;
+  const size_t lds = portfolio_cashflow_markov_lds_bytes(a.n_periods, a.n_bins);
+  const WalkKernel<PortfolioCashflowMarkovArgs> kernel =
+      exact_div ? PortfolioCashflowMarkovFamily::get<true>(x) : PortfolioCashflowMarkovFamily::get<false>(x);
+  const hipError_t err = allow_lds(kernel, lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(wave_walk_group_paths(SMMC_MODE_GAUSSIAN)), lds, stream, a, x);
   return hipGetLastError();
 }
 

@@ -33,18 +33,16 @@ int check_request(const smmc_engine *e, const smmc_sim *sim, const smmc_portfoli
 
 // The rule of include/smmc.h (smmc_engine_portfolio_cashflow_divide_kind); DESIGN.md, "Portfolio cash flows", has the
 // proof.  FAST only for the two schedule shapes it covers; everything else is the IEEE divide.
-int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf) {
+// Its two halves: the bounds of this call's own law, and the rule on given bounds (smmc_host.h lends the second).
+int divide_of_bounds(const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf, const double *lo, double hi_max) {
   if (sim->flags & SMMC_FLAG_EXACT_DIV) return SMMC_DIV_EXACT;
   const double cap = sim->initial_capital;
   if (!(cap > 0.0) || !std::isfinite(cap)) return SMMC_DIV_EXACT;
   const uint32_t K = pf->n_assets, P = sim->n_periods;
-  double lo[SMMC_MAX_ASSETS], lo_min = INFINITY, hi_max = 0.0, w_min = INFINITY, h_min = INFINITY;
+  double lo_min = INFINITY, w_min = INFINITY, h_min = INFINITY;
   bool held = false;
   for (uint32_t k = 0; k < K; ++k) {
-    double hi;
-    if (!smmc::portfolio_asset_bounds(e, sim, pf, k, &lo[k], &hi)) return SMMC_DIV_EXACT;
     lo_min = std::min(lo_min, lo[k]);
-    hi_max = std::max(hi_max, hi);
     if (!(pf->weights[k] > 0.0f)) continue;
     const float h0 = sim->initial_capital * pf->weights[k];  // the kernel's own first holding
     if (!(h0 > 0.0f)) return SMMC_DIV_EXACT;  // a weighted asset that starts at 0 would start from a flow's share
@@ -95,6 +93,15 @@ int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio 
   }
   return SMMC_DIV_EXACT;
 }
+int divide_rule(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf) {
+  double lo[SMMC_MAX_ASSETS], hi_max = 0.0;
+  for (uint32_t k = 0; k < pf->n_assets; ++k) {
+    double hi;
+    if (!smmc::portfolio_asset_bounds(e, sim, pf, k, &lo[k], &hi)) return SMMC_DIV_EXACT;
+    hi_max = std::max(hi_max, hi);
+  }
+  return divide_of_bounds(sim, pf, cf, lo, hi_max);
+}
 
 // The launch's arguments and LDS need, and the refusals that follow from them; asked before any device work.
 struct Plan {
@@ -121,6 +128,12 @@ int plan(const smmc_engine *e, const smmc_sim *sim, const smmc_portfolio *pf, co
 }
 
 }  // namespace
+
+namespace smmc {  // what smmc_portfolio_cashflow_regimes.cpp takes of this unit (smmc_host.h)
+int portfolio_cashflow_divide_of_bounds(const smmc_sim *sim, const smmc_portfolio *pf, const smmc_cashflow *cf, const double *lo, double hi_max) {
+  return divide_of_bounds(sim, pf, cf, lo, hi_max);
+}
+}  // namespace smmc
 
 extern "C" {
 
